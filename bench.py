@@ -755,15 +755,32 @@ def secondary(args, pkg, dev, job, emit=True):
         torch.cuda.synchronize()
         if 'reducer_obj' in comm:
             comm['reducer_obj'].launched_during_backward = 0
+    dump_dir = getattr(args, 'dump_outputs', None) if emit and rank == 0 else None
+    last, timed = {}, step
+    if dump_dir and not graphed:
+        def timed():   # keeps the last step's return value for --dump-outputs
+            last['out'] = step()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     job.barrier()
     torch.cuda.synchronize()
     e0.record()
-    elapsed, every = job.timed_steps(step, args.steps)   # barrier + sync both sides, MAX over ranks
+    elapsed, every = job.timed_steps(timed, args.steps)   # barrier + sync both sides, MAX over ranks
     e1.record()
     torch.cuda.synchronize()
     ms = elapsed * 1e3 / args.steps
     dev_ms = e0.elapsed_time(e1) / args.steps
+    dumped = None
+    if dump_dir:
+        # what the caller of the step holds afterwards: its return value, or the gradients it wrote
+        outs = named_tensors(graph_out if graphed else last.get('out'), 'out')
+        if args.workload in ('sweep_bwd', 'sweep_bwd_kitti'):
+            outs = {'grad_cur': g_cur, 'grad_prev': g_prev}
+        elif args.workload == 'voxel_sample_bwd':
+            outs['grad_voxels'] = vox.grad
+        elif args.workload in ('backbone_train', 'stereo_train'):
+            trained = m if args.workload == 'backbone_train' else path
+            outs = {f'grad.{n}': p.grad for n, p in trained.named_parameters() if p.grad is not None}
+        dumped = dump_outputs(dump_dir, outs)
     if comm is not None:
         comm['exposed_exchange_ms'] = round(ms - comm['ms_per_step_no_exchange'], 4)
         if 'reducer_obj' in comm:
@@ -791,7 +808,8 @@ def secondary(args, pkg, dev, job, emit=True):
                    'parallelism': f'dp{world}'},
         'roofline': roof, 'per_rank_ms_per_step': [round(v * 1e3 / args.steps, 4) for v in every],
         **rank_census(job),
-        **({'gradient_exchange': comm} if comm is not None else {})}
+        **({'gradient_exchange': comm} if comm is not None else {}),
+        **({'dump_outputs': {'dir': dump_dir, 'arrays': dumped}} if dumped is not None else {})}
     if graphed:
         line['config']['hip_graph_replay'] = True
     if args.workload.startswith('sweep_bwd'):
@@ -854,6 +872,49 @@ def secondary_block(pkg, sweep, dev, job, budget_s=45.0, traffic=True):
     out['wall_s'] = round(time.perf_counter() - t_start, 1)
     out['traffic_passes_s'] = round(t_traffic, 1)
     return out
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: payload of all arrays together (with the .npy headers < 64 MB)
+
+
+def named_tensors(obj, prefix):
+    """{name: tensor} of every tensor in a step's return value (tensor / tuple / list / dict, nested)"""
+    if isinstance(obj, torch.Tensor):
+        return {prefix: obj}
+    items = obj.items() if isinstance(obj, dict) else enumerate(obj) if isinstance(obj, (list, tuple)) else ()
+    out = {}
+    for k, v in items:
+        out.update(named_tensors(v, f'{prefix}.{k}'))
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, one ``<name>.npy`` per array,
+    float32 (float64 stays float64).  An array larger than its share of DUMP_BUDGET_BYTES is written as
+    ``<name>_sample.npy``: its values at sorted flat indices of the LOGICAL shape (independent of the memory
+    layout) drawn by a generator seeded with 0 -- the same elements for every build at the same shape.
+    Returns {file name: shape}."""
+    arrays = {k: v for k, v in arrays.items() if v is not None and v.numel() > 0}
+    if not arrays:
+        raise RuntimeError('--dump-outputs: the timed step returned no tensor to write')
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        esz = 8 if dt == torch.float64 else 4
+        if t.numel() * esz <= share:
+            a, fname = t.to(dt).cpu().numpy(), name
+        else:
+            g = torch.Generator().manual_seed(0)
+            flat = torch.randint(t.numel(), (share // esz,), generator=g, dtype=torch.int64).sort().values
+            idx = np.unravel_index(flat.numpy(), tuple(t.shape))
+            a = t[tuple(torch.from_numpy(i).to(t.device) for i in idx)].to(dt).cpu().numpy()
+            fname = name + '_sample'
+        np.save(os.path.join(dirname, fname + '.npy'), a)
+        written[fname] = list(a.shape)
+    return written
 
 
 def plant_special(cur, prev, w):
@@ -933,6 +994,9 @@ def main():
     ap.add_argument('--pipeline', type=int, default=0, help='LDS kernel body: 1 serial, 2 pipelined')
     ap.add_argument('--store-align', type=int, default=0, help='LDS kernel: band cuts at multiples of 8|16|32|64 points')
     ap.add_argument('--pair-stores', type=int, default=0, help='4 points per lane: 1 paired 16-byte stores, 2 8-byte stores')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32, a fixed seeded sample of an array too large for the 48 MB budget)")
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -1102,6 +1166,8 @@ def run(args, pkg, sweep, lib, dev, job, explicit):
     census = rank_census(job)   # a collective: every rank takes part
     ms_per_step = elapsed * 1e3 / args.steps
     value = job.value(B, args.steps, elapsed)
+    # the volume the last timed step wrote (before the extras below reuse or free it)
+    dumped = dump_outputs(args.dump_outputs, {'cost_volume': out}) if rank == 0 and args.dump_outputs else None
 
     if rank == 0:
         # everything below is rank 0 on its own, AFTER the job's closing barrier (the other ranks leave): the
@@ -1162,6 +1228,8 @@ def run(args, pkg, sweep, lib, dev, job, explicit):
             **census,
             'part': part,
         }
+        if dumped is not None:
+            line['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         if 'api_build_dfm_cost' in extras:
             # the public API (what DfMBackbone.forward calls): build_dfm_cost with device-resident
             # intrinsics / poses -- pads, inverts and packs them on the device, allocates the
