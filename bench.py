@@ -5,6 +5,11 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W`` prints ONE
 JSON line on rank 0.  For N>1 the driver launches it under
 ``python -m torch.distributed.run`` (one rank per GPU, RCCL).
 
+A plain run does only what the headline needs: set up, warm up, time the K steps, write ``--dump-outputs``,
+print the line.  ``--full`` adds everything else the line can carry, measured before or after the timed steps
+as always: the part probes and SMI readings, the tuning check, the public-API and channels-last rows, the
+in-run HBM counter passes, the secondary rows and the CPU baseline.
+
 A "step" = one pass of the hot path (dfm_plane_sweep_fwd: re-block the two
 feature maps + write the (B,2C,D,H,W) volume) over one batch of B=8 synthetic
 KITTI-shape frame pairs that are already resident in HBM.  The batch shards
@@ -300,9 +305,9 @@ def torch_cpu_sampling(w, prm, depths, orc, budget_s=14.0):
 
 
 def line_extras(args, w, elem, explicit, last_kernel):
-    """names of the reported blocks rank 0 adds to the headline line after the timed region, in order.  A pure
-    function of the command line and the workload -- NOT of the world size: `--gpus 8` prints the fields
-    `--gpus 1` prints (tests/test_distributed_cpu.py holds that)."""
+    """names of the reported blocks rank 0 adds to the headline line after the timed region of a --full run, in
+    order.  A pure function of the command line and the workload -- NOT of the world size: `--gpus 8` prints the
+    fields `--gpus 1` prints (tests/test_distributed_cpu.py holds that)."""
     ex = []
     if not args.channels_last:
         ex.append('api_build_dfm_cost')
@@ -328,7 +333,7 @@ def rank_census(job):
 def secondary(args, pkg, dev, job, emit=True):
     """Other hot-path rows on their config shapes; `value` = passes/s of the op over
     one sample batch, roofline from HIP-event step time (one fused kernel per step).
-    emit=False: return the JSON line's dict instead of printing it (the default run's
+    emit=False: return the JSON line's dict instead of printing it (the --full run's
     ``secondary`` block)."""
     rank, world = job.rank, job.world
     gen = torch.Generator().manual_seed(job.seed(0) // 1000)
@@ -825,7 +830,7 @@ def secondary(args, pkg, dev, job, emit=True):
 
 
 def secondary_block(pkg, sweep, dev, job, budget_s=45.0, traffic=True):
-    """What else the default run witnesses, after the timed headline and never as ``value``: other rows
+    """What else a --full run witnesses, after the timed headline and never as ``value``: other rows
     of SURVEY.md 8a on their config shapes, a few steps each -- the plane-sweep backward at N*, the
     shipped config's strided sweep (config K, NHWC maps) and its backward, FrustumToVoxel's channels-last sampling,
     DfMBackbone.forward and the voxel neck.
@@ -965,7 +970,7 @@ def quick_sweep_row(pkg, sweep, dev, wl, steps, warmup):
                          'frac': round(achieved / HBM_PEAK_GBPS, 4), 'algorithmic_bytes_per_launch': nbytes}}
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
@@ -983,13 +988,17 @@ def main():
                     help='write the volume (B,D,H,W,2C) (memory_format channels_last_3d)')
     ap.add_argument('--no-autotune', action='store_true',
                     help='skip dfm_plane_sweep_autotune (workgroup schedule stays at its default)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: part probes and SMI readings, the tuning '
+                         'check, the public-API and channels-last rows, HBM counter passes, the secondary rows and '
+                         'the CPU baseline (the --no-* options below leave parts of it out)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--reducer', default='none', choices=['none', 'ddp', 'bucket'],
                     help='backbone_train / stereo_train: gradient exchange of the step (DDP, or GradientBucketReducer)')
     ap.add_argument('--traffic-bytes', type=float, default=None,
                     help='HBM bytes per launch from a separate rocprofv3 --pmc pass (default: measured in this run)')
     ap.add_argument('--no-traffic', action='store_true', help='skip the in-run rocprofv3 --pmc passes')
-    ap.add_argument('--no-secondary', action='store_true', help="skip the default run's secondary rows")
+    ap.add_argument('--no-secondary', action='store_true', help="skip the --full run's secondary rows")
     ap.add_argument('--no-smi', action='store_true', help='skip the amd-smi / rocm-smi readings')
     ap.add_argument('--pipeline', type=int, default=0, help='LDS kernel body: 1 serial, 2 pipelined')
     ap.add_argument('--store-align', type=int, default=0, help='LDS kernel: band cuts at multiples of 8|16|32|64 points')
@@ -997,7 +1006,11 @@ def main():
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
                          "(float32, a fixed seeded sample of an array too large for the 48 MB budget)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = arg_parser().parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` is ONE command: no launcher around it -> this process becomes the
@@ -1074,11 +1087,11 @@ def run(args, pkg, sweep, lib, dev, job, explicit):
     # cut of every channel plane left two partial 64-byte writes behind, which some parts absorb and others
     # do not (profiles/archive/r04_c1..c4_*) -- and removed it.  The probes stay as a record of the part: the tile
     # kernel's store pattern replayed as zeros, a linear fill, the shader clock under an FMA load, and what
-    # the SMI tools report under load (tools/part_info.py).
+    # the SMI tools report under load (tools/part_info.py).  --full only.
     torch.cuda.synchronize()
     plane_bytes = w['D'] * desc.h_out * desc.w_out * elem
     part = None
-    if not args.channels_last and plane_bytes % 16 == 0:
+    if args.full and not args.channels_last and plane_bytes % 16 == 0:
         def probe(fn):
             pe0, pe1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             fn()
@@ -1129,8 +1142,8 @@ def run(args, pkg, sweep, lib, dev, job, explicit):
         tuned = sweep.plane_sweep_tuning(desc) or \
             sweep.plane_sweep_autotune(desc, cur, prev, depths, P, Pinv, T, out)
     verified, check_agrees = None, None
-    if tuned is not None and w['dtype'] == 'bf16':
-        # untimed, informational: the library's pick (dfm_plane_sweep_autotune: 4 rounds x 2 launches per
+    if args.full and tuned is not None and w['dtype'] == 'bf16':
+        # untimed, informational (--full): the library's pick (dfm_plane_sweep_autotune: 4 rounds x 2 launches per
         # candidate, median round) next to both tile shapes timed over as many launches as the timed
         # region has.  The bench runs WHAT THE LIBRARY PICKED -- what a build_dfm_cost() user gets -- and
         # reports whether this check agrees (round 2 overrode the library here).
@@ -1172,7 +1185,7 @@ def run(args, pkg, sweep, lib, dev, job, explicit):
     if rank == 0:
         # everything below is rank 0 on its own, AFTER the job's closing barrier (the other ranks leave): the
         # line carries the same fields at every N (line_extras: nothing in it depends on the world size)
-        extras = line_extras(args, w, elem, explicit, lib.dfm_plane_sweep_last_kernel())
+        extras = line_extras(args, w, elem, explicit, lib.dfm_plane_sweep_last_kernel()) if args.full else []
         bytes_per_launch = algorithmic_bytes(w, elem) * B
         avg_kernel_ms = kms.value / max(klaunches.value, 1)
         achieved = bytes_per_launch / (avg_kernel_ms * 1e-3) / 1e9
