@@ -15,7 +15,6 @@ Backward: the input gradient runs in the same MFMA kernel (transposed, mirrored 
 fragments); the weight gradient is torch's convolution backward (MIOpen).
 """
 import ctypes
-import os
 import warnings
 
 import torch
@@ -170,9 +169,6 @@ class _MfmaConvFn(torch.autograd.Function):
             k = weight.shape[1] // 32
             if k == 1:
                 gx = conv3d_k3_c32(gy, pack_conv3d_weights(weight, 0, transposed=True))
-            elif os.environ.get('DFM_C32_CAT') == '1':   # (A/B runs: the round-5 form)
-                halves = [conv3d_k3_c32(gy, pack_conv3d_weights(weight, 32 * i, transposed=True)) for i in range(k)]
-                gx = torch.cat(halves, dim=1).contiguous(memory_format=torch.channels_last_3d)
             else:
                 # the k halves written straight into the (N, D, H, W, 32 k) gradient (dfm_conv3d_k3_c32_fwd_slices)
                 N, _, D, H, W = gy.shape
@@ -289,7 +285,6 @@ class MfmaConv3d(DerivedStateMixin, nn.Conv3d):
 # the output gradient, chunks are summed in fp32.
 # ---------------------------------------------------------------------------------------------
 _OUT_DTYPE_OK = {}  # (op name, device type) -> does op(..., out_dtype=torch.float32) work on this build / backend?
-_SPLIT_LONG_AXIS = os.environ.get('DFM_PLAIN_WGRAD_1X1') != '1'
 
 
 def _product_f32(op, a, b):
@@ -328,7 +323,7 @@ def long_axis_gram(a, b, rows_per_batch=2048):
     step).  Here P is cut into batches of ~``rows_per_batch`` rows -- a batched GEMM of S x (M x N) tiles, fp32
     partial products where the build has ``out_dtype`` -- and the S partials are summed in fp32."""
     P = a.shape[0]
-    S = max(1, min(512, P // max(1, rows_per_batch))) if _SPLIT_LONG_AXIS else 1  # (DFM_PLAIN_WGRAD_1X1=1: A/B runs)
+    S = max(1, min(512, P // max(1, rows_per_batch)))
     while S > 1 and P % S:
         S -= 1
     if S < 4:
@@ -605,7 +600,7 @@ class _MfmaConvTo1Fn(torch.autograd.Function):
         N, _, D, H, W = gy.shape
         lib = _capi.lib()
         direct = (gy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and _is_ndhwc(x) and
-                  _ndhwc_channel_stride(x) == 32 and weight.dtype in _WDT and os.environ.get('DFM_TO1_PADDED_BWD') != '1')
+                  _ndhwc_channel_stride(x) == 32 and weight.dtype in _WDT)
         if direct:
             # round 6 (csrc/conv3d_to1_bwd.hip): both gradients as matrix products over the 27 taps -- no gradient padded
             # to 32 channels (a 118 MB fill + copy), no 32 -> 32 convolution / weight gradient for one useful row
@@ -676,8 +671,8 @@ class MfmaConv3dTo1(DerivedStateMixin, nn.Conv3d):
     def forward(self, x):
         why = self.why_not(x)
         if why is None:
-            # DFM_TO1_C32_FWD=1: the 32 -> 32 kernel on the zero-padded weight (A/B runs)
-            lean = os.environ.get('DFM_TO1_C32_FWD') != '1' and _ndhwc_channel_stride(x) == 32
+            # (other pixel strides: the 32 -> 32 kernel on the zero-padded weight)
+            lean = _ndhwc_channel_stride(x) == 32
             return _MfmaConvTo1Fn.apply(x, self.weight, None if lean else self._packed())
         if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and 'coverage' not in why and
                 _FP32_MODE['mode'] != 'torch' and x.shape[1] == 32 and

@@ -371,11 +371,6 @@ int conv_depth_chunk(int n, int d, int h, int w, int depth_chunk)
         const long long cols = (long long)((w + CV_TW - 1) / CV_TW) * ((h + CV_TH - 1) / CV_TH) * n;
         double best = 1e30;
         dc = d;
-        static const bool old_rule = [] { const char *e = getenv("DFM_CONV_OLD_CHUNK"); return e && e[0] == '1'; }();
-        if (old_rule) {  // (A/B runs: the rounds 1-4 rule)
-            const long long chunks = (4 * 256 + cols - 1) / cols;
-            return std::min((int)std::max<long long>(8, (d + chunks - 1) / chunks), d);
-        }
         for (int c = std::min(d, 4); c <= d; ++c) {
             const long long chunks = (d + c - 1) / c;
             const long long rounds = (cols * chunks + 255) / 256;

@@ -431,15 +431,15 @@ int wgrad_plan(const dfm_conv3d_wgrad_desc *d, WPlan &pl)
             return set_error(DFM_ERR_UNSUPPORTED, "sample larger than 2^31 elements");
     }
     // column mode (COL): row and depth stride 1 (and h stride 1: the item order the kernel relies on), a volume; work
-    // items = columns x chunks of output planes (a chunk's first tile stages all three slices).  DFM_WGRAD_COL=0 keeps a tile per step (A/B runs), DFM_WGRAD_CHUNK=<planes> (tests)
+    // items = columns x chunks of output planes (a chunk's first tile stages all three slices); other shapes take a
+    // tile per step
     pl.col = 0;
     g.dchunk = 1; g.nchunks = g.Do; g.nitems = g.ntiles;
     {
-        const char *e = getenv("DFM_WGRAD_COL");
         // (the kernel takes "the second batch of a lane's items = the new slice + the g rows" from the item order:
         //  3 slices x 4 rows x 4 channel blocks x 20 position groups = 5 items per lane exactly)
         const bool order_ok = 3 * RH * 4 * ((TW + 16) / 4) == 5 * WG_THREADS && WG_BATCH == 3;
-        if (!(e && e[0] == '0') && order_ok && pl.sw == 1 && g.sd == 1 && g.sh == 1 && !pl.flat && g.Do > 1) {
+        if (order_ok && pl.sw == 1 && g.sd == 1 && g.sh == 1 && !pl.flat && g.Do > 1) {
             const long long cols = (long long)g.N * g.tiles_h * g.tiles_w;
             const long long wgs = std::max<long long>(1, 512 / pl.pairs);
             // planes per chunk: the launch is rounds x (planes + the first tile's two extra slices, ~0.7 of a tile)
@@ -453,8 +453,6 @@ int wgrad_plan(const dfm_conv3d_wgrad_desc *d, WPlan &pl)
                 const double cost = (double)rounds * (c + 0.7);
                 if (cost < best - 1e-9) { best = cost; dc = c; }
             }
-            if (const char *c = getenv("DFM_WGRAD_CHUNK")) dc = std::max(1, atoi(c));
-            dc = std::min(dc, g.Do);
             g.dchunk = dc;
             g.nchunks = (g.Do + dc - 1) / dc;
             const long long items = cols * g.nchunks;

@@ -420,7 +420,7 @@ static size_t gather_foot_bytes(const dfm_sweep_desc *d)
 {
     if (d->h_out <= 0 || d->w_out <= 0) return 0;
     const size_t n = (size_t)d->batch * d->num_depths * d->h_out * d->w_out * 12;
-    if (n > ((size_t)2 << 30) || getenv("DFM_GATHER_NO_TABLE")) return 0;
+    if (n > ((size_t)2 << 30)) return 0;
     return (n + 255) & ~(size_t)255;
 }
 

@@ -4,7 +4,6 @@
 ``voxel_convs``."""
 import contextlib
 import ctypes
-import os
 import weakref
 
 import numpy as np
@@ -116,15 +115,14 @@ class _F2vFusedFn(torch.autograd.Function):
 
 
 _GRID_CACHE = {}
-_BWD_GATHER = {'on': os.environ.get('DFM_NO_F2V_GATHER') != '1',
-               # the gradient of a channels-last cost volume in that layout and type (DFM_F2V_PLANAR_GRAD=1: A/B runs)
-               'native': os.environ.get('DFM_F2V_PLANAR_GRAD') != '1'}
+# native: the gradient of a channels-last cost volume in that layout and type
+_BWD_GATHER = {'on': True, 'native': True}
 
 
 @contextlib.contextmanager
 def bwd_gather(on, native=None):
-    """backward by the gather kernel (default) or the pixel-major scatter (A/B runs, tests); ``native=False``: the
-    gather writes the planar fp32 gradient also for a channels-last cost volume"""
+    """backward by the gather kernel (default) or the pixel-major scatter (tests; irregular grids always take it);
+    ``native=False``: the gather writes the planar fp32 gradient also for a channels-last cost volume"""
     prev = dict(_BWD_GATHER)
     _BWD_GATHER['on'] = bool(on)
     if native is not None:

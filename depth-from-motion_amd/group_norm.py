@@ -7,7 +7,6 @@ GroupNorm kernel followed by a separate ReLU.
 touching checkpoints.
 """
 import ctypes
-import os
 import weakref
 
 import torch
@@ -38,7 +37,7 @@ def _f32_params(weight, bias):
     return hit[1], hit[2]
 
 
-_XMASK = os.environ.get('DFM_GN_KEEP_Y') != '1'   # (A/B runs: the backward reads the ReLU mask from the kept output)
+_XMASK = True   # False: the backward reads the ReLU mask from the kept output, as the fused-residual case does (tests)
 
 
 class _GroupNormFn(torch.autograd.Function):

@@ -22,8 +22,6 @@ Three ways to use this package from there, all routed to the HIP kernels:
 """
 import importlib
 
-import os
-
 import numpy as np
 import torch
 from torch import nn
@@ -107,7 +105,7 @@ class DfMStereoPath(nn.Module):
         self.hip_graphs = False
         self._graphed = {}
 
-    two_streams = os.environ.get('DFM_PATH_ONE_STREAM') != '1'
+    two_streams = True   # False: the previous frame's necks on the current stream too
 
     def _run_2d(self, name, module, tensors):
         """module(tensors) -- through a captured hipGraph when ``hip_graphs`` is on and nothing records

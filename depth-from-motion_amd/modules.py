@@ -22,7 +22,6 @@ The 3x3 2-D convolutions of SPPUNetNeck / BEVHourglass run in the same MFMA kern
 along depth); 1x1 convolutions and bilinear up-sampling outside the fused SPP tail are torch ops.
 """
 import ctypes
-import os
 import weakref
 
 import numpy as np
@@ -384,12 +383,8 @@ class DfMBackbone(DerivedStateMixin, nn.Module):
     # node takes the stream that is current when it is CREATED, so `_two_branches` creates the mono parameters'
     # nodes on the main stream before it forks (`_pin_accumulators`): the weight-gradient kernels still run on the
     # side stream, the accumulation -- and every hook -- on the main stream behind the engine's event wait
-    # (tests/test_backward_gpu.py checks the stream the hooks see).  DFM_TRAIN_ONE_STREAM=1 pins one stream.
-    two_streams_training = os.environ.get('DFM_TRAIN_ONE_STREAM') != '1'
+    # (tests/test_backward_gpu.py checks the stream the hooks see).  two_streams = False pins one stream here too.
     _side_streams = {}
-
-    # DFM_BACKBONE_SEQUENTIAL_ISSUE=1: the round-5 issue order (all of the mono stack, then all of the stereo stack)
-    interleaved_issue = os.environ.get('DFM_BACKBONE_SEQUENTIAL_ISSUE') != '1'
 
     def _stack_steps(self, first, second, hgs, pred):
         """one aggregation stack + its prediction head as a generator: ``first()`` produces the stack's input (the
@@ -451,9 +446,7 @@ class DfMBackbone(DerivedStateMixin, nn.Module):
             mo = mono_fn()
             assert len(mo) == 1, 'Only support num_hg=1 for now.'
             return mo, self._pred_head(self.pred_mono[0], mo[0])
-        if not (self.two_streams and device.type == 'cuda' and
-                (self.two_streams_training or not torch.is_grad_enabled()) and
-                not torch.cuda.is_current_stream_capturing()):
+        if not (self.two_streams and device.type == 'cuda' and not torch.cuda.is_current_stream_capturing()):
             return stereo_all(), mono_all()
         main = torch.cuda.current_stream(device)
         side = DfMBackbone._side_streams.get(device)
@@ -470,8 +463,8 @@ class DfMBackbone(DerivedStateMixin, nn.Module):
             t.record_stream(main)
         return (stereo, s_cost), (mono, m_cost)
 
-    # DFM_PRED_UNFUSED=1 keeps the three-launch prediction head at inference too (A/B runs)
-    fused_pred = os.environ.get('DFM_PRED_UNFUSED') != '1'
+    # False keeps the three-launch prediction head at inference too (the reference of the fused head's tests)
+    fused_pred = True
 
     def _pred_head(self, seq, x):
         """ConvModule(32 -> 32, GN, ReLU) -> Conv3d(32 -> 1) (dfm_backbone.py:120-127).  Inference on the bf16 NDHWC
@@ -490,7 +483,7 @@ class DfMBackbone(DerivedStateMixin, nn.Module):
         return seq(x)
 
     def _interleave_ok(self, device):
-        return (self.interleaved_issue and self.two_streams and device.type == 'cuda' and
+        return (self.two_streams and device.type == 'cuda' and
                 not torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing())
 
     def _pin_accumulators(self):
@@ -567,9 +560,10 @@ class DfMBackbone(DerivedStateMixin, nn.Module):
             lambda: self._aggregate(self.dres0_mono, self.dres1_mono, self.hg_mono, cost_cur), cost_raw.device)
         return self._predict(*stereo, *mono)
 
-    # DFM_GATE_TORCH=1 keeps the torch sequence of the gate at inference too (A/B runs)
-    fused_gate = os.environ.get('DFM_GATE_TORCH') != '1'
-    mfma_gate = os.environ.get('DFM_GATE_VALU') != '1'
+    # fused_gate = False keeps the torch sequence of the gate at inference too, mfma_gate = False the VALU kernel for
+    # bf16 costs as well (the references of the gate's tests)
+    fused_gate = True
+    mfma_gate = True
 
     def _gate_fused(self, s_cost, m_cost):
         """cat + Conv2d(2D -> D, 1x1) + sigmoid + blend (dfm_backbone.py:136-141) as one launch
@@ -585,7 +579,7 @@ class DfMBackbone(DerivedStateMixin, nn.Module):
         lib = _capi.lib()
         out = torch.empty_like(s_cost)
         # bf16 costs and a bf16 weight (the fast path's model): the product on the matrix cores (round 6; every
-        # bf16 x bf16 product is exact, sums in fp32) -- DFM_GATE_VALU=1 keeps the VALU kernel (A/B runs)
+        # bf16 x bf16 product is exact, sums in fp32); other types take the VALU kernel
         mfma = (self.mfma_gate and s_cost.dtype == torch.bfloat16 and w.dtype == torch.bfloat16)
         key = (w._version, w.data_ptr(), str(w.device), w.dtype, mfma)
         with torch.cuda.device(s_cost.device):
@@ -937,7 +931,7 @@ def _conv_norm_2d(seq, x, residual=None, relu=False):
         scale, shift = seq.__dict__['_fold']
         return conv.forward_fused(x, scale, shift, residual=residual, relu=relu)
     y = conv(x)
-    if isinstance(norm, nn.modules.batchnorm._BatchNorm) and _BN2D_FUSED:
+    if isinstance(norm, nn.modules.batchnorm._BatchNorm):
         # training: the batch statistics, the normalisation, the residual and the ReLU in the fused GroupNorm kernels on
         # the NHWC map as it lies (round 6; MIOpen's training BatchNorm + separate add / ReLU passes were 0.9 ms of
         # the DfMStereoPath step) -- None when it does not apply (eval mode, NCHW, SyncBatchNorm across ranks)
@@ -950,9 +944,7 @@ def _conv_norm_2d(seq, x, residual=None, relu=False):
     return F.relu(y) if relu else y
 
 
-_BN2D_FUSED = os.environ.get('DFM_BN2D_TORCH') != '1'   # (A/B runs: torch's training BatchNorm in the 2-D necks)
 _INTERP_MATRICES = {}
-_BILINEAR_GATHER = os.environ.get('DFM_BILINEAR_MATMUL') != '1'   # (A/B runs: the matrix-product backward)
 
 
 def _interp_matrix(n_in, n_out, align_corners, scale, device):
@@ -1017,7 +1009,7 @@ class _BilinearResizeFn(torch.autograd.Function):
         a_h = _interp_matrix(h_in, h_out, ac, scale, gy.device)            # (h_out, h_in)
         vec = 16 // gy.element_size()
         if (gy.stride(1) == 1 and C % vec == 0 and gy.is_contiguous(memory_format=torch.channels_last) and
-                gy.dtype in (torch.float32, torch.bfloat16) and _BILINEAR_GATHER):
+                gy.dtype in (torch.float32, torch.bfloat16)):
             # NHWC: the gather kernel (csrc/bilinear_bwd.hip) -- a lane per input pixel and 16-byte channel vector walks
             # the few output pixels that interpolate from it (an up-sampling by 2 has at most 4 x 4)
             ri, rw, kh = _interp_table(h_in, h_out, ac, scale, gy.device)
@@ -1089,14 +1081,12 @@ def _channels_last_2d(module, feats):
     NHWC tensor are matrix products, GroupNorm is the HIP kernel in either layout and the bilinear resizes
     have a matrix-product backward (bilinear_resize) -- the three things that made torch's NHWC training
     path 2.1 s per DfMStereoPath step in round 3 (MIOpen's naive NHWC convolutions, ATen's channels-last
-    bilinear backward; profiles/archive/r03_c43_*).  ``DFM_TRAIN_NCHW=1`` (or ``module.train_nhwc = False``) keeps the
-    round-3 behaviour: NCHW between the layers, each MFMA convolution converting its operands."""
+    bilinear backward; profiles/archive/r03_c43_*).  An fp32 model trains NCHW: its 3x3 convolutions are torch's."""
     if not feats[0].is_cuda:
         return feats
     train = torch.is_grad_enabled() and (module.training or any(f.requires_grad for f in feats))
     # (an fp32 model's 3x3 convolutions are torch's: keep them away from MIOpen's NHWC kernels)
-    nhwc = not train or (feats[0].dtype == torch.bfloat16 and
-                         module.__dict__.get('train_nhwc', os.environ.get('DFM_TRAIN_NCHW') != '1'))
+    nhwc = not train or feats[0].dtype == torch.bfloat16
     want = torch.channels_last if nhwc else torch.contiguous_format
     if module.__dict__.get('_weights_format') is not want:
         module.to(memory_format=want)

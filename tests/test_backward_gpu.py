@@ -237,7 +237,7 @@ def test_mv_lifting_backward(pkg, case):
     np.testing.assert_allclose(fg.grad[0].cpu().numpy(), fr.grad.numpy(), **TOL)
 
 
-def test_backbone_two_stream_training_hooks_see_the_main_stream(pkg):
+def test_backbone_two_streams_in_training_hooks_see_the_main_stream(pkg):
     """DfMBackbone trains its mono stack on a side HIP stream (modules.DfMBackbone._two_branches).  Gradient
     hooks -- DistributedDataParallel's reducer, parallel.GradientBucketReducer -- order their work against the
     stream that is current INSIDE the hook only, so every parameter's AccumulateGrad (and with it every hook)
@@ -274,7 +274,7 @@ def test_backbone_two_stream_training_hooks_see_the_main_stream(pkg):
         torch.cuda.synchronize()
         return {n: p.grad.float().clone() for n, p in m.named_parameters() if p.grad is not None}
 
-    assert m.two_streams_training
+    assert m.two_streams
     g2 = run(True)
     assert mods.DfMBackbone._side_streams.get(dev) is not None, 'the side stream was never used'
     off = [n for n, ok in seen.items() if not ok]

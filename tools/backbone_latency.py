@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Latency of ONE DfMBackbone.forward at config K (bf16 NDHWC, synchronised after every forward -- bench.py times
-back-to-back forwards, where the host runs ahead of the device): the two stacks issued alternately, the whole mono
-stack first (round 5), one stream.  GPU box.  usage: python tools/backbone_latency.py"""
+back-to-back forwards, where the host runs ahead of the device): the two stacks on two streams, issued alternately,
+and on one stream.  GPU box.  usage: python tools/backbone_latency.py"""
 import importlib, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.getcwd())
@@ -25,8 +25,6 @@ def lat(n=40):
         for _ in range(n):
             t0 = time.perf_counter(); m(cur, prev, [meta]); torch.cuda.synchronize(); ts.append(time.perf_counter() - t0)
     return np.median(ts) * 1e3
-for mode in (True, False, True, False):
-    m.interleaved_issue = mode
-    print('interleaved' if mode else 'sequential ', 'single-forward latency (sync per forward): %.3f ms' % lat())
-m.two_streams = False
-print('one stream  single-forward latency: %.3f ms' % lat())
+for two in (True, False, True, False):
+    m.two_streams = two
+    print('two streams' if two else 'one stream ', 'single-forward latency (sync per forward): %.3f ms' % lat())
