@@ -466,9 +466,10 @@ class _ChannelSplitFn(torch.autograd.Function):
     cost volume feeds dres0 whole and dres0_mono by its first C channels, dfm_backbone.py:175,189; DfMNeck likewise,
     dfm_neck.py:78-84).  As two separate uses the slice's gradient came back as a zero-filled tensor of x's size with
     the slice copied in (_ChannelSliceFn) and the engine added the two full-size gradients: a fill, a copy and a
-    full-size addition (0.2 ms per training step at config K).  Here the backward receives both gradients and adds
-    the slice's INTO the whole tensor's, in place, over the slice's channels only.  (The whole tensor's gradient is
-    the fresh result of its single consumer's backward; nothing else holds it.)"""
+    full-size addition (0.2 ms per training step at config K).  Here the backward receives both gradients and returns
+    a copy of the whole tensor's (same layout) with the slice's added over the slice's channels only.  (A copy, not
+    an in-place add: the whole tensor's gradient may be another tensor's gradient too -- a consumer such as
+    ``x_all + z`` hands the same tensor to x_all and to z.)"""
 
     @staticmethod
     def forward(ctx, x, lo, hi):
@@ -486,13 +487,14 @@ class _ChannelSplitFn(torch.autograd.Function):
             g_full[:, lo:hi] = g_part
             return g_full, None, None
         if g_part is not None:
+            g_full = g_full.clone(memory_format=torch.preserve_format)
             g_full[:, lo:hi] += g_part.to(g_full.dtype)
         return g_full, None, None
 
 
 def channel_split(x, lo, hi):
     """``(x, x[:, lo:hi])`` for the two consumers of a channels-last 5-D GPU tensor under autograd: one backward node
-    that adds the slice's gradient into the whole tensor's in place (see _ChannelSplitFn); plain views otherwise"""
+    that adds the slice's gradient into a copy of the whole tensor's (see _ChannelSplitFn); plain views otherwise"""
     if x.is_cuda and x.dim() == 5 and x.requires_grad and torch.is_grad_enabled() and \
             x.is_contiguous(memory_format=torch.channels_last_3d) and not x.is_contiguous():
         return _ChannelSplitFn.apply(x, lo, hi)

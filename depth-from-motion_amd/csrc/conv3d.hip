@@ -489,6 +489,9 @@ static int conv_c32_impl(int32_t n, int32_t d, int32_t h, int32_t w, const void 
     if (stats && out_f32) return set_error(DFM_ERR_INVALID_ARG, "statistics are taken of the bf16 output");
     if (n <= 0 || d <= 0 || h <= 0 || w <= 0) return set_error(DFM_ERR_INVALID_ARG, "non-positive size");
     if (!x || !packed_weights || !out) return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
+    // x is staged in 16-byte LDS-DMA pieces; the epilogue stores 16-byte vectors (bf16 and fp32) and reads acc_in in them
+    if ((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)acc_in)) & 15)
+        return set_error(DFM_ERR_INVALID_ARG, "x, out and acc_in must be 16-byte aligned");
     if ((long long)h * w * x_channel_stride * 2 >= (1ll << 31)) return set_error(DFM_ERR_UNSUPPORTED, "depth plane too large");
     if (n > 65535) return set_error(DFM_ERR_UNSUPPORTED, "batch > 65535");
     ConvGeom g;

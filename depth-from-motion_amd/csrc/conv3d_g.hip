@@ -835,6 +835,9 @@ static int conv3d_g_launch(const dfm_conv3d_desc *desc, const void *x, const voi
     const int rc = g_check(desc);
     if (rc != DFM_OK) return rc;
     if (!x || !packed_weights || !out) return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
+    // x is staged in 16-byte LDS-DMA pieces, the epilogues store (and read the residual in) 16-byte vectors
+    if ((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)residual)) & 15)
+        return set_error(DFM_ERR_INVALID_ARG, "x, out and residual must be 16-byte aligned");
     if ((scale == nullptr) != (shift == nullptr))
         return set_error(DFM_ERR_INVALID_ARG, "scale and shift come together");
     GPlan pl;

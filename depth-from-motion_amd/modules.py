@@ -549,7 +549,7 @@ class DfMBackbone(DerivedStateMixin, nn.Module):
             img_scale_factor=meta0.get('scale_factor', [1.0])[0],
             memory_format=self.volume_memory_format)
         # the volume's two consumers: dres0 (whole) and dres0_mono (the cur half) -- one autograd node whose backward adds
-        # the half's gradient into the whole volume's in place (conv3d.channel_split)
+        # the half's gradient into a copy of the whole volume's (conv3d.channel_split)
         cost_all, cost_cur = channel_split(cost_raw, 0, self.in_channels)
         if self._interleave_ok(cost_raw.device):
             stereo, mono = self._two_stacks_interleaved(

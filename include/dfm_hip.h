@@ -688,6 +688,8 @@ DFM_API int dfm_conv3d_k3_c32_pack_weights(const void *weight, int32_t weight_dt
  *           channel, producing wave) -- the per-channel GroupNorm statistics of the layer that
  *           follows, consumed by dfm_group_norm_apply_channels_last (bf16 output only)
  * fp32 accumulation over the 27 x 32 products of a voxel (v_mfma_f32_32x32x16_bf16).
+ * x, acc_in and out must be 16-byte aligned (16-byte loads and stores): DFM_ERR_INVALID_ARG otherwise,
+ * before any HIP call.  The same holds for dfm_conv3d_k3_c32_fwd_strided and _fwd_slices.
  */
 DFM_API int dfm_conv3d_k3_c32_stats_splits(int32_t n, int32_t d, int32_t h, int32_t w,
                                            int32_t depth_chunk);
@@ -807,6 +809,8 @@ DFM_API int dfm_conv3d_g_pack_weights_2d(const void *weight, int32_t weight_dtyp
  *            eval mode, or a bias) applied to the fp32 accumulator
  * residual : NULL, or (n, od, oh, ow, cout) bf16 added after scale / shift (ResModule identity)
  * out      : (n, od, oh, ow, cout) bf16; order: scale/shift -> + residual -> ReLU -> round to bf16
+ * x, residual and out must be 16-byte aligned (x is staged in 16-byte pieces, the epilogue reads and
+ * stores 16-byte vectors): DFM_ERR_INVALID_ARG otherwise, before any HIP call.
  */
 DFM_API int dfm_conv3d_g_fwd(const dfm_conv3d_desc *desc, const void *x, const void *packed_weights,
                              const float *scale, const float *shift, const void *residual,
@@ -821,7 +825,7 @@ DFM_API int dfm_conv3d_g_fwd(const dfm_conv3d_desc *desc, const void *x, const v
  * Either way: what nn.Conv3d / ConvTranspose3d (dfm_backbone.py:175-201, conv_modules.py:73-149,
  * imvoxel_neck.py:26-55) compute at the reference's default precision, without MIOpen.  A non-finite
  * operand value travels in the first piece only (its remainders are zero, not Inf - Inf).
- * desc->relu must be 0; no scale / shift / residual. */
+ * desc->relu must be 0; no scale / shift / residual.  x, acc_in and out must be 16-byte aligned. */
 DFM_API int dfm_conv3d_g_fwd_f32(const dfm_conv3d_desc *desc, const void *x, const void *packed_weights,
                                  const float *acc_in, float *out, void *stream);
 /* The tiling dfm_conv3d_g_fwd uses for desc: {pixel fragments per wave, channel fragments per
