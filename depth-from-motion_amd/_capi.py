@@ -109,6 +109,11 @@ EXPORTS = (
     'dfm_group_norm_bwd',
     'dfm_group_norm_bwd_channels_last',
     'dfm_group_norm_bwd_channels_last_xmask',
+    'dfm_batch_norm_workspace_bytes',
+    'dfm_batch_norm_stats_channels_last',
+    'dfm_batch_norm_apply_gathered_channels_last',
+    'dfm_batch_norm_bwd_reduce_channels_last',
+    'dfm_batch_norm_bwd_apply_channels_last',
 )
 
 
@@ -454,6 +459,19 @@ def lib():
     h.dfm_group_norm_bwd_channels_last.restype = ctypes.c_int
     h.dfm_group_norm_bwd_channels_last.argtypes = [i32, i32, i64, i32, i32, i32, vp, vp, vp, fp, fp, fp, vp, vp, fp,
                                                    fp, vp, sz, vp]
+    h.dfm_batch_norm_workspace_bytes.restype = sz
+    h.dfm_batch_norm_workspace_bytes.argtypes = [i32, i64]
+    h.dfm_batch_norm_stats_channels_last.restype = ctypes.c_int
+    h.dfm_batch_norm_stats_channels_last.argtypes = [i32, i64, i32, vp, fp, vp, sz, vp]
+    h.dfm_batch_norm_apply_gathered_channels_last.restype = ctypes.c_int
+    h.dfm_batch_norm_apply_gathered_channels_last.argtypes = [i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, vp, fp,
+                                                              fp, fp, vp]
+    h.dfm_batch_norm_bwd_reduce_channels_last.restype = ctypes.c_int
+    h.dfm_batch_norm_bwd_reduce_channels_last.argtypes = [i32, i64, i32, i32, vp, vp, vp, fp, fp, fp, fp, fp, vp, sz,
+                                                          vp]
+    h.dfm_batch_norm_bwd_apply_channels_last.restype = ctypes.c_int
+    h.dfm_batch_norm_bwd_apply_channels_last.argtypes = [i32, i64, i32, i32, vp, vp, vp, fp, fp, fp, fp, fp, fp, vp,
+                                                         vp, vp, sz, vp]
     _lib = h
     return h
 

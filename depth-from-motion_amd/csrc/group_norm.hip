@@ -725,6 +725,71 @@ __global__ __launch_bounds__(256) void gn_coefficients_kernel(const float *__res
     }
 }
 
+// ---- BatchNorm across ranks (SyncBatchNorm at world > 1) ------------------------------------------------------
+// The channels-last BatchNorm of one rank's shard is the GroupNorm above with n = 1, groups = C, spatial = rows; the
+// entry points below stop between the local reduction and the normalisation so that the caller can exchange a
+// payload whose size depends on C alone.
+
+// gathered [world][C][3] (count, mean, M2 per rank and channel) -> merged [C][3]: Chan's merge in rank order, count-0
+// entries skipped by merge(); one thread per channel, so every rank that merges the same payload gets the same bits
+__global__ __launch_bounds__(256) void bn_merge_gathered_kernel(const float *__restrict__ gathered, int world, int C,
+                                                                float *__restrict__ merged)
+{
+    const int c = threadIdx.x;
+    if (c >= C) return;
+    Moments r = {0.0f, 0.0f, 0.0f};
+    for (int k = 0; k < world; ++k) {
+        const float *p = gathered + ((size_t)k * C + c) * 3;
+        r = merge(r, Moments{p[0], p[1], p[2]});
+    }
+    float *o = merged + (size_t)c * 3;
+    o[0] = r.n; o[1] = r.mean; o[2] = r.m2;
+}
+
+// backward partials [C][splits][2] (gn_bwd_stats_cl_kernel, n = 1) -> sums [2][C]: row 0 sum(dy'), row 1
+// sum(dy' * xhat); one wave per channel, a fixed order of additions, plain stores
+__global__ __launch_bounds__(64) void bn_bwd_sum_kernel(const float *__restrict__ partial, int C, int splits,
+                                                        float *__restrict__ sums)
+{
+    const int c = blockIdx.x;
+    float a = 0.0f, b = 0.0f;
+    for (int k = threadIdx.x; k < splits; k += 64) {
+        const float *p = partial + ((size_t)c * splits + k) * 2;
+        a += p[0]; b += p[1];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
+    if (threadIdx.x == 0) { sums[c] = a; sums[C + c] = b; }
+}
+
+// gn_bwd_coef_kernel's coefficients for one sample, groups = C, from sums over ALL ranks and the global count:
+// dx = rs * (gm * g - Am - xh * Bm) = k1 g + k2 x + k3, Am = gm * G1 / M, Bm = gm * G2 / M
+__global__ __launch_bounds__(256) void bn_bwd_coef_kernel(const float *__restrict__ sums,
+                                                          const float *__restrict__ count, int C,
+                                                          const float *__restrict__ mean,
+                                                          const float *__restrict__ rstd,
+                                                          const float *__restrict__ gamma, float *__restrict__ coef)
+{
+    const int c = threadIdx.x;
+    if (c >= C) return;
+    const float invL = 1.0f / count[0];
+    const float A = gamma[c] * sums[c], B = gamma[c] * sums[C + c];
+    const float Am = A * invL, Bm = B * invL;
+    const float mu = mean[c], rs = rstd[c];
+    float *o = coef + (size_t)c * 3;
+    o[0] = rs * gamma[c];
+    o[1] = -rs * rs * Bm;
+    o[2] = rs * (rs * mu * Bm - Am);
+}
+
+// the shape checks every BatchNorm entry point shares: C whole 16-byte vectors, a power of two of them, C <= 256
+bool bn_channels_ok(int32_t c, int32_t dtype)
+{
+    const int vec = dtype == DFM_BF16 ? 8 : 4;
+    const int nvb = c / vec;
+    return c % vec == 0 && c <= 256 && (nvb & (nvb - 1)) == 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1014,6 +1079,147 @@ DFM_API int dfm_group_norm_bwd_channels_last_xmask(int32_t n, int32_t c, int64_t
     if (!beta) return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     return gn_bwd_cl_impl(n, c, spatial, groups, dtype, 1, grad_y, x, nullptr, mean, rstd, gamma, beta, grad_x,
                           nullptr, grad_gamma, grad_beta, workspace, workspace_bytes, stream);
+}
+
+// ---- BatchNorm across ranks -------------------------------------------------------------------------------------
+
+DFM_API size_t dfm_batch_norm_workspace_bytes(int32_t c, int64_t rows)
+{
+    if (c <= 0 || c > 256 || rows < 0) return 0;
+    // forward partials (c * splits * 3, splits <= 2048) or backward partials (c * GN_BW_SPLITS * 2) + coefficients
+    const size_t fw = (size_t)c * 2048 * 3, bw = (size_t)c * (GN_BW_SPLITS * 2 + 3);
+    return ((fw > bw ? fw : bw) * sizeof(float) + 255) & ~(size_t)255;
+}
+
+DFM_API int dfm_batch_norm_stats_channels_last(int32_t c, int64_t rows, int32_t dtype, const void *x, float *stats,
+                                               void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (c <= 0 || rows < 0) return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_batch_norm_stats_channels_last");
+    if (dtype != DFM_F32 && dtype != DFM_BF16)
+        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if ((rows > 0 && !x) || !stats || !workspace) return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
+    if (workspace_bytes < dfm_batch_norm_workspace_bytes(c, rows))
+        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_batch_norm_workspace_bytes");
+    if (!bn_channels_ok(c, dtype) || ((uintptr_t)x & 15))
+        return set_error(DFM_ERR_UNSUPPORTED,
+                         "channels-last BatchNorm needs C = 16-byte vectors x a power of two, C <= 256");
+    // rows == 0: one workgroup that loads nothing writes a count-0 partial, merged to (0, 0, 0)
+    const int splits = pick_splits_cl(rows * c);
+    hipStream_t st = (hipStream_t)stream;
+    float *partial = (float *)workspace;
+    if (dtype == DFM_F32)
+        hipLaunchKernelGGL(gn_stats_cl_kernel<float>, dim3(splits, 1), dim3(256), 0, st, (const float *)x,
+                           (long long)rows, c, c, splits, partial);
+    else
+        hipLaunchKernelGGL(gn_stats_cl_kernel<bf16_t>, dim3(splits, 1), dim3(256), 0, st, (const bf16_t *)x,
+                           (long long)rows, c, c, splits, partial);
+    hipLaunchKernelGGL(gn_merge_partials_kernel, dim3(c), dim3(256), 0, st, partial, splits, stats);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    return DFM_OK;
+}
+
+DFM_API int dfm_batch_norm_apply_gathered_channels_last(int32_t c, int64_t rows, int32_t world, float eps,
+                                                        int32_t dtype, int32_t relu, const void *x,
+                                                        const float *gamma, const float *beta, const void *residual,
+                                                        const float *gathered, void *y, float *mean, float *rstd,
+                                                        float *moments, void *stream)
+{
+    if (c <= 0 || rows < 0 || world <= 0)
+        return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_batch_norm_apply_gathered_channels_last");
+    if (dtype != DFM_F32 && dtype != DFM_BF16)
+        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if ((rows > 0 && (!x || !y)) || !gamma || !beta || !gathered || !mean || !rstd || !moments)
+        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
+    if (!bn_channels_ok(c, dtype) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)residual & 15))
+        return set_error(DFM_ERR_UNSUPPORTED,
+                         "channels-last BatchNorm needs C = 16-byte vectors x a power of two, C <= 256");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_merge_gathered_kernel, dim3(1), dim3(256), 0, st, gathered, world, c, moments);
+    // gn_apply_cl_kernel with one merged partial per channel: the arithmetic of the single-process pass
+    const int asplits = pick_splits_cl(rows * c);
+    if (dtype == DFM_F32)
+        hipLaunchKernelGGL(gn_apply_cl_kernel<float>, dim3(asplits, 1), dim3(256), 0, st, (const float *)x,
+                           (long long)rows, c, c, asplits, eps, moments, gamma, beta, relu, (float *)y, mean, rstd, 1,
+                           (const float *)residual);
+    else
+        hipLaunchKernelGGL(gn_apply_cl_kernel<bf16_t>, dim3(asplits, 1), dim3(256), 0, st, (const bf16_t *)x,
+                           (long long)rows, c, c, asplits, eps, moments, gamma, beta, relu, (bf16_t *)y, mean, rstd,
+                           1, (const bf16_t *)residual);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    return DFM_OK;
+}
+
+DFM_API int dfm_batch_norm_bwd_reduce_channels_last(int32_t c, int64_t rows, int32_t dtype, int32_t relu,
+                                                    const void *grad_y, const void *x, const void *y,
+                                                    const float *mean, const float *rstd, const float *gamma,
+                                                    const float *beta, float *sums, void *workspace,
+                                                    size_t workspace_bytes, void *stream)
+{
+    const bool xmask = relu && !y && beta;
+    if (c <= 0 || rows < 0)
+        return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_batch_norm_bwd_reduce_channels_last");
+    if (dtype != DFM_F32 && dtype != DFM_BF16)
+        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if ((rows > 0 && (!grad_y || !x)) || (relu && !y && !beta) || !mean || !rstd || !gamma || !sums || !workspace)
+        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
+    if (workspace_bytes < dfm_batch_norm_workspace_bytes(c, rows))
+        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_batch_norm_workspace_bytes");
+    if (!bn_channels_ok(c, dtype) || ((uintptr_t)x & 15) || ((uintptr_t)grad_y & 15) || ((uintptr_t)y & 15))
+        return set_error(DFM_ERR_UNSUPPORTED,
+                         "channels-last BatchNorm needs C = 16-byte vectors x a power of two, C <= 256");
+    const int splits = std::min(GN_BW_SPLITS, pick_splits_cl(rows * c));
+    hipStream_t st = (hipStream_t)stream;
+    float *partial = (float *)workspace;
+#define BN_RED(T_, X_)                                                                                            \
+    hipLaunchKernelGGL((gn_bwd_stats_cl_kernel<T_, X_>), dim3(splits, 1), dim3(256), 0, st, (const T_ *)grad_y,   \
+                       (const T_ *)x, (const T_ *)y, (long long)rows, c, c, splits, relu, mean, rstd, gamma, beta, \
+                       partial)
+    if (dtype == DFM_F32) { if (xmask) BN_RED(float, true); else BN_RED(float, false); }
+    else { if (xmask) BN_RED(bf16_t, true); else BN_RED(bf16_t, false); }
+#undef BN_RED
+    hipLaunchKernelGGL(bn_bwd_sum_kernel, dim3(c), dim3(64), 0, st, partial, c, splits, sums);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    return DFM_OK;
+}
+
+DFM_API int dfm_batch_norm_bwd_apply_channels_last(int32_t c, int64_t rows, int32_t dtype, int32_t relu,
+                                                   const void *grad_y, const void *x, const void *y,
+                                                   const float *mean, const float *rstd, const float *gamma,
+                                                   const float *beta, const float *sums, const float *count,
+                                                   void *grad_x, void *grad_residual, void *workspace,
+                                                   size_t workspace_bytes, void *stream)
+{
+    const bool xmask = relu && !y && beta;
+    if (c <= 0 || rows < 0)
+        return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_batch_norm_bwd_apply_channels_last");
+    if (dtype != DFM_F32 && dtype != DFM_BF16)
+        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if ((rows > 0 && (!grad_y || !x || !grad_x)) || (relu && !y && !beta) || !mean || !rstd || !gamma || !sums ||
+        !count || !workspace)
+        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
+    if (workspace_bytes < dfm_batch_norm_workspace_bytes(c, rows))
+        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_batch_norm_workspace_bytes");
+    if (!bn_channels_ok(c, dtype) || ((uintptr_t)x & 15) || ((uintptr_t)grad_y & 15) || ((uintptr_t)grad_x & 15) ||
+        ((uintptr_t)y & 15) || ((uintptr_t)grad_residual & 15))
+        return set_error(DFM_ERR_UNSUPPORTED,
+                         "channels-last BatchNorm needs C = 16-byte vectors x a power of two, C <= 256");
+    const int asplits = pick_splits_cl(rows * c);
+    hipStream_t st = (hipStream_t)stream;
+    float *coef = (float *)workspace;
+    hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3(1), dim3(256), 0, st, sums, count, c, mean, rstd, gamma, coef);
+#define BN_BA(T_, X_)                                                                                             \
+    hipLaunchKernelGGL((gn_bwd_apply_cl_kernel<T_, X_>), dim3(asplits, 1), dim3(256), 0, st, (const T_ *)grad_y,  \
+                       (const T_ *)x, (const T_ *)y, (long long)rows, c, c, asplits, relu, coef, mean, rstd, gamma, \
+                       beta, (T_ *)grad_x, (T_ *)grad_residual)
+    if (dtype == DFM_F32) { if (xmask) BN_BA(float, true); else BN_BA(float, false); }
+    else { if (xmask) BN_BA(bf16_t, true); else BN_BA(bf16_t, false); }
+#undef BN_BA
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    return DFM_OK;
 }
 
 }  // extern "C"

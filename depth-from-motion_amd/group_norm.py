@@ -192,13 +192,211 @@ class HipGroupNorm(nn.GroupNorm):
         return torch.relu_(y) if relu else y
 
 
+def _channels_ok(x):
+    vec = 16 // x.element_size() if x.dtype in _DTYPES else 0
+    c = x.shape[1] if x.dim() >= 2 else 0
+    return bool(vec) and 0 < c <= 256 and c % vec == 0 and ((c // vec) & (c // vec - 1)) == 0
+
+
+def sync_batch_norm_eligible(bn, x):
+    """Whether an nn.SyncBatchNorm at world size > 1 runs ``x`` through the fused cross-rank kernels.  The answer must
+    be the same on every rank -- a rank that took torch's SyncBatchNorm while another took this path would issue
+    different collectives and hang the job -- so it looks only at what the ranks share: the module, dtype, C, rank
+    and channels-last-ness read from the channel stride (1 in a channels-last tensor whatever its batch size, spatial
+    extent or storage offset, an empty shard included; H * W in an NCHW one).  Never the batch size, spatial extent,
+    contiguity or alignment of the local shard; those are fixed by a copy instead.  (An NCHW map of 1 x 1 pixels has
+    channel stride 1 as well: a model whose SyncBatchNorm inputs are NCHW must not hand one rank a 1 x 1 map.)"""
+    return bool(bn.training and bn.affine and bn.track_running_stats and x.dim() in (4, 5) and _channels_ok(x) and
+                x.stride(1) == 1)
+
+
+def _sync_world(bn):
+    """the process group of a SyncBatchNorm that needs statistics across ranks, else None"""
+    if isinstance(bn, nn.SyncBatchNorm) and torch.distributed.is_available() and torch.distributed.is_initialized() \
+            and torch.distributed.get_world_size() > 1:
+        return bn.process_group if bn.process_group is not None else torch.distributed.group.WORLD
+    return None
+
+
+def _memory_format(x):
+    return torch.channels_last_3d if x.dim() == 5 else torch.channels_last
+
+
+def _dense(t, fmt):
+    """t channels-last contiguous and 16-byte aligned (a copy only when it is not: a slice, an odd storage offset)"""
+    t = t.contiguous(memory_format=fmt)
+    if t.data_ptr() % 16:
+        t = t.clone(memory_format=fmt)
+    return t
+
+
+def _nullable(t):
+    return _ptr(t) if t is not None and t.numel() else None
+
+
+def bn_stats(x):
+    """dfm_batch_norm_stats_channels_last: this rank's payload, fp32 (C, 3) (count, mean, M2) per channel, of a
+    channels-last contiguous, 16-byte aligned (N, C, *spatial) tensor (N may be 0)"""
+    lib = _capi.lib()
+    c, rows = x.shape[1], x.numel() // x.shape[1]
+    nbytes = lib.dfm_batch_norm_workspace_bytes(c, rows)
+    ws = _Workspace.get(x.device, nbytes)
+    out = torch.empty(c, 3, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _capi.check(lib.dfm_batch_norm_stats_channels_last(c, rows, _DTYPES[x.dtype], _nullable(x), _ptr(out),
+                                                           _ptr(ws), nbytes, _stream_ptr(x.device)))
+    return out
+
+
+def bn_apply_gathered(x, gathered, w32, b32, eps, relu, residual=None):
+    """dfm_batch_norm_apply_gathered_channels_last: gathered (world, C, 3) rank-ordered payloads [device] ->
+    (y, mean, rstd, moments); y = relu?(bn(x) + residual), moments (C, 3) the global (count, mean, M2)"""
+    lib = _capi.lib()
+    c, rows = x.shape[1], x.numel() // x.shape[1]
+    y = torch.empty_like(x)
+    mean = torch.empty(c, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    moments = torch.empty(c, 3, dtype=torch.float32, device=x.device)
+    gathered = gathered.contiguous()
+    with torch.cuda.device(x.device):
+        _capi.check(lib.dfm_batch_norm_apply_gathered_channels_last(
+            c, rows, gathered.shape[0], float(eps), _DTYPES[x.dtype], int(relu), _nullable(x), _ptr(w32), _ptr(b32),
+            _nullable(residual), _ptr(gathered), _nullable(y), _ptr(mean), _ptr(rstd), _ptr(moments),
+            _stream_ptr(x.device)))
+    return y, mean, rstd, moments
+
+
+def bn_bwd_reduce(gy, x, y, mean, rstd, w32, b32, relu):
+    """dfm_batch_norm_bwd_reduce_channels_last: this rank's (2, C) sums (row 0 sum(dy') = grad_bias, row 1
+    sum(dy' * xhat) = grad_weight).  relu with y None: the mask is recomputed from x."""
+    lib = _capi.lib()
+    c, rows = x.shape[1], x.numel() // x.shape[1]
+    nbytes = lib.dfm_batch_norm_workspace_bytes(c, rows)
+    ws = _Workspace.get(x.device, nbytes)
+    sums = torch.empty(2, c, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _capi.check(lib.dfm_batch_norm_bwd_reduce_channels_last(
+            c, rows, _DTYPES[x.dtype], int(relu), _nullable(gy), _nullable(x), _nullable(y), _ptr(mean), _ptr(rstd),
+            _ptr(w32), _ptr(b32), _ptr(sums), _ptr(ws), nbytes, _stream_ptr(x.device)))
+    return sums
+
+
+def bn_bwd_apply(gy, x, y, mean, rstd, w32, b32, relu, sums, moments, want_gres=False):
+    """dfm_batch_norm_bwd_apply_channels_last: (grad_x, grad_residual or None) from the rank-summed (2, C) sums and
+    the global count moments[0, 0]"""
+    lib = _capi.lib()
+    c, rows = x.shape[1], x.numel() // x.shape[1]
+    nbytes = lib.dfm_batch_norm_workspace_bytes(c, rows)
+    ws = _Workspace.get(x.device, nbytes)
+    gx = torch.empty_like(x)
+    gres = torch.empty_like(x) if want_gres else None
+    with torch.cuda.device(x.device):
+        _capi.check(lib.dfm_batch_norm_bwd_apply_channels_last(
+            c, rows, _DTYPES[x.dtype], int(relu), _nullable(gy), _nullable(x), _nullable(y), _ptr(mean), _ptr(rstd),
+            _ptr(w32), _ptr(b32), _ptr(sums.contiguous()), _ptr(moments), _nullable(gx), _nullable(gres), _ptr(ws),
+            nbytes, _stream_ptr(x.device)))
+    return gx, gres
+
+
+def update_running_stats(bn, mean, moments):
+    """torch's batch_norm_gather_stats_with_counts: unbiased variance over the global count, momentum or the
+    cumulative average, num_batches_tracked += 1 -- on the device, from the global moments"""
+    with torch.no_grad():
+        m = moments[:, 0]
+        var = moments[:, 2] / (m - 1).clamp_min(1)
+        bn.num_batches_tracked += 1
+        f = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+        bn.running_mean.mul_(1 - f).add_(mean.to(bn.running_mean.dtype), alpha=f)
+        bn.running_var.mul_(1 - f).add_(var.to(bn.running_var.dtype), alpha=f)
+
+
+def _gather_payload(local, group):
+    """(world, C, 3) payloads of every rank in rank order: all_gather_into_tensor on the device (NCCL / RCCL); through
+    host tensors on gloo (C x 3 floats), as torch's SyncBatchNorm does"""
+    dist = torch.distributed
+    world = dist.get_world_size(group)
+    if dist.get_backend(group) == 'gloo':
+        h = local.cpu()
+        parts = [torch.empty_like(h) for _ in range(world)]
+        dist.all_gather(parts, h, group=group)
+        return torch.stack(parts).to(local.device)
+    out = torch.empty((world,) + tuple(local.shape), dtype=local.dtype, device=local.device)
+    dist.all_gather_into_tensor(out, local, group=group)
+    return out
+
+
+def _sum_payload(sums, group):
+    """the (2, C) sums added over the ranks (a new tensor: the local ones stay the parameter gradients)"""
+    dist = torch.distributed
+    if dist.get_backend(group) == 'gloo':
+        h = sums.cpu()
+        dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
+        return h.to(sums.device)
+    out = sums.clone()
+    dist.all_reduce(out, op=dist.ReduceOp.SUM, group=group)
+    return out
+
+
+class _SyncBatchNormFn(torch.autograd.Function):
+    """nn.SyncBatchNorm's training forward / backward at world size > 1 through the fused channels-last kernels:
+    local statistics -> one all-gather of the (C, 3) payloads -> apply; local gradient sums -> one all-reduce of the
+    (2, C) sums -> apply.  The collectives are blocking and issued from the host in program order, one per forward
+    and one per backward of every layer, as torch's SyncBatchNorm issues its own."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, bn, relu, group):
+        w32, b32 = _f32_params(weight, bias)
+        fused_res = residual is not None and residual.shape == x.shape
+        res = _dense(residual.to(x.dtype), _memory_format(x)) if fused_res else None
+        gathered = _gather_payload(bn_stats(x), group)
+        y, mean, rstd, moments = bn_apply_gathered(x, gathered, w32, b32, bn.eps,
+                                                   relu and (fused_res or residual is None), res)
+        if residual is not None and not fused_res:   # a broadcast residual: plain torch ops
+            y = y + residual
+            if relu:
+                y = torch.relu_(y)
+        update_running_stats(bn, mean, moments)
+        xmask = bool(relu) and residual is None and _XMASK
+        ctx.save_for_backward(x, y if (relu and not xmask) else x, mean, rstd, w32, b32, moments)
+        ctx.cfg = (bool(relu), weight.dtype, bias.dtype, residual.dtype if residual is not None else None, xmask,
+                   group)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, y, mean, rstd, w32, b32, moments = ctx.saved_tensors
+        relu, wdt, bdt, rdt, xmask, group = ctx.cfg
+        gy = _dense(gy.to(x.dtype), _memory_format(x))
+        ym = None if (xmask or not relu) else y
+        sums = bn_bwd_reduce(gy, x, ym, mean, rstd, w32, b32, relu)
+        total = _sum_payload(sums, group)
+        want_res = rdt is not None and ctx.needs_input_grad[3]
+        gx, gres = bn_bwd_apply(gy, x, ym, mean, rstd, w32, b32, relu, total, moments, want_res and relu)
+        if want_res and not relu:
+            gres = gy
+        if gres is not None:
+            gres = gres.to(rdt)
+        return gx, sums[1].to(wdt), sums[0].to(bdt), gres, None, None, None
+
+
 def batch_norm_train_channels_last(bn, x, relu=False, residual=None):
-    """Training-mode BatchNorm (nn.BatchNorm2d / 3d / SyncBatchNorm in a single-process job) of a channels-last GPU
-    tensor through the fused GroupNorm kernels, or None when it does not apply.  The batch statistics of a
-    channels-last (N, C, *spatial) tensor are the per-channel GroupNorm statistics of the same memory viewed as ONE
-    sample (1, C, N * s0, ...): normalisation (+ residual) (+ ReLU) is one statistics pass and one apply pass, the
-    backward the channels-last GroupNorm backward; running statistics are updated as torch does (unbiased variance,
-    momentum / cumulative average).  y = relu?(bn(x) + residual)."""
+    """Training-mode BatchNorm (nn.BatchNorm2d / 3d / SyncBatchNorm) of a channels-last GPU tensor through the fused
+    GroupNorm kernels, or None when it does not apply.  The batch statistics of a channels-last (N, C, *spatial)
+    tensor are the per-channel GroupNorm statistics of the same memory viewed as ONE sample (1, C, N * s0, ...):
+    normalisation (+ residual) (+ ReLU) is one statistics pass and one apply pass, the backward the channels-last
+    GroupNorm backward; running statistics are updated as torch does (unbiased variance, momentum / cumulative
+    average).  y = relu?(bn(x) + residual).
+
+    An nn.SyncBatchNorm in a process group of more than one rank runs the same passes split where the ranks exchange
+    their statistics (_SyncBatchNormFn): one all-gather of a (C, 3) payload per forward, one all-reduce of a (C, 2)
+    payload per backward, over ``bn.process_group`` (WORLD if None).  Whether it does is decided by
+    ``sync_batch_norm_eligible`` from what every rank shares, never from the local shard (an empty one included)."""
+    group = _sync_world(bn)
+    if group is not None:
+        if not (x.is_cuda and sync_batch_norm_eligible(bn, x)):
+            return None   # the same answer on every rank: torch's SyncBatchNorm everywhere
+        fmt = _memory_format(x)
+        return _SyncBatchNormFn.apply(_dense(x, fmt), bn.weight, bn.bias, residual, bn, bool(relu), group)
     vec = 16 // x.element_size() if x.dtype in _DTYPES else 0
     c = x.shape[1]
     fmt = torch.channels_last_3d if x.dim() == 5 else torch.channels_last
@@ -206,9 +404,6 @@ def batch_norm_train_channels_last(bn, x, relu=False, residual=None):
             c % vec == 0 and c <= 256 and ((c // vec) & (c // vec - 1)) == 0 and
             not x.is_contiguous() and x.is_contiguous(memory_format=fmt)):
         return None
-    if isinstance(bn, nn.SyncBatchNorm) and torch.distributed.is_available() and torch.distributed.is_initialized() \
-            and torch.distributed.get_world_size() > 1:
-        return None   # statistics across ranks: torch's implementation
 
     def one_sample(t):   # (N, C, s0, ...) channels-last -> (1, C, N * s0, ...) channels-last, the same memory
         n = t.shape[0]

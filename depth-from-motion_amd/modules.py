@@ -934,7 +934,8 @@ def _conv_norm_2d(seq, x, residual=None, relu=False):
     if isinstance(norm, nn.modules.batchnorm._BatchNorm):
         # training: the batch statistics, the normalisation, the residual and the ReLU in the fused GroupNorm kernels on
         # the NHWC map as it lies (round 6; MIOpen's training BatchNorm + separate add / ReLU passes were 0.9 ms of
-        # the DfMStereoPath step) -- None when it does not apply (eval mode, NCHW, SyncBatchNorm across ranks)
+        # the DfMStereoPath step; a SyncBatchNorm across ranks exchanges its statistics in between) -- None when it does
+        # not apply (eval mode, NCHW)
         out = batch_norm_train_channels_last(norm, y, relu=relu, residual=residual)
         if out is not None:
             return out

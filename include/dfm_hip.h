@@ -1002,6 +1002,58 @@ DFM_API int dfm_group_norm_bwd_channels_last_xmask(int32_t n, int32_t c, int64_t
                                                    float *grad_beta, void *workspace, size_t workspace_bytes,
                                                    void *stream);
 
+/* ---------------------------------------------------------------------- */
+/* training BatchNorm with statistics across ranks (nn.SyncBatchNorm at     */
+/* world size > 1): the channels-last passes above, split where the ranks   */
+/* exchange a payload whose size depends on C alone                         */
+/* ---------------------------------------------------------------------- */
+/* One rank's shard is a channels-last (N, C, *spatial) tensor viewed as rows = N * prod(spatial) rows of C contiguous
+ * values [dtype], 16-byte aligned.  rows == 0 (an empty shard) is legal: x, y, grad_y, grad_x may then be NULL.  C is
+ * a power-of-two count of 16-byte vectors, C <= 256 (DFM_ERR_UNSUPPORTED otherwise, as for the channels-last
+ * GroupNorm).  One forward:
+ *   1. dfm_batch_norm_stats_channels_last                 -> this rank's payload stats [C][3]
+ *   2. the caller gathers the payloads of all ranks, in rank order, into gathered [world][C][3]
+ *   3. dfm_batch_norm_apply_gathered_channels_last         -> y, the global mean / rstd / moments
+ * and one backward:
+ *   4. dfm_batch_norm_bwd_reduce_channels_last            -> this rank's sums [2][C]
+ *   5. the caller sums the sums of all ranks (all-reduce)
+ *   6. dfm_batch_norm_bwd_apply_channels_last             -> grad_x (+ grad_residual)
+ * Every rank that runs 3 on the same gathered payload computes bit-identical mean / rstd. */
+DFM_API size_t dfm_batch_norm_workspace_bytes(int32_t c, int64_t rows);
+/* stats: fp32 [C][3] (count, mean, M2) of this rank's rows per channel, merged on the device (written (0, 0, 0) when
+ * rows == 0); its size does not depend on rows. */
+DFM_API int dfm_batch_norm_stats_channels_last(int32_t c, int64_t rows, int32_t dtype, const void *x, float *stats,
+                                               void *workspace, size_t workspace_bytes, void *stream);
+/* gathered : fp32 [world][C][3], the payloads of every rank in rank order, merged with Chan's formula in that order
+ *            (count-0 entries skipped) into moments [C][3] (global count, mean, M2)              [device]
+ * y = relu?((x - mean) * rstd * gamma + beta + residual), residual NULL or a tensor of x's shape and dtype;
+ * biased variance, rstd = 1/sqrt(M2 / count + eps), the arithmetic of dfm_group_norm_apply_channels_last_res.
+ * mean, rstd: fp32 [C] written for the backward and the running statistics.  No workspace. */
+DFM_API int dfm_batch_norm_apply_gathered_channels_last(int32_t c, int64_t rows, int32_t world, float eps,
+                                                        int32_t dtype, int32_t relu, const void *x,
+                                                        const float *gamma, const float *beta, const void *residual,
+                                                        const float *gathered, void *y, float *mean, float *rstd,
+                                                        float *moments, void *stream);
+/* sums: fp32 [2][C] OVERWRITTEN, row 0 = sum(dy'), row 1 = sum(dy' * xhat) over this rank's rows, xhat from the global
+ * mean / rstd, dy' = grad_y behind the ReLU mask (relu != 0): read from y > 0, or -- y NULL, beta (the norm's bias,
+ * fp32 [C]) given -- recomputed from x with the forward's expression as dfm_group_norm_bwd_channels_last_xmask does.
+ * The two rows are this rank's grad_beta and grad_gamma.  A fixed order of additions, no atomics. */
+DFM_API int dfm_batch_norm_bwd_reduce_channels_last(int32_t c, int64_t rows, int32_t dtype, int32_t relu,
+                                                    const void *grad_y, const void *x, const void *y,
+                                                    const float *mean, const float *rstd, const float *gamma,
+                                                    const float *beta, float *sums, void *workspace,
+                                                    size_t workspace_bytes, void *stream);
+/* sums : fp32 [2][C], the sums of step 4 added over all ranks; count: ONE fp32, the global element count per
+ * channel (moments[0] of step 3)                                                                 [device]
+ * grad_x = rstd * gamma * (dy' - G1 / M - xhat * G2 / M) (the mask forms of step 4); grad_residual: NULL or a
+ * tensor of grad_y's shape receiving dy' (the gradient of the residual input). */
+DFM_API int dfm_batch_norm_bwd_apply_channels_last(int32_t c, int64_t rows, int32_t dtype, int32_t relu,
+                                                   const void *grad_y, const void *x, const void *y,
+                                                   const float *mean, const float *rstd, const float *gamma,
+                                                   const float *beta, const float *sums, const float *count,
+                                                   void *grad_x, void *grad_residual, void *workspace,
+                                                   size_t workspace_bytes, void *stream);
+
 /* Backward of F.interpolate(mode='bilinear') on an NHWC map as a gather (round 6; the up-sampling steps of the 2-D
  * necks either side of the path: mmdet3d/models/necks/spp_unet_neck.py:60-70, 83-91, training only):
  *   gx[b, hi, wi, :] = sum_a sum_c row_w[hi][a] * col_w[wi][c] * gy[b, row_idx[hi][a], col_idx[wi][c], :]
