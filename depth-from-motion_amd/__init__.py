@@ -24,10 +24,10 @@ from .depth_head import depth_distribution_loss  # noqa: F401
 from .data_geometry import (fold_ref_frame_matrices, select_ref_frames, stage_geometry,  # noqa: F401
                             video_cur2prevs)
 from .point_sample import (mv_feature_transformation, point_sample, voxel_centers,  # noqa: F401
-                           voxel_sample)
+                           voxel_sample, voxel_sample_mv)
 
 __all__ = ['build_dfm_cost', 'plane_sweep_grid', 'point_sample', 'mv_feature_transformation',
-           'voxel_centers', 'voxel_sample', 'frustum_to_voxel_sample', 'depth_head_forward', 'prepare_depth',
+           'voxel_centers', 'voxel_sample', 'voxel_sample_mv', 'frustum_to_voxel_sample', 'depth_head_forward', 'prepare_depth',
            'prepare_coordinates_3d', 'group_norm', 'HipGroupNorm', 'DfMStereoPath', 'MultiViewDfMMixin',
            'MultiViewVoxelPath', 'inject_detector_attributes', 'patch_reference', 'enable_fast_path', 'set_fallback_policy', 'set_fp32_mode',
            'fallback_policy', 'MfmaPathError', 'select_ref_frames', 'fold_ref_frame_matrices', 'video_cur2prevs',

@@ -98,6 +98,8 @@ EXPORTS = (
     'dfm_depth_loss_fused_bwd',
     'dfm_voxel_sample_fwd',
     'dfm_voxel_sample_bwd',
+    'dfm_voxel_sample_mv_fwd',
+    'dfm_voxel_sample_mv_bwd',
     'dfm_spp_tail_workspace_bytes',
     'dfm_spp_tail_fwd',
     'dfm_group_norm_workspace_bytes',
@@ -206,6 +208,18 @@ class VsDesc(ctypes.Structure):
                 ('voxel_range', ctypes.c_float * 6), ('voxel_size', ctypes.c_float * 3),
                 ('proj_inv', ctypes.c_float * 16), ('mode', ctypes.c_int32),
                 ('dtype', ctypes.c_int32)]
+
+
+VS_PAIR_FLOATS = 24  # DFM_VS_PAIR_FLOATS
+
+
+class VsMvDesc(ctypes.Structure):
+    """struct dfm_vs_mv_desc"""
+    _fields_ = [(n, ctypes.c_int32) for n in ('batch', 'num_views', 'channels', 'nx', 'ny', 'nz', 'num_depths',
+                                              'h_out', 'w_out')] + \
+        [('downsample_factor', ctypes.c_float), ('voxel_range', ctypes.c_float * 6),
+         ('voxel_size', ctypes.c_float * 3), ('dtype', ctypes.c_int32),
+         ('volume_channels_last', ctypes.c_int32), ('out_channels_last', ctypes.c_int32)]
 
 
 class DepthLossDesc(ctypes.Structure):
@@ -430,6 +444,10 @@ def lib():
     h.dfm_voxel_sample_fwd.argtypes = [ctypes.POINTER(VsDesc), vp, fp, vp, vp]
     h.dfm_voxel_sample_bwd.restype = ctypes.c_int
     h.dfm_voxel_sample_bwd.argtypes = [ctypes.POINTER(VsDesc), vp, fp, fp, vp]
+    h.dfm_voxel_sample_mv_fwd.restype = ctypes.c_int
+    h.dfm_voxel_sample_mv_fwd.argtypes = [ctypes.POINTER(VsMvDesc), fp, vp, fp, vp, vp]
+    h.dfm_voxel_sample_mv_bwd.restype = ctypes.c_int
+    h.dfm_voxel_sample_mv_bwd.argtypes = [ctypes.POINTER(VsMvDesc), fp, vp, fp, fp, vp]
     h.dfm_spp_tail_workspace_bytes.restype = ctypes.c_size_t
     h.dfm_spp_tail_workspace_bytes.argtypes = [ctypes.POINTER(SppDesc)]
     h.dfm_spp_tail_fwd.restype = ctypes.c_int

@@ -21,6 +21,7 @@ Three ways to use this package from there, all routed to the HIP kernels:
 3. ``MultiViewDfMMixin`` -- for a subclass ``class MultiViewDfM(MultiViewDfMMixin, RefMultiViewDfM)``.
 """
 import importlib
+import inspect
 
 import numpy as np
 import torch
@@ -28,9 +29,11 @@ from torch import nn
 
 from . import registry
 from .geometry import prepare_coordinates_3d, prepare_depth
+from .conv3d import MfmaConv3dTo1
 from .graphs import GraphedCallable
 from .plane_sweep import build_dfm_cost
-from .point_sample import mv_feature_transformation, point_sample, voxel_centers, voxel_sample
+from .point_sample import (mv_feature_transformation, point_sample, voxel_centers, voxel_sample,
+                           voxel_sample_mv)
 
 
 def inject_detector_attributes(detector, depth_cfg=None, voxel_cfg=None):
@@ -44,10 +47,11 @@ def inject_detector_attributes(detector, depth_cfg=None, voxel_cfg=None):
         detector.downsampled_depth, detector.depth = downsampled, depth
         detector.depth_downsample_factor = ds_factor
         ft = getattr(detector, 'feature_transformation', None)
-        if ft is not None:
+        if ft is not None and not inspect.ismethod(ft):   # (a method on the multi-view detectors)
             ft.depth_cfg = depth_cfg
         if getattr(detector, 'depth_head', None) is not None:
-            detector.backbone_stereo.downsampled_depth = downsampled
+            if getattr(detector, 'backbone_stereo', None) is not None:   # (the multi-view path has none)
+                detector.backbone_stereo.downsampled_depth = downsampled
             detector.depth_head.depth_samples = depth
             detector.depth_head.downsample_factor = ds_factor
     if voxel_cfg is not None:
@@ -212,21 +216,23 @@ class MultiViewDfMMixin:
                 bev_feat = outputs[-1]
         batch_stereo_feats = None
         if getattr(self, 'with_depth_head', False):
-            feats = []
-            for b, meta in enumerate(img_metas):
-                for v in range(num_views):
-                    td = self.transform_depth
-                    sf = meta.get('scale_factor', 1.0) if td else 1.0
-                    feats.append(voxel_sample(
-                        volume_feat[b][None], voxel_range=self.voxel_range, voxel_size=self.voxel_size,
-                        depth_samples=torch.as_tensor(self.depth_samples, dtype=torch.float32),
-                        proj_mat=torch.as_tensor(np.asarray(meta['ori_lidar2img'][v], np.float32)),
-                        downsample_factor=self.depth_head.downsample_factor, img_scale_factor=sf,
-                        img_crop_offset=meta.get('img_crop_offset', 0) if td else 0,
-                        img_flip=meta.get('flip', False) if td else False,
-                        img_pad_shape=meta['input_shape'] if td else meta['ori_shape'][:2],
-                        img_shape=meta['img_shape'][v][:2], aligned=True))
-            batch_stereo_feats = torch.cat(feats)
+            # every (sample, view) frustum in one launch, read from the volume where it lies and written at its
+            # final offset: the bits of the reference's voxel_sample loop + torch.cat (multiview_dfm.py:220-256)
+            td = self.transform_depth
+            conv = getattr(self.depth_head, 'conv_depth', None)
+            to1 = volume_feat.dtype == torch.bfloat16 and isinstance(conv, MfmaConv3dTo1)
+            batch_stereo_feats = voxel_sample_mv(
+                volume_feat, self.voxel_range, self.voxel_size,
+                torch.as_tensor(self.depth_samples, dtype=torch.float32),
+                [meta['ori_lidar2img'][:num_views] for meta in img_metas],
+                self.depth_head.downsample_factor,
+                [meta.get('scale_factor', 1.0) if td else 1.0 for meta in img_metas],
+                [meta.get('img_crop_offset', 0) if td else 0 for meta in img_metas],
+                [meta.get('flip', False) if td else False for meta in img_metas],
+                [meta['input_shape'] if td else meta['ori_shape'][:2] for meta in img_metas],
+                [[meta['img_shape'][v][:2] for v in range(num_views)] for meta in img_metas], num_views,
+                # the layout the depth head's 32 -> 1 kernel reads; the values do not depend on it
+                memory_format=torch.channels_last_3d if to1 else torch.contiguous_format)
         if getattr(self, 'with_neck_3d', False):
             if getattr(self, 'with_backbone_3d', False) and self.backbone_3d.output_bev:
                 volume_feat = self.neck_3d(bev_feat)[1]
@@ -245,9 +251,14 @@ class MultiViewDfMMixin:
 
 class MultiViewVoxelPath(MultiViewDfMMixin, nn.Module):
     """The multi-view path of ``MultiViewDfM`` from its config ``model`` dict (neck_3d,
-    voxel_size, anchor_generator.ranges, temporal_aggregate), without mmdet3d: voxel lifting +
-    the 3-D neck.  ``forward(batch_feats (B, Nv*F, C, Hf, Wf), img_metas, num_views, num_frames)``
-    -> BEV feature (B, C_out, Ny, Nx)."""
+    voxel_size, anchor_generator.ranges, temporal_aggregate, optionally depth_head + depth_cfg), without
+    mmdet3d: voxel lifting + the 3-D neck.  ``forward(batch_feats (B, Nv*F, C, Hf, Wf), img_metas, num_views,
+    num_frames)`` -> BEV feature (B, C_out, Ny, Nx).
+
+    With a ``depth_head`` in the config (depth supervision, multiview_dfm.py:218-256, 296-304):
+    ``forward_with_depth(...)`` -> (bev_feat, depth_volumes, depth_softmax, depth_preds), the last three
+    (B, Nv, ...) as ``DepthHead.forward`` returns them, and ``loss_dense_depth(depth_preds, depth_volumes,
+    depth_img)``."""
 
     def __init__(self, model_cfg):
         super().__init__()
@@ -260,9 +271,32 @@ class MultiViewVoxelPath(MultiViewDfMMixin, nn.Module):
         self.transform_depth = model_cfg.get('transform_depth', True)
         self.neck_3d = registry.build_neck(dict(model_cfg['neck_3d']))
         self.with_neck_3d, self.with_backbone_3d, self.with_depth_head = True, False, False
+        if model_cfg.get('depth_head'):
+            depth_cfg = model_cfg.get('depth_cfg')
+            if depth_cfg is None:
+                raise KeyError("a model with a 'depth_head' needs 'depth_cfg' (dfm.py:79-92)")
+            self.depth_head = registry.build_head(dict(model_cfg['depth_head']))
+            self.with_depth_head = True
+            inject_detector_attributes(self, depth_cfg)          # dfm.py:82-92
+            self.depth_samples = self.depth                      # what feature_transformation samples at
 
     def forward(self, batch_feats, img_metas, num_views, num_frames):
         return self.feature_transformation(batch_feats, img_metas, num_views, num_frames)[0]
+
+    def forward_with_depth(self, batch_feats, img_metas, num_views, num_frames):
+        """-> (bev_feat, depth_volumes, depth_softmax, depth_preds): multiview_dfm.py:277-278, 297-298"""
+        if not self.with_depth_head:
+            raise RuntimeError("this MultiViewVoxelPath was built without a 'depth_head'")
+        bev_feat, stereo_feat = self.feature_transformation(batch_feats, img_metas, num_views, num_frames)
+        depth_volumes, depth_softmax, depth_preds = self.depth_head(stereo_feat)
+        return bev_feat, depth_volumes, depth_softmax, depth_preds
+
+    def loss_dense_depth(self, depth_preds, depth_volumes, depth_img):
+        """multiview_dfm.py:299-303: depth_preds (B, Nv, H, W), depth_volumes (B, Nv, D, H, W), depth_img
+        (B, Nv, H, W)"""
+        return self.depth_head.loss(depth_preds.flatten(start_dim=0, end_dim=1),
+                                    depth_volumes.flatten(start_dim=0, end_dim=1),
+                                    depth_img.flatten(start_dim=0, end_dim=1))
 
 
 # the functions the reference's modules look up by name, and the files that define them

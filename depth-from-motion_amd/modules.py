@@ -668,7 +668,9 @@ class DepthHead(DerivedStateMixin, nn.Module):
         self.min_depth = depth_cfg['min_depth']
         self.max_depth = depth_cfg['max_depth']
         if with_convs:
-            self.conv_depth = nn.Conv3d(in_channels, 1, 3, 1, 1, bias=False)
+            # 32 -> 1: the hand-written kernel for a bf16 / NDHWC volume (an nn.Conv3d otherwise, same key)
+            self.conv_depth = (MfmaConv3dTo1 if in_channels == 32 else nn.Conv3d)(in_channels, 1, 3, 1, 1,
+                                                                                  bias=False)
         self.depth_samples = None  # injected by the detector (dfm.py:90)
 
     def forward(self, stereo_features, lazy=False):

@@ -368,3 +368,157 @@ class _VoxelSampleFn(torch.autograd.Function):
             _capi.check(lib.dfm_voxel_sample_bwd(ctypes.byref(ctx.desc), _ptr(go), _ptr(depths), _ptr(gv),
                                                  _stream_ptr(device)))
         return gv.to(dtype), None, None
+
+
+def _pair_rows(inv, scales, crops, flips, img_shapes, num_views):
+    """the (B * Nv, VS_PAIR_FLOATS) rows of dfm_voxel_sample_mv_*: ``inv`` (B * Nv, 16) or None (filled on the
+    device), then scale, crop, ori_w and flip of each pair"""
+    B = len(scales)
+    rows = np.zeros((B * num_views, _capi.VS_PAIR_FLOATS), dtype=np.float32)
+    if inv is not None:
+        rows[:, :16] = inv
+    for b in range(B):
+        for v in range(num_views):
+            rows[b * num_views + v, 16:22] = (*scales[b], *crops[b], float(img_shapes[b][v][1]),
+                                              1.0 if flips[b] else 0.0)
+    return rows
+
+
+def voxel_sample_mv(volume,
+                    voxel_range,
+                    voxel_size,
+                    depth_samples,
+                    proj_mats,
+                    downsample_factor,
+                    img_scale_factors,
+                    img_crop_offsets,
+                    img_flips,
+                    img_pad_shape,
+                    img_shapes,
+                    num_views,
+                    memory_format=torch.contiguous_format,
+                    proj_invs=None):
+    """``voxel_sample`` (aligned=True) for every (sample, view) pair of a batch in one launch: the loop of
+    ``MultiViewDfM.feature_transformation`` with its two ``torch.cat`` (multiview_dfm.py:220-256).
+
+    ``volume`` (B, C, Nx, Ny, Nz) fp32 / bf16, contiguous or channels_last_3d (read where it lies) ->
+    (B * Nv, C, D, h_out, w_out), pair b * Nv + v from sample b and view v; bit for bit what B * Nv calls of
+    ``voxel_sample`` on ``volume[b][None]`` give, concatenated.  Differentiable with respect to ``volume`` (the
+    views of a sample are summed with fp32 atomics: the last bits of the gradient are not fixed from run to run).
+
+    ``proj_mats``: the ORIGINAL lidar2img matrices, ``proj_mats[b][v]`` a 4x4 (nested lists, arrays, one
+    (B, Nv, 4, 4) tensor, or per-sample tensors).  Host matrices are inverted one by one with ``torch.inverse``
+    in fp32 on the host -- the reference's op (utils.py:241), the bits the single call uses -- and uploaded
+    together, once.  Matrices that live on the device (``data_geometry.stage_geometry``) stay there: they are
+    inverted by ``dfm_camera_prepare``, which agrees with the host inverse to fp32 rounding, not bit for bit.
+    ``proj_invs`` (B, Nv, 4, 4): precomputed fp32 inverses (bit-exact replays of a fixture).
+    ``img_scale_factors`` / ``img_crop_offsets`` / ``img_flips``: one entry per sample, as ``voxel_sample`` takes
+    them; ``img_pad_shape``: (h, w) shared by the batch (a list with one equal entry per sample is accepted);
+    ``img_shapes[b][v]``: (h, w, ...) of the view before padding.
+    ``memory_format=torch.channels_last_3d``: the result stored (B * Nv, D, h_out, w_out, C), what
+    ``MfmaConv3dTo1`` reads."""
+    _require_gpu(volume, 'volume')
+    assert volume.dim() == 5
+    if volume.dtype not in _DTYPES:
+        raise TypeError(f'volume must be float32 or bfloat16, got {volume.dtype}')
+    lib = _capi.lib()
+    device = volume.device
+    B, C = volume.shape[:2]
+    num_views = int(num_views)
+    P = B * num_views
+    if not (len(img_scale_factors) == len(img_crop_offsets) == len(img_flips) == len(img_shapes) == B):
+        raise ValueError('one scale factor, crop offset, flip and img_shapes entry per sample of the volume')
+    pads = list(img_pad_shape) if isinstance(img_pad_shape[0], (tuple, list, torch.Size, np.ndarray)) else [img_pad_shape]
+    pads = {(int(p_[0]), int(p_[1])) for p_ in pads}
+    if len(pads) != 1:
+        raise ValueError(f'the samples of a batch share one padded shape, got {sorted(pads)}')
+    pad = pads.pop()
+    if volume.is_contiguous():
+        vox, vcl = volume, 0
+    elif volume.is_contiguous(memory_format=torch.channels_last_3d):
+        vox, vcl = volume, 1
+    else:
+        vox, vcl = volume.contiguous(), 0
+    downsample_factor = int(downsample_factor)
+    depths = _upload(torch.as_tensor(depth_samples, dtype=torch.float32).detach()[::downsample_factor], device)
+    depths = depths.contiguous()
+    scales = [_scale_xy(s) for s in img_scale_factors]
+    crops = [_crop_xy(c) for c in img_crop_offsets]
+    on_device = proj_invs is None and (
+        (torch.is_tensor(proj_mats) and proj_mats.is_cuda) or
+        (not torch.is_tensor(proj_mats) and all(torch.is_tensor(m) and m.is_cuda for m in proj_mats)))
+    if on_device:
+        mats = proj_mats if torch.is_tensor(proj_mats) else torch.stack([m[:num_views] for m in proj_mats])
+        mats = mats[:, :num_views].to(device=device, dtype=torch.float32).reshape(P, 4, 4).contiguous()
+        pad4, inv = torch.empty((P, 16), dtype=torch.float32, device=device), \
+            torch.empty((P, 16), dtype=torch.float32, device=device)
+        with torch.cuda.device(device):
+            _capi.check(lib.dfm_camera_prepare(_ptr(mats), 4, 4, P, _ptr(pad4), _ptr(inv), _stream_ptr(device)))
+        pairs = _upload(torch.from_numpy(_pair_rows(None, scales, crops, img_flips, img_shapes, num_views)), device)
+        pairs[:, :16] = inv
+    else:
+        def host(m):
+            return torch.as_tensor(np.asarray(m.detach().cpu() if torch.is_tensor(m) else m, dtype=np.float32))
+        if proj_invs is not None:
+            inv = torch.stack([host(proj_invs[b][v]) for b in range(B) for v in range(num_views)])
+        else:
+            inv = torch.stack([torch.inverse(host(proj_mats[b][v]))   # utils.py:241, one matrix at a time
+                               for b in range(B) for v in range(num_views)])
+        pairs = _upload(torch.from_numpy(_pair_rows(inv.reshape(P, 16).numpy(), scales, crops, img_flips,
+                                                    img_shapes, num_views)), device)
+    desc = _capi.VsMvDesc()
+    desc.batch, desc.num_views, desc.channels = B, num_views, C
+    desc.nx, desc.ny, desc.nz = vox.shape[2:]
+    desc.num_depths = depths.numel()
+    desc.h_out, desc.w_out = round(pad[0] / downsample_factor), round(pad[1] / downsample_factor)
+    desc.downsample_factor = float(downsample_factor)
+    for i, v in enumerate(np.asarray(voxel_range, dtype=np.float32).reshape(6)):
+        desc.voxel_range[i] = float(v)
+    for i, v in enumerate(np.asarray(voxel_size, dtype=np.float32).reshape(3)):
+        desc.voxel_size[i] = float(v)
+    desc.dtype = _DTYPES[vox.dtype]
+    desc.volume_channels_last = vcl
+    desc.out_channels_last = 1 if memory_format == torch.channels_last_3d else 0
+    return _VoxelSampleMvFn.apply(vox, depths, pairs, desc)
+
+
+class _VoxelSampleMvFn(torch.autograd.Function):
+    """dfm_voxel_sample_mv_fwd / _bwd (gradient w.r.t. the volume, in the volume's layout)"""
+
+    @staticmethod
+    def forward(ctx, vox, depths, pairs, desc):
+        lib = _capi.lib()
+        device = vox.device
+        P, C = desc.batch * desc.num_views, desc.channels
+        lattice = (desc.num_depths, desc.h_out, desc.w_out)
+        if desc.out_channels_last:
+            out = torch.empty((P,) + lattice + (C,), dtype=vox.dtype, device=device).permute(0, 4, 1, 2, 3)
+        else:
+            out = torch.empty((P, C) + lattice, dtype=vox.dtype, device=device)
+        with torch.cuda.device(device):
+            _capi.check(lib.dfm_voxel_sample_mv_fwd(ctypes.byref(desc), _ptr(pairs), _ptr(vox), _ptr(depths),
+                                                    _ptr(out), _stream_ptr(device)))
+        ctx.desc, ctx.meta = desc, (vox.shape, vox.dtype)
+        ctx.save_for_backward(depths, pairs)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        depths, pairs = ctx.saved_tensors
+        (B, C, nx, ny, nz), dtype = ctx.meta
+        desc = ctx.desc
+        lib = _capi.lib()
+        device = gout.device
+        go = gout.to(dtype)
+        if desc.out_channels_last:
+            go = go.permute(0, 2, 3, 4, 1).contiguous().permute(0, 4, 1, 2, 3)
+        else:
+            go = go.contiguous()
+        if desc.volume_channels_last:
+            gv = torch.zeros((B, nx, ny, nz, C), dtype=torch.float32, device=device).permute(0, 4, 1, 2, 3)
+        else:
+            gv = torch.zeros((B, C, nx, ny, nz), dtype=torch.float32, device=device)
+        with torch.cuda.device(device):
+            _capi.check(lib.dfm_voxel_sample_mv_bwd(ctypes.byref(desc), _ptr(pairs), _ptr(go), _ptr(depths),
+                                                    _ptr(gv), _stream_ptr(device)))
+        return gv.to(dtype), None, None, None

@@ -569,6 +569,40 @@ DFM_API int dfm_voxel_sample_fwd(const dfm_vs_desc *desc, const void *voxel_feat
 DFM_API int dfm_voxel_sample_bwd(const dfm_vs_desc *desc, const void *grad_out, const float *depths,
                                  float *grad_voxel_features, void *stream);
 
+/* The same op for every (sample, view) pair of a batch in ONE launch: the voxel_sample loop of
+ * MultiViewDfM.feature_transformation (multiview_dfm.py:220-256) including its two torch.cat.  Trilinear
+ * (aligned=True, what the detector passes) only.  What the pairs share is the descriptor; what differs is a row of
+ * DFM_VS_PAIR_FLOATS fp32 values per pair in DEVICE memory, pair index = sample * num_views + view:
+ *   [0..15] fp32 inverse of the view's 4x4 lidar2img, row-major (utils.py:241)
+ *   [16] scale_x  [17] scale_y  [18] crop_x  [19] crop_y  [20] ori_w (img_shape[1])  [21] flip (0 or 1)  [22..23] 0
+ * Every lattice point is computed with dfm_voxel_sample_fwd's arithmetic, op for op: the result equals num_views *
+ * batch single calls concatenated, bit for bit, in every layout. */
+#define DFM_VS_PAIR_FLOATS 24
+typedef struct dfm_vs_mv_desc {
+    int32_t batch, num_views;
+    int32_t channels;        /* C of voxel_features (B, C, nx, ny, nz)           */
+    int32_t nx, ny, nz;
+    int32_t num_depths;      /* len(depth_samples[::downsample_factor])         */
+    int32_t h_out, w_out;    /* round(img_pad_shape / downsample_factor)        */
+    float downsample_factor;
+    float voxel_range[6];
+    float voxel_size[3];
+    int32_t dtype;
+    int32_t volume_channels_last; /* voxel_features stored (B, nx, ny, nz, C): torch channels_last_3d, read in place */
+    int32_t out_channels_last;    /* out (and grad_out) stored (B * Nv, D, h_out, w_out, C)                          */
+} dfm_vs_mv_desc;
+
+/* pairs (B * Nv, DFM_VS_PAIR_FLOATS), voxel_features (B, C, nx, ny, nz), depths (num_depths) fp32 ->
+ * out (B * Nv, C, D, h_out, w_out), every element written once.  A channels-last volume whose C is a multiple of
+ * the 16-byte channel block (4 fp32 / 8 bf16) is gathered with 16-byte loads. */
+DFM_API int dfm_voxel_sample_mv_fwd(const dfm_vs_mv_desc *desc, const float *pairs, const void *voxel_features,
+                                    const float *depths, void *out, void *stream);
+/* grad_out (B * Nv, C, D, h_out, w_out) dtype, desc->out_channels_last layout -> grad_voxel_features
+ * (B, C, nx, ny, nz) FP32 in the layout desc->volume_channels_last names, zero-filled by the caller: the views of a
+ * sample are summed with fp32 atomics (the order of the sum, and with it the last bits, is not fixed). */
+DFM_API int dfm_voxel_sample_mv_bwd(const dfm_vs_mv_desc *desc, const float *pairs, const void *grad_out,
+                                    const float *depths, float *grad_voxel_features, void *stream);
+
 /* ---------------------------------------------------------------------- */
 /* DepthHead.forward (with_convs=False), dense_heads/depth_head.py:205-210  */
 /* ---------------------------------------------------------------------- */

@@ -1,0 +1,155 @@
+"""CPU: the batched voxel_sample (``voxel_sample_mv``, dfm_voxel_sample_mv_fwd / _bwd) is declared, bound and
+exported, and ``MultiViewVoxelPath`` builds the depth head of a ``MultiViewDfM`` config (multiview_dfm.py:218-256,
+296-304).  No compute calls -- there is no GPU here."""
+import ctypes
+import importlib
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from tests import util
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WAYMO = 'multiview-dfm_r101_dcn_2x16_waymoD5-3d-3class_camsync.py'
+DEPTH_HEAD = dict(type='DepthHead', depth_cfg=dict(mode='UD', num_bins=8, min_depth=1.0, max_depth=13.0),
+                  in_channels=32, with_convs=True, depth_loss=dict(type='ce', loss_weight=1.0),
+                  downsample_factor=4, num_views=5)
+DEPTH_CFG = dict(mode='UD', num_bins=8, depth_min=1.0, depth_max=13.0, downsample_factor=4)
+
+
+@pytest.fixture(scope='module')
+def pkg():
+    importlib.import_module('depth-from-motion_amd.build').build_hip()
+    return importlib.import_module('depth-from-motion_amd')
+
+
+def small_model(with_depth_head, in_channels=32):
+    with open(os.path.join(util.GOLDEN, 'configs_dfm.json')) as f:
+        model = dict(json.load(f)[WAYMO]['model'])
+    model['anchor_generator'] = dict(model['anchor_generator'], ranges=[[-10.0, -12.0, -2.0, 10.0, 12.0, 2.0]])
+    model['voxel_size'] = [1.0, 1.0, 2.0 / 3.0]
+    model['neck_3d'] = dict(model['neck_3d'], in_channels=32, out_channels=32)
+    model.pop('depth_head', None)
+    if with_depth_head:
+        model['depth_head'] = dict(DEPTH_HEAD, in_channels=in_channels)
+        model['depth_cfg'] = dict(DEPTH_CFG)
+    return model
+
+
+def test_function_and_entry_points_are_public(pkg):
+    assert 'voxel_sample_mv' in pkg.__all__ and callable(pkg.voxel_sample_mv)
+    header = open(os.path.join(ROOT, 'include', 'dfm_hip.h')).read()
+    lib = ctypes.CDLL(pkg._capi.LIB_PATH)
+    for name in ('dfm_voxel_sample_mv_fwd', 'dfm_voxel_sample_mv_bwd'):
+        assert name in pkg._capi.EXPORTS
+        assert re.search(r'DFM_API\s+int\s+%s\s*\(' % name, header)
+        assert hasattr(lib, name)
+    pair = int(re.search(r'#define\s+DFM_VS_PAIR_FLOATS\s+(\d+)', header).group(1))
+    assert pair == pkg._capi.VS_PAIR_FLOATS
+
+
+def test_descriptor_matches_the_header(pkg):
+    """struct dfm_vs_mv_desc, field by field in order, against the ctypes mirror"""
+    header = open(os.path.join(ROOT, 'include', 'dfm_hip.h')).read()
+    body = re.search(r'typedef struct dfm_vs_mv_desc \{(.*?)\} dfm_vs_mv_desc;', header, re.S).group(1)
+    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
+    fields = []
+    for ctype, names in re.findall(r'(int32_t|float)\s+([^;]+);', body):
+        for n in names.split(','):
+            m = re.match(r'\s*(\w+)(?:\[(\d+)\])?\s*$', n)
+            fields.append((m.group(1), ctype, int(m.group(2) or 1)))
+    names = {ctypes.c_float: 'float', ctypes.c_int32: 'int32_t'}
+    mirror = [(n, names[t._type_ if hasattr(t, '_length_') else t], getattr(t, '_length_', 1))
+              for n, t in pkg._capi.VsMvDesc._fields_]
+    assert fields == mirror
+
+
+def test_invalid_calls_are_rejected_without_touching_the_gpu(pkg):
+    lib = pkg._capi.lib()
+    desc = pkg._capi.VsMvDesc()   # all zero
+    assert lib.dfm_voxel_sample_mv_fwd(ctypes.byref(desc), None, None, None, None, None) == -1
+    assert b'size' in lib.dfm_last_error()
+    desc.batch, desc.num_views, desc.channels = 2, 5, 32
+    desc.nx = desc.ny = desc.nz = desc.num_depths = desc.h_out = desc.w_out = 4
+    desc.dtype = 7
+    assert lib.dfm_voxel_sample_mv_fwd(ctypes.byref(desc), None, None, None, None, None) == -2
+    desc.dtype = 1
+    assert lib.dfm_voxel_sample_mv_fwd(ctypes.byref(desc), None, None, None, None, None) == -1   # NULL pointers
+    assert lib.dfm_voxel_sample_mv_bwd(ctypes.byref(desc), None, None, None, None, None) == -1
+    desc.batch = 20000   # more pairs than a grid's second dimension holds
+    assert lib.dfm_voxel_sample_mv_bwd(ctypes.byref(desc), None, None, None, None, None) == -2
+
+
+def test_cpu_tensors_are_refused(pkg):
+    vol = torch.zeros(2, 32, 4, 4, 4)
+    with pytest.raises(RuntimeError, match='no CPU path'):
+        pkg.voxel_sample_mv(vol, [-2, -2, -2, 2, 2, 2], [1, 1, 1], torch.arange(1.0, 9.0),
+                            np.tile(np.eye(4, dtype=np.float32), (2, 5, 1, 1)), 4, [1.0, 1.0], [0, 0],
+                            [False, False], (16, 16), [[(16, 16)] * 5] * 2, 5)
+
+
+def test_path_builds_the_depth_head_of_the_config(pkg):
+    path = pkg.MultiViewVoxelPath(small_model(True))
+    assert path.with_depth_head and type(path.depth_head).__name__ == 'DepthHead'
+    keys = list(path.state_dict().keys())
+    assert 'depth_head.conv_depth.weight' in keys
+    assert [k for k in keys if k.startswith('depth_head.')] == ['depth_head.conv_depth.weight']
+    # 32 -> 1: the hand-written kernel's module, which IS an nn.Conv3d with the reference's parameter
+    conv = path.depth_head.conv_depth
+    assert isinstance(conv, torch.nn.Conv3d) and type(conv).__name__ == 'MfmaConv3dTo1'
+    assert tuple(conv.weight.shape) == (1, 32, 3, 3, 3) and conv.bias is None
+    # the detector's attribute injection (dfm.py:82-92) and the samples feature_transformation reads
+    want = torch.tensor([(i + 0.5) * 1.5 + 1.0 for i in range(8)])
+    assert torch.equal(path.depth_head.depth_samples, want) and torch.equal(path.depth_samples, want)
+    assert path.depth_head.downsample_factor == 4
+    # a reference-shaped state dict (nn.Conv3d(32, 1, 3, 1, 1, bias=False) under depth_head.conv_depth) loads
+    ref_head = torch.nn.Conv3d(32, 1, 3, 1, 1, bias=False)
+    sd = dict(path.state_dict())
+    sd['depth_head.conv_depth.weight'] = ref_head.weight.detach().clone()
+    path.load_state_dict(sd, strict=True)
+    assert torch.equal(path.depth_head.conv_depth.weight, ref_head.weight)
+    assert callable(path.forward_with_depth) and callable(path.loss_dense_depth)
+
+
+def test_other_channel_counts_keep_the_plain_convolution(pkg):
+    path = pkg.MultiViewVoxelPath(small_model(True, in_channels=16))
+    assert type(path.depth_head.conv_depth) is torch.nn.Conv3d
+
+
+def test_path_without_a_depth_head_is_unchanged(pkg):
+    plain = pkg.MultiViewVoxelPath(small_model(False))
+    assert not plain.with_depth_head and not hasattr(plain, 'depth_head')
+    keys = list(plain.state_dict().keys())
+    assert keys and all(k.startswith('neck_3d.') for k in keys)
+    with_head = pkg.MultiViewVoxelPath(small_model(True))
+    assert [k for k in with_head.state_dict().keys() if not k.startswith('depth_head.')] == keys
+    with pytest.raises(RuntimeError, match='depth_head'):
+        plain.forward_with_depth(None, None, 5, 1)
+
+
+def test_a_depth_head_needs_the_detectors_depth_cfg(pkg):
+    model = small_model(True)
+    del model['depth_cfg']
+    with pytest.raises(KeyError, match='depth_cfg'):
+        pkg.MultiViewVoxelPath(model)
+
+
+def test_inject_detector_attributes_without_a_stereo_backbone(pkg):
+    """the multi-view path has a depth head and no backbone_stereo (dfm.py:87-92 assumes both)"""
+    from types import SimpleNamespace
+    det = SimpleNamespace(depth_head=SimpleNamespace())
+    pkg.inject_detector_attributes(det, dict(DEPTH_CFG))
+    assert det.depth_head.depth_samples.numel() == 8 and det.depth_head.downsample_factor == 4
+
+
+def test_fixture_is_within_the_size_of_a_committed_file():
+    p = os.path.join(util.GOLDEN, 'multiview_depth.npz')
+    assert os.path.getsize(p) < (1 << 20)
+    z = np.load(p)
+    assert z['stereo_td1'].shape == (10, 32, 2, 6, 8) and z['stereo_td0'].shape == (10, 4, 2, 12, 16)
+    assert z['head_vol'].shape == (2, 5, 8, 24, 32) and z['proj_inv'].shape == (2, 5, 4, 4)
+    assert 0.5 < (z['stereo_td1'] != 0).mean() < 0.95   # lattice points inside and outside the volume
