@@ -313,14 +313,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_g_kernel(
                 // CW MFMAs = 64 clocks: two steps ahead (round 5) is 128 clocks against an L2 round trip of ~700 -- the
                 // small hourglass layers (250 workgroups, PFW = 1) stalled on every step (profiles/r06_c8_*: conv1 102 ->
                 // 72 us with the weight loads ablated).  Round 6: five steps ahead for PFW = 1 (48 registers at CW = 2).
-#ifdef DFM_WRING3   // (A/B builds: the round-5 ring)
-                constexpr int WR = 3, WD = WR - 1;
-#else
 #ifndef DFM_WRING6_MAXPFW
 #define DFM_WRING6_MAXPFW 3
 #endif
                 constexpr int WR = PFW <= DFM_WRING6_MAXPFW ? 6 : 3, WD = WR - 1;
-#endif
                 bf16x8_t w[WR][CW];  // weight fragments of k-steps s .. s + WD (mod WR)
                 u32x4_t q[2][PFW];   // activation fragments of k-steps s, s + 1 (mod 2)
                 uint32_t addr[PFW];  // the k-step-0 addresses of the tap being read (k-step 1 = ^ 32)

@@ -28,23 +28,10 @@
 // PLAIN stores let the L2 merge them: the non-temporal form pushed partial lines out and measured 1.9x
 // slower here (f2v_cl 1.93 -> 3.59 ms, profiles/archive/r04_c7_lift_nt_vs_plain.txt) -- while the batched
 // multi-view kernel (point_sample.hip), whose lanes write whole contiguous KiBs, gains 6 % from nt.
-#define DFM_LIFT_PLAIN 1
 template <typename T>
 __device__ __forceinline__ void lift_store16(T *p, const float (&f)[dfm::vec16<T>::N])
 {
-#ifdef DFM_LIFT_PLAIN
     dfm::store16<T>(p, f);
-#else
-    typedef uint32_t lift_u32x4 __attribute__((ext_vector_type(4)));
-    lift_u32x4 v;
-    if constexpr (sizeof(T) == 4) {
-        v = lift_u32x4{__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3])};
-    } else {
-        v = lift_u32x4{dfm::pack_bf16x2(f[0], f[1]), dfm::pack_bf16x2(f[2], f[3]), dfm::pack_bf16x2(f[4], f[5]),
-                       dfm::pack_bf16x2(f[6], f[7])};
-    }
-    __builtin_nontemporal_store(v, (lift_u32x4 *)p);
-#endif
 }
 
 
@@ -1236,11 +1223,7 @@ __global__ __launch_bounds__(256, DFM_F2G_WGS) void f2v_bwd_gather_kernel(F2vGeo
             };
             // boxes of up to 8 x 8 voxels -- what the path's grids produce -- take the counted loops; a wave that
             // holds a larger box walks it in full (uniform choice)
-#ifdef DFM_GATHER_R5_LOOPS   // (A/B builds only: the round-5 form -- boxes cut at 8 x 8)
-            const bool small_box = true;
-#else
             const bool small_box = !__any(some && (iy1 - iy0 > 7 || iz1 - iz0 > 7));
-#endif
             if (small_box) {
                 for (int jz = 0; jz < 8; ++jz) {
                     const int iz = iz0 + jz;

@@ -1,5 +1,7 @@
-// plane_sweep.hip -- gfx950 kernels + C ABI for build_dfm_cost
-// (reference: mmdet3d/models/backbones/dfm_backbone.py:217-314).
+// plane_sweep.hip -- gfx950 kernels + C ABI for the forward of build_dfm_cost
+// (reference: mmdet3d/models/backbones/dfm_backbone.py:217-314).  The backward is plane_sweep_bwd.hip
+// (one of its kernels is compiled here: sweep_bwd_kernel);
+// the error string, the LDS attribute cache and the profiler are runtime.hip.
 //
 // Data layout in HBM
 //   cur/prev  : caller tensors (B, C, H, W), T in {f32, bf16}
@@ -14,18 +16,19 @@
 //                         of the volume bytes).
 //   sweep_gather_kernel : one lane = one lattice point; loops channel blocks,
 //                         four 16-B taps per map straight from L2/L1.
-//   sweep_bwd_tile_kernel: backward, gradients accumulated in fixed-point LDS rows.
-//   sweep_bwd_kernel    : backward fallback (maps wider than the LDS rows), lane-per-point
-//                         scatter-add with global atomics.
+//   sweep_tile_kernel   : one workgroup = a tile of lattice points x one map; feature rows staged in
+//                         LDS by DMA (or direct taps), 16-byte volume stores.
+//   sweep_spill_kernel, sweep_respill_kernel, sweep_patch_kernel : the tiles and plane-boundary
+//                         points the tile kernel leaves over.
+//   sweep_bwd_kernel    : the backward's lane-per-point scatter (the adjoint of sweep_gather_kernel).
 //   sweep_grid_kernel   : parity aid, dumps the normalised grids.
-#include "dfm_common.h"
+//   camera_prepare_kernel: cam2img -> the padded 4x4 and its inverse.
+#include "plane_sweep_common.h"
 
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -34,9 +37,7 @@ using namespace dfm;
 
 namespace {
 
-thread_local char g_err[512] = "";
 thread_local int g_last_kernel = 0;
-std::atomic<int> g_last_bwd_kernel{0};  // process-wide: autograd runs the backward on its own thread
 #ifdef DFM_DEBUG_HOOKS
 unsigned long long *g_trace = nullptr;  // debug builds only: see dfm_debug_set_trace
 #endif
@@ -65,56 +66,6 @@ struct TuneKey {
 };
 std::mutex g_tune_mu;
 std::map<TuneKey, dfm_sweep_opts> g_tuned;
-
-// optional per-launch timing of the dominant (volume-writing) kernel with HIP
-// events on the caller's stream (bench.py's roofline leg)
-struct Profiler {
-    std::mutex mu;
-    bool on = false;
-    std::vector<hipEvent_t> ev;  // pairs
-    int used = 0;
-} g_prof;
-
-int fail(int code, const char *fmt, const char *detail = "")
-{
-    snprintf(g_err, sizeof(g_err), fmt, detail);
-    return code;
-}
-}  // namespace
-
-int dfm::set_error(int code, const char *msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel, size) instead of on
-// every launch.  The attribute is per DEVICE: every translation unit of the library goes through
-// this one (device, kernel) map, so a second GPU driven from the same process gets its own call.
-int dfm::ensure_dynamic_lds(const void *kern, int lds_bytes)
-{
-    static std::mutex mu;
-    static std::map<std::pair<int, const void *>, int> seen;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
-    std::lock_guard<std::mutex> lk(mu);
-    int &have = seen[std::make_pair(dev, kern)];
-    if (lds_bytes > have) {
-        e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
-        have = lds_bytes;
-    }
-    return DFM_OK;
-}
-
-namespace {
-
-#define HIP_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess) return fail(DFM_ERR_HIP, #expr ": %s", hipGetErrorString(e_)); \
-    } while (0)
 
 // ---------------------------------------------------------------------------
 // NCHW -> [B][nblk][H][W][CB]
@@ -217,7 +168,6 @@ __device__ __forceinline__ void blend(const Tap &t, const uint4 &qnw, const uint
     }
 }
 
-
 template <int CB>
 __device__ __forceinline__ void blend_nomask(const Tap &t, const uint4 &qnw, const uint4 &qne,
                                              const uint4 &qsw, const uint4 &qse, float (&r)[CB])
@@ -293,6 +243,57 @@ __global__ __launch_bounds__(256) void sweep_gather_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// The adjoint of sweep_gather_kernel, the backward's fallback for maps wider than its LDS rows
+// (plane_sweep_bwd.hip launches it through dfm::sweep_bwd_scatter_launch): grad feats +=
+// scatter(grad_out * weights); grid (ceil(N/256), B).  It is compiled HERE, with the other two callers of
+// sweep_point: alone in a translation unit whose every call passes norm == nullptr, hipcc folds that
+// into sweep_point before inlining it and schedules the projection differently.
+// ---------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void sweep_bwd_kernel(
+    SweepGeom g, const T *__restrict__ gout, const float *__restrict__ depths,
+    const float *__restrict__ P, const float *__restrict__ Pinv, const float *__restrict__ Tm,
+    float *__restrict__ gcur, float *__restrict__ gprev)
+{
+    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    if (n >= g.N) return;
+    const int hw = g.h_out * g.w_out;
+    const int d = (int)(n / hw);
+    const int rem = (int)(n - (long long)d * hw);
+    const int hi = rem / g.w_out;
+    const int wi = rem - hi * g.w_out;
+    float cx, cy, px, py;
+    sweep_point(g, P + b * 16, Pinv + b * 16, Tm + b * 16, depths[d], hi, wi, cx, cy, px, py,
+                nullptr);
+    const Tap tc = make_tap(cx, cy, g.h_in, g.w_in);
+    const Tap tp = make_tap(px, py, g.h_in, g.w_in);
+    const int HW = g.h_in * g.w_in;
+    const int c00 = tc.iy * g.w_in + tc.ix, c01 = c00 + tc.dx;
+    const int c10 = c00 + tc.dy * g.w_in, c11 = c10 + tc.dx;
+    const int p00 = tp.iy * g.w_in + tp.ix, p01 = p00 + tp.dx;
+    const int p10 = p00 + tp.dy * g.w_in, p11 = p10 + tp.dx;
+    const T *gc = gout + ((size_t)b * 2 * g.C) * g.N + n;
+    const T *gp = gc + (size_t)g.C * g.N;
+    float *dc = gcur + (size_t)b * g.C * HW;
+    float *dp = gprev + (size_t)b * g.C * HW;
+    for (int c = 0; c < g.C; ++c) {
+        const float go_c = elem<T>::load(gc[(size_t)c * g.N]);
+        const float go_p = elem<T>::load(gp[(size_t)c * g.N]);
+        if (tc.ok & 1u) atomicAdd(dc + c00, go_c * tc.nw);
+        if (tc.ok & 2u) atomicAdd(dc + c01, go_c * tc.ne);
+        if (tc.ok & 4u) atomicAdd(dc + c10, go_c * tc.sw);
+        if (tc.ok & 8u) atomicAdd(dc + c11, go_c * tc.se);
+        if (tp.ok & 1u) atomicAdd(dp + p00, go_p * tp.nw);
+        if (tp.ok & 2u) atomicAdd(dp + p01, go_p * tp.ne);
+        if (tp.ok & 4u) atomicAdd(dp + p10, go_p * tp.sw);
+        if (tp.ok & 8u) atomicAdd(dp + p11, go_p * tp.se);
+        dc += HW;
+        dp += HW;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // LDS-staged forward.
 //
 // One workgroup = NT lanes = (a tile of NT*V consecutive lattice points of one
@@ -321,25 +322,11 @@ __global__ __launch_bounds__(256) void sweep_gather_kernel(
 // ---------------------------------------------------------------------------
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
-// How the volume's 16-byte vectors leave the CU.  Default: non-temporal (global_store_dwordx4 ... nt).
-// -DDFM_STORE_FLAVOUR=1 plain, 2 sc1, 3 sc0 sc1 (write-through), 4 sc1 nt: experiment builds
-// (build.build_variant), measured in profiles/archive/r04_c6_*.
-#ifndef DFM_STORE_FLAVOUR
-#define DFM_STORE_FLAVOUR 0
-#endif
+// How the volume's 16-byte vectors leave the CU: non-temporal (global_store_dwordx4 ... nt).  Plain, sc1,
+// sc0 sc1 (write-through) and sc1 nt stores were measured in profiles/archive/r04_c6_*.
 __device__ __forceinline__ void vol_store16(const u32x4_t &v, void *p)
 {
-#if DFM_STORE_FLAVOUR == 0
     __builtin_nontemporal_store(v, (u32x4_t *)p);
-#elif DFM_STORE_FLAVOUR == 1
-    *(u32x4_t *)p = v;
-#elif DFM_STORE_FLAVOUR == 2
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-#elif DFM_STORE_FLAVOUR == 3
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-#else
-    asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
-#endif
 }
 
 // s_waitcnt immediate (gfx9 encoding) that waits only on vmcnt <= n
@@ -396,10 +383,6 @@ struct TileGrid {
 // because the second buffer is addressed through the 16-bit immediate offset of ds_read_b128
 constexpr int PIPE_BUF_SLOTS = 2504;  // 8 rows of 311 pixels + pad
 constexpr int PIPE_LDS_BYTES = (8 + 2 * PIPE_BUF_SLOTS) * 16;
-// experiments (build_variant): how the matrix-core unpack is written
-#ifndef DFM_MX_MODE
-#define DFM_MX_MODE 1   // 1 products and chain steps in a pinned order, 2 left to hipcc
-#endif
 template <int N> struct IntC { static constexpr int value = N; };
 
 template <typename T, int NT, bool LDS, int V, bool PIPE = false, bool MXK = false>
@@ -668,20 +651,6 @@ __device__ __forceinline__ int tile_body(
 #define DFM_TAP_READ(dst, addr) \
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(BOFF))
             const mx_f32x4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
-            // one tap -> its CB channels in fp32 (two 4x4x4 products, 4 channels each)
-            auto cvt = [&](const u32x4_t &qq, float (&f)[CB]) {
-                mx_bf16x4 b0, b1;
-                const uint32_t h0[2] = {qq.x, qq.y}, h1[2] = {qq.z, qq.w};
-                __builtin_memcpy(&b0, h0, 8);
-                __builtin_memcpy(&b1, h1, 8);
-                const mx_f32x4 lo = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(mx_sel, b0, z4, 0, 0, 0);
-                f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-                if constexpr (CB == 8) {  // (the branch only runs for bf16: CB == 8)
-                    const mx_f32x4 hi = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(mx_sel, b1, z4, 0, 0, 0);
-                    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-                }
-            };
-            (void)cvt;
             // half a tap (4 channels): ONE 4x4x4 product
             auto cvt_half = [&](uint32_t lo, uint32_t hi, float *f) {
                 mx_bf16x4 bfrag;
@@ -718,18 +687,6 @@ __device__ __forceinline__ int tile_body(
                 // the matrix pipe (8 clocks), and products placed right in front of their consumers wait out
                 // the latency.  hipcc's own placement varies from build to build between 5.16 and 5.7 ms
                 // (profiles/archive/r04_c21/c22/c23), so the order is pinned with scheduling fences.
-#if DFM_MX_MODE == 2
-                const float e = 1.0f - w, s2 = 1.0f - n;
-                const float wt[4] = {s2 * e, s2 * w, n * e, n * w};  // nw ne sw se: blend_nomask's chain
-                float r[CB];
-#pragma unroll
-                for (int c4 = 0; c4 < 4; ++c4) {
-                    float f[CB];
-                    cvt(q[cb][c4], f);
-#pragma unroll
-                    for (int k = 0; k < CB; ++k) r[k] = c4 == 0 ? f[k] * wt[0] : __builtin_fmaf(f[k], wt[c4], r[k]);
-                }
-#else
                 float fa[CB], fb[CB], r[CB];
 #define DFM_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define DFM_CHAIN(dst, src, wgt, lo, first)                                                          \
@@ -769,7 +726,6 @@ __device__ __forceinline__ int tile_body(
                 DFM_CHAIN(r, fb, wt[3], 4, false);
 #undef DFM_CHAIN
 #undef DFM_FENCE
-#endif
                 // (pins the chain here: the vectoriser otherwise builds one tree from the 16-byte store
                 // vectors down through all 8 points and sinks every chain below the last conversion)
                 if constexpr (CB == 8)
@@ -1124,473 +1080,6 @@ __global__ __launch_bounds__(256) void sweep_patch_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// backward: grad feats += scatter(grad_out * weights); grid (ceil(N/256), B)
-// ---------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void sweep_bwd_kernel(
-    SweepGeom g, const T *__restrict__ gout, const float *__restrict__ depths,
-    const float *__restrict__ P, const float *__restrict__ Pinv, const float *__restrict__ Tm,
-    float *__restrict__ gcur, float *__restrict__ gprev)
-{
-    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int b = blockIdx.y;
-    if (n >= g.N) return;
-    const int hw = g.h_out * g.w_out;
-    const int d = (int)(n / hw);
-    const int rem = (int)(n - (long long)d * hw);
-    const int hi = rem / g.w_out;
-    const int wi = rem - hi * g.w_out;
-    float cx, cy, px, py;
-    sweep_point(g, P + b * 16, Pinv + b * 16, Tm + b * 16, depths[d], hi, wi, cx, cy, px, py,
-                nullptr);
-    const Tap tc = make_tap(cx, cy, g.h_in, g.w_in);
-    const Tap tp = make_tap(px, py, g.h_in, g.w_in);
-    const int HW = g.h_in * g.w_in;
-    const int c00 = tc.iy * g.w_in + tc.ix, c01 = c00 + tc.dx;
-    const int c10 = c00 + tc.dy * g.w_in, c11 = c10 + tc.dx;
-    const int p00 = tp.iy * g.w_in + tp.ix, p01 = p00 + tp.dx;
-    const int p10 = p00 + tp.dy * g.w_in, p11 = p10 + tp.dx;
-    const T *gc = gout + ((size_t)b * 2 * g.C) * g.N + n;
-    const T *gp = gc + (size_t)g.C * g.N;
-    float *dc = gcur + (size_t)b * g.C * HW;
-    float *dp = gprev + (size_t)b * g.C * HW;
-    for (int c = 0; c < g.C; ++c) {
-        const float go_c = elem<T>::load(gc[(size_t)c * g.N]);
-        const float go_p = elem<T>::load(gp[(size_t)c * g.N]);
-        if (tc.ok & 1u) atomicAdd(dc + c00, go_c * tc.nw);
-        if (tc.ok & 2u) atomicAdd(dc + c01, go_c * tc.ne);
-        if (tc.ok & 4u) atomicAdd(dc + c10, go_c * tc.sw);
-        if (tc.ok & 8u) atomicAdd(dc + c11, go_c * tc.se);
-        if (tp.ok & 1u) atomicAdd(dp + p00, go_p * tp.nw);
-        if (tp.ok & 2u) atomicAdd(dp + p01, go_p * tp.ne);
-        if (tp.ok & 4u) atomicAdd(dp + p10, go_p * tp.sw);
-        if (tp.ok & 8u) atomicAdd(dp + p11, go_p * tp.se);
-        dc += HW;
-        dp += HW;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// backward: LDS-accumulating tiles.
-// A workgroup = one band of 256 lattice points (same (h, w) for every plane) of ONE map x G plane
-// groups (1024 lanes, G = 4 for the prev map; 512 lanes, G = 2 for the cur map), over a chunk of
-// <= BWD_MAXP depth planes: lane (tid & 255) is the point, (tid >> 8) takes the planes
-// p = group, group + G, ...
-//   * Footprints once: a prologue computes every (plane, point) sampling position with the
-//     forward kernel's own sweep_point_map and keeps it in an LDS table (corner + in-bounds bits
-//     and the two fractions: 12 bytes per entry), so the C/CW channel passes that follow never
-//     touch the geometry again.  (Round 1 re-derived the position per plane per pass and was
-//     VALU-bound on exactly that: 34 of 39 ms at N*.)
-//   * Per pass of CW channels the taps' gradients are added into a slab of feature rows in LDS
-//     ([channel][row][x], 64-bit two's-complement fixed point: integer LDS atomics run at 10-14
-//     lanes per clock, ds_add_f32 at 0.33 -- profiles/archive/r01_atomic_microbench.txt); the slab goes
-//     to the global gradient with ONE coalesced fp32 atomic per touched pixel at the end of each
-//     slab window (the longest run of planes whose rows fit; the chunk, unless the footprint
-//     drifts far).
-//       cur map : x = w +- 1e-5, the footprint stays inside a 3x3 block anchored at the lane's
-//                 smallest corner: gradients are summed over the lane's planes in registers and
-//                 scattered once per window (a lane whose footprint leaves its block -- general
-//                 poses -- scatters that plane's taps straight to memory);
-//       prev map: the footprint drifts with depth; the four taps are scattered per plane.
-//   * The fixed-point scale is LOCAL: the prev kernel scans the pass's gradient values of its own
-//     (chunk, band) first (they are re-read from L2 right after), the cur kernel takes the maximum
-//     of its register sums at scatter time -- no pass over the whole gradient volume
-//     (absmax_bits_kernel: 5 ms of the 39 at N*), no device allocation.  An all-zero pass is
-//     skipped; a pass holding Inf / NaN takes plain float atomics so they propagate like torch's.
-// ---------------------------------------------------------------------------
-constexpr int BWD_MAXP = 32;  // depth planes per workgroup, at most
-constexpr int BWD_PTS = 256;  // lattice points per band
-// plane groups per workgroup: 4 for the prev map (70 VGPRs, LDS-atomic latency wants many waves),
-// 2 for the cur map (its 3x3 register block needs more than the 128 VGPRs a 1024-lane group allows)
-__host__ __device__ constexpr int bwd_groups(int half) { return half ? 4 : 2; }
-
-struct BwdGrid {
-    int batch, bands, band_pts, planes, dchunks, rows;
-    int ablate;  // debug builds only (DFM_BWD_ABLATE): 1 no gradient loads, 2 no slab atomics, 4 no flush
-    int grad_cl;  // 1: the gradient volume is stored channels-last, (B, D, h, w, 2C) (torch channels_last_3d)
-    int row_tiles;  // 0: bands are runs of band_pts points of the flat (h, w) index;
-                    // > 0 (strided sweeps): that many bands per lattice row, none crossing rows --
-                    // consecutive lattice rows sample feature rows `cost_sample_factor` apart,
-                    // which one slab window cannot hold
-    int split;      // 1: only the planes before sweep_zoom_split (the matrix-product backward takes the rest)
-};
-
-// float -> 64-bit two's-complement fixed point (|x| < 2^61 after scaling): high word =
-// floor(x / 2^32), low word = x - high * 2^32, which the fma delivers exactly except for a negative
-// x of tiny magnitude, whose 2^32 - |x| rounds to 2^32 and saturates the conversion -- one unit of
-// 2^-50 of the local maximum.  Five VALU operations; the pair is assembled from the two converted
-// words (the first version went through a float -> u64 conversion: 12 operations per add).
-__device__ __forceinline__ unsigned long long bwd_to_fixed(float x)
-{
-    const float hif = floorf(x * 2.3283064365386963e-10f);
-    const float lof = __builtin_fmaf(hif, -4294967296.0f, x);  // in [0, 2^32]
-    unsigned lo;
-    asm("v_cvt_u32_f32 %0, %1" : "=v"(lo) : "v"(lof));  // saturating
-    const unsigned hi = (unsigned)(int)hif;
-    return ((unsigned long long)hi << 32) | (unsigned long long)lo;
-}
-
-// scale 2^sh with max|x| * 2^sh < 2^50 from the raw bits of max|x| (finite, non-zero)
-__device__ __forceinline__ void bwd_scale(unsigned mb, float &fx_scale, float &fx_inv)
-{
-    const int sh = min(120, max(-100, 50 - ((int)(mb >> 23) - 127 + 1)));
-    fx_scale = __uint_as_float((unsigned)(sh + 127) << 23);
-    fx_inv = __uint_as_float((unsigned)(127 - sh) << 23);
-}
-
-#ifdef DFM_DEBUG_HOOKS
-#define BWD_ABLATE(bit) ((tg.ablate & (bit)) != 0)
-#else
-#define BWD_ABLATE(bit) false
-#endif
-template <typename T, int CW, int HALF>
-__global__ __launch_bounds__(BWD_PTS * bwd_groups(HALF)) void sweep_bwd_tile_kernel(
-    SweepGeom g, SweepFast fast, BwdGrid tg, const T *__restrict__ gout,
-    const float *__restrict__ depths, const float *__restrict__ P, const float *__restrict__ Pinv,
-    const float *__restrict__ Tm, float *__restrict__ gcur, float *__restrict__ gprev)
-{
-    constexpr int BWD_GROUPS = bwd_groups(HALF);
-    constexpr int NT = BWD_PTS * BWD_GROUPS;
-    constexpr int VB = 8;  // plane slots whose gradient values are fetched together (one latency)
-    extern __shared__ __attribute__((aligned(16))) unsigned long long slab[];
-    __shared__ int yr[2 * BWD_MAXP];
-    __shared__ unsigned wgm[3];  // rotating slots of the workgroup-wide maximum (see wg_max)
-    __shared__ int wins[4 * BWD_MAXP + 1];  // slab windows of the chunk: count, then {first, last plane, y0, top}
-    // block id = (band*dchunks + dchunk)*batch + b
-    int th = blockIdx.x;
-    const int b = th % tg.batch;
-    th /= tg.batch;
-    const int dchunk = th % tg.dchunks;
-    const int band = th / tg.dchunks;
-    const int tid = threadIdx.x, pt = tid & (BWD_PTS - 1), grp = tid >> 8;
-    const int hw = g.h_out * g.w_out;
-    const int W = g.w_in, H = g.h_in, HW = H * W;
-    int p_lo = band * tg.band_pts, p_hi = min(p_lo + tg.band_pts, hw);
-    if (tg.row_tiles > 0) {
-        const int row = band / tg.row_tiles, t = band - row * tg.row_tiles;
-        p_lo = row * g.w_out + t * tg.band_pts;
-        p_hi = min(p_lo + tg.band_pts, (row + 1) * g.w_out);
-    }
-    const int d_lo = dchunk * tg.planes;
-    int d_hi = min(d_lo + tg.planes, g.D);
-    const float *Pb = P + b * 16, *Pib = Pinv + b * 16, *Tb = Tm + b * 16;
-    if (tg.split) {  // workgroup-uniform
-        d_hi = min(d_hi, sweep_zoom_split<HALF>(g, fast, Pb, Pib, Tb, depths, SWEEP_BWD_ZOOM_FOUR, threadIdx.x,
-                                                BWD_PTS * BWD_GROUPS, &yr[0]));
-        if (d_hi <= d_lo) return;
-        __syncthreads();  // yr is initialised below
-    }
-    const int np = d_hi - d_lo;
-    const int rows = tg.rows, slab_c = rows * W;
-    // footprint table behind the slab: [plane][point] x {packed, fw, fn}
-    uint32_t *fpT = (uint32_t *)(slab + (size_t)CW * slab_c);
-    float *fwT = (float *)(fpT + tg.planes * BWD_PTS);
-    float *fnT = fwT + tg.planes * BWD_PTS;
-    const int idx = p_lo + pt;
-    const bool live = idx < p_hi;
-    const int hi = idx / g.w_out, wi = idx - hi * g.w_out;
-
-    for (int i = tid; i < 2 * BWD_MAXP; i += NT) yr[i] = (i & 1) ? -1 : 0x7fffffff;
-    for (int i = tid; i < CW * slab_c; i += NT) slab[i] = 0ull;
-    if (tid < 3) wgm[tid] = 0u;
-    __syncthreads();
-    // workgroup-wide maximum with ONE barrier per call: round k accumulates into slot k % 3 and
-    // clears slot (k + 1) % 3, which nobody reads (round k - 1 reads slot (k - 1) % 3) or
-    // writes (round k + 1 starts after this barrier) meanwhile
-    int mround = 0;
-    auto wg_max = [&](unsigned m) -> unsigned {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-        const int slot = mround % 3;
-        if ((tid & 63) == 0 && m) atomicMax(&wgm[slot], m);
-        if (tid == 0) wgm[(mround + 1) % 3] = 0u;
-        __syncthreads();
-        ++mround;
-        return wgm[slot];
-    };
-
-    // ---- footprints of the band's points in every plane of the chunk -> LDS table ------------
-    int bx = 0x7fffffff, by = 0x7fffffff;  // cur map: block anchor = this lane's smallest corner
-    for (int p = grp; p < np; p += BWD_GROUPS) {
-        int ymin = 0x7fffffff, ymax = -1;
-        uint32_t f = 0u;
-        float fw = 0.0f, fn = 0.0f;
-        if (live) {
-            float sx, sy;
-            sweep_point_map<HALF>(g, fast, Pb, Pib, Tb, depths[d_lo + p], hi, wi, sx, sy);
-            f = bwd_footprint(sx, sy, H, W, fw, fn);
-            if (f) {
-                const int iyn = (int)(f & 0x1fffu) - 1, ixw = (int)((f >> 13) & 0x1fffu) - 1;
-                if (f & (1u << 29)) { ymin = min(ymin, iyn); ymax = max(ymax, iyn); }
-                if (f & (1u << 30)) { ymin = min(ymin, iyn + 1); ymax = max(ymax, iyn + 1); }
-                bx = min(bx, ixw);
-                by = min(by, iyn);
-            }
-        }
-        fpT[p * BWD_PTS + pt] = f;
-        fwT[p * BWD_PTS + pt] = fw;
-        fnT[p * BWD_PTS + pt] = fn;
-#pragma unroll
-        for (int s2 = 32; s2 > 0; s2 >>= 1) {
-            ymin = min(ymin, __shfl_xor(ymin, s2));
-            ymax = max(ymax, __shfl_xor(ymax, s2));
-        }
-        if ((tid & 63) == 0 && ymax >= 0) {
-            atomicMin(&yr[2 * p], ymin);
-            atomicMax(&yr[2 * p + 1], ymax);
-        }
-    }
-    __syncthreads();
-    // slab windows: maximal runs of planes whose rows fit `rows` slab rows -- the same for every
-    // channel pass, so they are laid out once
-    if (tid == 0) {
-        int nw = 0, p = 0;
-        while (p < np) {
-            while (p < np && yr[2 * p + 1] < yr[2 * p]) ++p;  // planes that miss the map
-            if (p >= np) break;
-            int umin = yr[2 * p], umax = yr[2 * p + 1], e = p;
-            while (e + 1 < np) {
-                const int l2 = yr[2 * (e + 1)], u2 = yr[2 * (e + 1) + 1];
-                if (u2 >= l2) {
-                    if (max(umax, u2) - min(umin, l2) + 1 > rows) break;
-                    umin = min(umin, l2);
-                    umax = max(umax, u2);
-                }
-                ++e;
-            }
-            wins[1 + 4 * nw] = p;
-            wins[2 + 4 * nw] = e;
-            wins[3 + 4 * nw] = umin;
-            wins[4 + 4 * nw] = min(umax, umin + rows - 1);
-            ++nw;
-            p = e + 1;
-        }
-        wins[0] = nw;
-    }
-    __syncthreads();
-    const int nwin = __builtin_amdgcn_readfirstlane(wins[0]);
-
-    // element strides of the gradient volume: the reference layout (B, 2C, D, h, w), or channels-last
-    // (B, D, h, w, 2C) -- what the NDHWC aggregation stack's backward hands over (read in place: the
-    // 236 MB layout conversion at config K cost 2.2 ms per training step, and a lane's CW channels of a
-    // (plane, point) are then adjacent)
-    const size_t s_chan = tg.grad_cl ? (size_t)1 : (size_t)g.N;
-    const size_t s_plane = tg.grad_cl ? (size_t)hw * 2 * g.C : (size_t)hw;
-    const size_t s_point = tg.grad_cl ? (size_t)2 * g.C : (size_t)1;
-    const T *go = gout + (size_t)b * 2 * g.C * g.N + (size_t)HALF * g.C * s_chan + (size_t)d_lo * s_plane +
-                  (size_t)min(idx, p_hi - 1) * s_point;
-    float *gf = (HALF ? gprev : gcur) + (size_t)b * g.C * HW;
-
-    for (int c0 = 0; c0 < g.C; c0 += CW) {
-        const int nc = min(CW, g.C - c0);
-        const T *gp = go + (size_t)c0 * s_chan;
-        float fx_scale = 1.0f, fx_inv = 1.0f;
-        bool plain = false;  // Inf / NaN in this pass (window): plain float atomics
-        int y0 = -1, top = -1;
-        auto flush = [&]() {
-            if (BWD_ABLATE(4)) return;
-            const int cnt = (top - y0 + 1) * W;
-            for (int c = 0; c < nc; ++c) {
-                unsigned long long *sl = slab + c * slab_c;
-                float *dst = gf + (size_t)(c0 + c) * HW + (size_t)y0 * W;
-                for (int r = tid; r < cnt; r += NT) {
-                    const unsigned long long v = sl[r];
-                    if (v != 0ull) {
-                        const float f = __builtin_fmaf((float)(int)(v >> 32), 4294967296.0f, (float)(unsigned)v);
-                        atomicAdd(dst + r, f * fx_inv);
-                        sl[r] = 0ull;
-                    }
-                }
-            }
-        };
-        // gradient values of up to VB of this lane's planes (slots k0 .. k0+VB-1; slot k is plane
-        // grp + k*G), all loads in flight together; planes outside the chunk / map give 0
-        auto load_block = [&](int k0, T (&gv)[VB][CW]) {
-            // every load is unconditional (clamped, always-valid address) and the masking happens on
-            // the values afterwards: a load under a runtime condition makes hipcc branch around it
-            // and wait for each one separately (cdna_hip_programming.md, ".s-level traps" (c))
-#pragma unroll
-            for (int k = 0; k < VB; ++k) {
-                const int p = min(grp + (k0 + k) * BWD_GROUPS, np - 1);
-#pragma unroll
-                for (int c = 0; c < CW; ++c) gv[k][c] = gp[(size_t)p * s_plane + (size_t)min(c, nc - 1) * s_chan];
-            }
-#pragma unroll
-            for (int k = 0; k < VB; ++k) {
-                const int p = grp + (k0 + k) * BWD_GROUPS;
-                const bool on = p < np && fpT[min(p, np - 1) * BWD_PTS + pt] != 0u && !BWD_ABLATE(1);
-#pragma unroll
-                for (int c = 0; c < CW; ++c) gv[k][c] = (on && c < nc) ? gv[k][c] : T(0);
-            }
-        };
-
-        if constexpr (HALF == 1) {
-            static_assert(BWD_MAXP / bwd_groups(1) <= VB, "one block holds all planes of a lane");
-            T gv[VB][CW];
-            load_block(0, gv);
-            // ---- scale of this pass: max |grad| over the workgroup's values ----------------
-            unsigned m = 0u;
-#pragma unroll
-            for (int k = 0; k < VB; ++k)
-#pragma unroll
-                for (int c = 0; c < CW; ++c) m = max(m, __float_as_uint(elem<T>::load(gv[k][c])) & 0x7fffffffu);
-            const unsigned mb = wg_max(m);
-            if (mb == 0u) continue;  // nothing to add in this pass
-            plain = (mb >> 23) == 0xffu;
-            if (!plain) bwd_scale(mb, fx_scale, fx_inv);
-            // ---- windows of planes; the four taps of every plane go into the slab ----------
-            for (int wi_ = 0; wi_ < nwin; ++wi_) {
-                const int pw = __builtin_amdgcn_readfirstlane(wins[1 + 4 * wi_]);
-                const int pe = __builtin_amdgcn_readfirstlane(wins[2 + 4 * wi_]);
-                y0 = __builtin_amdgcn_readfirstlane(wins[3 + 4 * wi_]);
-                top = __builtin_amdgcn_readfirstlane(wins[4 + 4 * wi_]);
-#pragma unroll
-                for (int k = 0; k < VB; ++k) {
-                    const int p = grp + k * BWD_GROUPS;
-                    if (p < pw || p > pe) continue;
-                    const uint32_t f = fpT[p * BWD_PTS + pt];
-                    if (!f) continue;
-                    const int iyn = (int)(f & 0x1fffu) - 1, ixw = (int)((f >> 13) & 0x1fffu) - 1;
-                    const float fw = fwT[p * BWD_PTS + pt], fn = fnT[p * BWD_PTS + pt];
-                    const float cwt = (f & (1u << 27)) ? 1.0f - fw : 0.0f, cet = (f & (1u << 28)) ? fw : 0.0f;
-                    const float rnt = (f & (1u << 29)) ? 1.0f - fn : 0.0f, rst = (f & (1u << 30)) ? fn : 0.0f;
-                    const float wq[4] = {rnt * cwt, rnt * cet, rst * cwt, rst * cet};
-                    float gvf[CW];
-#pragma unroll
-                    for (int c = 0; c < CW; ++c) gvf[c] = elem<T>::load(gv[k][c]);
-                    const int rr0 = iyn - y0;  // >= 0 for an in-bounds north row: y0 <= the window's first row
-                    if ((f & 0x78000000u) == 0x78000000u && rr0 + 1 < rows && !plain && !BWD_ABLATE(2)) {
-                        // interior footprint inside the slab window (nearly every point): four taps x CW
-                        // channels without a branch; channels past nc carry 0 into slab rows nobody flushes
-                        unsigned long long *l = slab + rr0 * W + ixw;
-                        const float w0 = wq[0] * fx_scale, w1 = wq[1] * fx_scale;
-                        const float w2 = wq[2] * fx_scale, w3 = wq[3] * fx_scale;
-#pragma unroll
-                        for (int c = 0; c < CW; ++c) {
-                            unsigned long long *lc = l + c * slab_c;
-                            atomicAdd(lc, bwd_to_fixed(gvf[c] * w0));
-                            atomicAdd(lc + 1, bwd_to_fixed(gvf[c] * w1));
-                            atomicAdd(lc + W, bwd_to_fixed(gvf[c] * w2));
-                            atomicAdd(lc + W + 1, bwd_to_fixed(gvf[c] * w3));
-                        }
-                        continue;
-                    }
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        if (wq[q] == 0.0f) continue;  // out-of-bounds (or weightless) tap
-                        const int py = iyn + (q >> 1), px = ixw + (q & 1);
-                        const int rr = py - y0;  // >= 0: y0 <= the window's first row
-                        if (BWD_ABLATE(2)) continue;
-                        if (rr < rows && !plain) {
-                            unsigned long long *l = slab + rr * W + px;
-                            const float ws = wq[q] * fx_scale;
-#pragma unroll
-                            for (int c = 0; c < CW; ++c) atomicAdd(l + c * slab_c, bwd_to_fixed(gvf[c] * ws));
-                        } else {  // taller than the slab window (rare), or a non-finite pass
-                            float *gl = gf + (size_t)c0 * HW + (size_t)py * W + px;
-#pragma unroll
-                            for (int c = 0; c < CW; ++c)
-                                if (c < nc) atomicAdd(gl + (size_t)c * HW, gvf[c] * wq[q]);
-                        }
-                    }
-                }
-                __syncthreads();
-                flush();
-                __syncthreads();
-            }
-        } else {
-            // ---- cur map: per window, sum over this lane's planes in registers, one scatter -
-            for (int wi_ = 0; wi_ < nwin; ++wi_) {
-                const int pw = __builtin_amdgcn_readfirstlane(wins[1 + 4 * wi_]);
-                const int pe = __builtin_amdgcn_readfirstlane(wins[2 + 4 * wi_]);
-                y0 = __builtin_amdgcn_readfirstlane(wins[3 + 4 * wi_]);
-                top = __builtin_amdgcn_readfirstlane(wins[4 + 4 * wi_]);
-                float acc[9][CW];
-#pragma unroll
-                for (int cell = 0; cell < 9; ++cell)
-#pragma unroll
-                    for (int c = 0; c < CW; ++c) acc[cell][c] = 0.0f;
-                for (int k0 = 0; k0 < BWD_MAXP / BWD_GROUPS; k0 += VB) {
-                    if (grp + k0 * BWD_GROUPS > pe) break;  // uniform per wave (grp is)
-                    T gv[VB][CW];
-                    load_block(k0, gv);
-#pragma unroll
-                    for (int k = 0; k < VB; ++k) {
-                        const int p = grp + (k0 + k) * BWD_GROUPS;
-                        if (p < pw || p > pe) continue;
-                        const uint32_t f = fpT[p * BWD_PTS + pt];
-                        if (!f) continue;
-                        float gvf[CW];
-#pragma unroll
-                        for (int c = 0; c < CW; ++c) gvf[c] = elem<T>::load(gv[k][c]);
-                        const int iyn = (int)(f & 0x1fffu) - 1, ixw = (int)((f >> 13) & 0x1fffu) - 1;
-                        const float fw = fwT[p * BWD_PTS + pt], fn = fnT[p * BWD_PTS + pt];
-                        const float cw = (f & (1u << 27)) ? 1.0f - fw : 0.0f, ce = (f & (1u << 28)) ? fw : 0.0f;
-                        const float rn = (f & (1u << 29)) ? 1.0f - fn : 0.0f, rs = (f & (1u << 30)) ? fn : 0.0f;
-                        const int ox = ixw - bx, oy = iyn - by;  // 0 or 1 while the footprint stays in the block
-                        if ((unsigned)ox <= 1u && (unsigned)oy <= 1u) {
-                            const bool xlo = ox == 0, ylo = oy == 0;
-                            const float cx[3] = {xlo ? cw : 0.0f, xlo ? ce : cw, xlo ? 0.0f : ce};
-                            const float ry[3] = {ylo ? rn : 0.0f, ylo ? rs : rn, ylo ? 0.0f : rs};
-#pragma unroll
-                            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                                for (int q = 0; q < 3; ++q) {
-                                    const float wgt = ry[r] * cx[q];
-#pragma unroll
-                                    for (int c = 0; c < CW; ++c)
-                                        acc[3 * r + q][c] = __builtin_fmaf(gvf[c], wgt, acc[3 * r + q][c]);
-                                }
-                        } else {  // the footprint left the lane's block (general poses): straight to memory
-                            const float wq[4] = {rn * cw, rn * ce, rs * cw, rs * ce};
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                if (wq[q] == 0.0f) continue;
-                                float *gl = gf + (size_t)c0 * HW + (size_t)(iyn + (q >> 1)) * W + ixw + (q & 1);
-#pragma unroll
-                                for (int c = 0; c < CW; ++c)
-                                    if (c < nc) atomicAdd(gl + (size_t)c * HW, gvf[c] * wq[q]);
-                            }
-                        }
-                    }
-                }
-                // scale from the register sums themselves
-                unsigned m = 0u;
-#pragma unroll
-                for (int cell = 0; cell < 9; ++cell)
-#pragma unroll
-                    for (int c = 0; c < CW; ++c) m = max(m, __float_as_uint(acc[cell][c]) & 0x7fffffffu);
-                const unsigned mb = wg_max(m);
-                if (mb != 0u) {
-                    const bool pl = (mb >> 23) == 0xffu;
-                    if (!pl) bwd_scale(mb, fx_scale, fx_inv);
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) {
-                        const int py = by + r, rr = py - y0;
-#pragma unroll
-                        for (int q = 0; q < 3; ++q) {
-                            const int px = bx + q;
-#pragma unroll
-                            for (int c = 0; c < CW; ++c) {
-                                const float v = acc[3 * r + q][c];
-                                if (c >= nc || v == 0.0f || BWD_ABLATE(2)) continue;  // (out-of-bounds cells carry 0)
-                                if (!pl && rr >= 0 && rr < rows)
-                                    atomicAdd(slab + c * slab_c + rr * W + px, bwd_to_fixed(v * fx_scale));
-                                else
-                                    atomicAdd(gf + (size_t)(c0 + c) * HW + (size_t)py * W + px, v);
-                            }
-                        }
-                    }
-                    __syncthreads();
-                    if (!pl) flush();
-                    __syncthreads();
-                }
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
 // parity aid: normalised grids of sample b
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sweep_grid_kernel(SweepGeom g, int b,
@@ -1675,15 +1164,15 @@ __global__ void camera_prepare_kernel(const float *__restrict__ cam2img, int row
 // ---------------------------------------------------------------------------
 int check_desc(const dfm_sweep_desc *d)
 {
-    if (!d) return fail(DFM_ERR_INVALID_ARG, "desc is NULL%s");
+    if (!d) return set_error(DFM_ERR_INVALID_ARG, "desc is NULL");
     if (d->batch <= 0 || d->channels <= 0 || d->h_in <= 0 || d->w_in <= 0 || d->num_depths <= 0 ||
         d->h_out <= 0 || d->w_out <= 0)
-        return fail(DFM_ERR_INVALID_ARG, "non-positive size in dfm_sweep_desc%s");
+        return set_error(DFM_ERR_INVALID_ARG, "non-positive size in dfm_sweep_desc");
     if (d->dtype != DFM_F32 && d->dtype != DFM_BF16)
-        return fail(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16%s");
+        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
     if ((long long)d->h_in * d->w_in >= (1ll << 31) / 64)
-        return fail(DFM_ERR_UNSUPPORTED, "feature map too large for 32-bit tap offsets%s");
-    if (d->batch > 32767) return fail(DFM_ERR_UNSUPPORTED, "batch > 32767%s");
+        return set_error(DFM_ERR_UNSUPPORTED, "feature map too large for 32-bit tap offsets");
+    if (d->batch > 32767) return set_error(DFM_ERR_UNSUPPORTED, "batch > 32767");
     return DFM_OK;
 }
 
@@ -1758,25 +1247,23 @@ int resolve(const dfm_sweep_desc *d, const dfm_sweep_opts *o, Launch &L)
     L.ppl = o && o->points_per_lane ? o->points_per_lane : CB;
     L.align = o && o->store_align_points ? o->store_align_points : 64;
     if (L.align != 8 && L.align != 16 && L.align != 32 && L.align != 64)
-        return fail(DFM_ERR_INVALID_ARG, "opts: store_align_points in {8,16,32,64}%s");
+        return set_error(DFM_ERR_INVALID_ARG, "opts: store_align_points in {8,16,32,64}");
     L.pair = o && o->pair_stores ? (o->pair_stores == 1) : 1;  // 0 default (on), 1 on, 2 off
     // 0 default (matrix core), 1 matrix core, 2 VALU
-    if (o && (o->unpack < 0 || o->unpack > 2)) return fail(DFM_ERR_INVALID_ARG, "opts: unpack must be 0, 1 or 2%s");
+    if (o && (o->unpack < 0 || o->unpack > 2)) return set_error(DFM_ERR_INVALID_ARG, "opts: unpack must be 0, 1 or 2");
     L.unpack = o && o->unpack ? (o->unpack == 1) : 1;
     L.pipe = o && o->pipeline ? o->pipeline : 2;
-    if (L.pipe != 1 && L.pipe != 2) return fail(DFM_ERR_INVALID_ARG, "opts: pipeline must be 0, 1 or 2%s");
+    if (L.pipe != 1 && L.pipe != 2) return set_error(DFM_ERR_INVALID_ARG, "opts: pipeline must be 0, 1 or 2");
     if (!L.lds_kib) L.lds_kib = L.pipe >= 2 ? 80 : 52;
-    if (L.kernel < 0 || L.kernel > 5) return fail(DFM_ERR_INVALID_ARG, "opts: kernel must be 0..5%s");
+    if (L.kernel < 0 || L.kernel > 5) return set_error(DFM_ERR_INVALID_ARG, "opts: kernel must be 0..5");
     if (L.lanes != 128 && L.lanes != 256 && L.lanes != 512 && L.lanes != 1024)
-        return fail(DFM_ERR_INVALID_ARG, "opts: lanes_per_workgroup in {128,256,512,1024}%s");
+        return set_error(DFM_ERR_INVALID_ARG, "opts: lanes_per_workgroup in {128,256,512,1024}");
     if (L.lds_kib < 4 || L.lds_kib > 160 || L.bpg < 1 || L.planes < 1 || L.band_chunk < 1)
-        return fail(DFM_ERR_INVALID_ARG,
-                    "opts: 4 <= lds_kib <= 160, blocks_per_group / planes / bands_per_chunk >= 1%s");
+        return set_error(DFM_ERR_INVALID_ARG, "opts: 4 <= lds_kib <= 160, blocks_per_group / planes / bands_per_chunk >= 1");
     if (L.ppl != CB && !(L.ppl == 4 && CB == 8 && L.lanes >= 256))
-        return fail(DFM_ERR_INVALID_ARG,
-                    "opts: points_per_lane is 16/sizeof(T), or 4 for bf16 with >= 256 lanes%s");
+        return set_error(DFM_ERR_INVALID_ARG, "opts: points_per_lane is 16/sizeof(T), or 4 for bf16 with >= 256 lanes");
     if (L.lanes == 1024 && L.ppl != 4)
-        return fail(DFM_ERR_INVALID_ARG, "opts: 1024 lanes need points_per_lane = 4%s");
+        return set_error(DFM_ERR_INVALID_ARG, "opts: 1024 lanes need points_per_lane = 4");
     return DFM_OK;
 }
 
@@ -1819,8 +1306,8 @@ int launch_tiles(int which, const dfm_sweep_desc *d, const SweepGeom &g, const L
 #endif
     const long long nchunks = (tg.bands + tg.band_chunk - 1) / tg.band_chunk;
     const long long nb = nchunks * tg.band_chunk * tg.dgroups * 2 * d->batch * groups;
-    if (nb > 2147483647ll) return fail(DFM_ERR_UNSUPPORTED, "too many lattice points%s");
-    if ((size_t)(nb + 1) * 4 > flag_bytes(d)) return fail(DFM_ERR_WORKSPACE, "spill list too small%s");
+    if (nb > 2147483647ll) return set_error(DFM_ERR_UNSUPPORTED, "too many lattice points");
+    if ((size_t)(nb + 1) * 4 > flag_bytes(d)) return set_error(DFM_ERR_WORKSPACE, "spill list too small");
     int rc = DFM_OK;
     const SweepFast fast = make_fast(d);
     if (which == 2) {
@@ -1925,7 +1412,7 @@ int launch_fwd(const dfm_sweep_desc *d, const Launch &L, const void *cur, const 
     int rc = DFM_OK;
     if (which == 1) {
         const long long nb = (g.N + 255) / 256;
-        if (nb > 2147483647ll) return fail(DFM_ERR_UNSUPPORTED, "too many lattice points%s");
+        if (nb > 2147483647ll) return set_error(DFM_ERR_UNSUPPORTED, "too many lattice points");
         dim3 grid((unsigned)nb, d->batch);
         hipLaunchKernelGGL(sweep_gather_kernel<T>, grid, dim3(256), 0, st, g, cur_blk, prev_blk,
                            depths, P, Pinv, Tm, (T *)out);
@@ -1981,11 +1468,11 @@ int check_fwd_args(const dfm_sweep_desc *desc, const void *cur, const void *prev
     int rc = check_desc(desc);
     if (rc != DFM_OK) return rc;
     if (!cur || !prev || !depths || !cam2img || !cam2img_inv || !cur2prev || !out)
-        return fail(DFM_ERR_INVALID_ARG, "NULL device pointer%s");
+        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     if (!workspace || workspace_bytes < fwd_workspace_bytes(desc))
-        return fail(DFM_ERR_WORKSPACE, "workspace smaller than dfm_plane_sweep_workspace_bytes%s");
+        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_plane_sweep_workspace_bytes");
     if (((uintptr_t)workspace & 15) || ((uintptr_t)out & 1))
-        return fail(DFM_ERR_INVALID_ARG, "workspace must be 16-byte aligned%s");
+        return set_error(DFM_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
     return DFM_OK;
 }
 
@@ -2009,81 +1496,45 @@ bool takes_lds_tiles(const dfm_sweep_desc *d, const void *out)
 
 }  // namespace
 
+// shared with the other plane-sweep translation units
+int dfm::sweep_check_desc(const dfm_sweep_desc *d) { return check_desc(d); }
+dfm::SweepGeom dfm::sweep_make_geom(const dfm_sweep_desc *d) { return make_geom(d); }
+dfm::SweepFast dfm::sweep_make_fast(const dfm_sweep_desc *d) { return make_fast(d); }
+void dfm::sweep_set_last_kernel(int which) { g_last_kernel = which; }
+int dfm::sweep_bwd_scatter_launch(const dfm_sweep_desc *desc, const void *grad_out, const float *depths,
+                                  const float *cam2img, const float *cam2img_inv, const float *cur2prev,
+                                  float *grad_cur, float *grad_prev, void *stream)
+{
+    const SweepGeom g = make_geom(desc);
+    hipStream_t st = (hipStream_t)stream;
+    const long long nb = (g.N + 255) / 256;
+    if (nb > 2147483647ll) return set_error(DFM_ERR_UNSUPPORTED, "too many lattice points");
+    dim3 grid((unsigned)nb, desc->batch);
+    if (desc->dtype == DFM_F32)
+        hipLaunchKernelGGL(sweep_bwd_kernel<float>, grid, dim3(256), 0, st, g,
+                           (const float *)grad_out, depths, cam2img, cam2img_inv, cur2prev,
+                           grad_cur, grad_prev);
+    else
+        hipLaunchKernelGGL(sweep_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, g,
+                           (const bf16_t *)grad_out, depths, cam2img, cam2img_inv, cur2prev,
+                           grad_cur, grad_prev);
+    return DFM_OK;
+}
+
 extern "C" {
 
-DFM_API int dfm_version(void) { return 3; }
-DFM_API const char *dfm_last_error(void) { return g_err; }
 DFM_API int dfm_plane_sweep_last_kernel(void) { return g_last_kernel; }
-DFM_API int dfm_plane_sweep_bwd_last_kernel(void) { return g_last_bwd_kernel.load(); }
 #ifdef DFM_DEBUG_HOOKS
 // debug builds only (not in dfm_hip.h): device buffer of 64 x u64 per traced workgroup
 DFM_API void dfm_debug_set_trace(void *buf) { g_trace = (unsigned long long *)buf; }
 #endif
 
-DFM_API int dfm_profile_begin(int max_launches)
-{
-    if (max_launches <= 0 || max_launches > 65536)
-        return fail(DFM_ERR_INVALID_ARG, "max_launches out of range%s");
-    std::lock_guard<std::mutex> lk(g_prof.mu);
-    for (hipEvent_t e : g_prof.ev) (void)hipEventDestroy(e);
-    g_prof.ev.assign(2 * (size_t)max_launches, nullptr);
-    for (auto &e : g_prof.ev) HIP_TRY(hipEventCreate(&e));
-    g_prof.used = 0;
-    g_prof.on = true;
-    return DFM_OK;
-}
-
-DFM_API int dfm_profile_end(double *total_ms, int *launches)
-{
-    if (!total_ms || !launches) return fail(DFM_ERR_INVALID_ARG, "NULL output%s");
-    std::lock_guard<std::mutex> lk(g_prof.mu);
-    g_prof.on = false;
-    double sum = 0.0;
-    for (int i = 0; i + 1 < g_prof.used; i += 2) {
-        HIP_TRY(hipEventSynchronize(g_prof.ev[i + 1]));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, g_prof.ev[i], g_prof.ev[i + 1]));
-        sum += ms;
-    }
-    *total_ms = sum;
-    *launches = g_prof.used / 2;
-    for (hipEvent_t e : g_prof.ev) (void)hipEventDestroy(e);
-    g_prof.ev.clear();
-    g_prof.used = 0;
-    return DFM_OK;
-}
-
-}  // extern "C"
-
-// shared with the other translation units
-int dfm::sweep_check_desc(const dfm_sweep_desc *d) { return check_desc(d); }
-dfm::SweepGeom dfm::sweep_make_geom(const dfm_sweep_desc *d) { return make_geom(d); }
-dfm::SweepFast dfm::sweep_make_fast(const dfm_sweep_desc *d) { return make_fast(d); }
-void dfm::sweep_set_last_kernel(int which) { g_last_kernel = which; }
-void dfm::sweep_set_last_bwd_kernel(int which) { g_last_bwd_kernel.store(which); }
-bool dfm::profile_mark(void *stream, bool stop)
-{
-    hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(g_prof.mu);
-    if (!stop) {
-        if (!(g_prof.on && g_prof.used + 2 <= (int)g_prof.ev.size())) return false;
-        (void)hipEventRecord(g_prof.ev[g_prof.used], st);
-        return true;
-    }
-    if (!(g_prof.on && g_prof.used + 2 <= (int)g_prof.ev.size())) return false;
-    (void)hipEventRecord(g_prof.ev[g_prof.used + 1], st);
-    g_prof.used += 2;
-    return true;
-}
-
-extern "C" {
-
 DFM_API int dfm_camera_prepare(const float *cam2img, int32_t rows, int32_t cols, int32_t batch,
                                float *cam2img_4x4, float *cam2img_inv, void *stream)
 {
-    if (!cam2img || !cam2img_4x4 || !cam2img_inv) return fail(DFM_ERR_INVALID_ARG, "NULL device pointer%s");
+    if (!cam2img || !cam2img_4x4 || !cam2img_inv) return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     if ((rows != 3 && rows != 4) || (cols != 3 && cols != 4) || batch <= 0)
-        return fail(DFM_ERR_INVALID_ARG, "cam2img must be (B,3|4,3|4) with B >= 1%s");
+        return set_error(DFM_ERR_INVALID_ARG, "cam2img must be (B,3|4,3|4) with B >= 1");
     hipLaunchKernelGGL(camera_prepare_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                        cam2img, rows, cols, batch, cam2img_4x4, cam2img_inv);
     HIP_TRY(hipGetLastError());
@@ -2217,7 +1668,7 @@ DFM_API int dfm_plane_sweep_autotune(const dfm_sweep_desc *desc, const void *cur
                                  workspace, st);
                 (void)hipEventRecord(e1, st);
                 if (rc == DFM_OK && hipEventSynchronize(e1) != hipSuccess)
-                    rc = fail(DFM_ERR_HIP, "autotune: event sync failed%s");
+                    rc = set_error(DFM_ERR_HIP, "autotune: event sync failed");
                 float ms = 0.0f;
                 if (rc == DFM_OK) (void)hipEventElapsedTime(&ms, e0, e1);
                 if (rc == DFM_OK) rounds[i].push_back(ms);
@@ -2256,7 +1707,7 @@ DFM_API int dfm_plane_sweep_tuning(const dfm_sweep_desc *desc, dfm_sweep_opts *o
 {
     int rc = check_desc(desc);
     if (rc != DFM_OK) return rc;
-    if (!opts) return fail(DFM_ERR_INVALID_ARG, "NULL output%s");
+    if (!opts) return set_error(DFM_ERR_INVALID_ARG, "NULL output");
     TuneKey k;
     rc = tune_key(desc, k);
     if (rc != DFM_OK) return rc;
@@ -2268,305 +1719,11 @@ DFM_API int dfm_plane_sweep_tuning(const dfm_sweep_desc *desc, dfm_sweep_opts *o
     return 1;
 }
 
-// Which part did the process land on?  The tile kernel's store stream -- every workgroup writes a 4 KiB
-// run into each of the 2C channel planes of a sample, planes D*h*w elements apart -- sustains 5.1-5.3 TB/s
-// on most MI355X parts and ~3.9-4.1 TB/s on others (same binary, same clocks; a linear fill runs at
-// 6.8 TB/s on both: profiles/archive/r03_c17_*).  This probe writes zeros in exactly that pattern so that a
-// bench line can say which kind of part produced it.  `out` is overwritten with zeros.
-__global__ __launch_bounds__(256) void store_probe_kernel(uint4 *__restrict__ out, long long plane_vec,
-                                                          long long runs_per_plane, int planes, int pieces, int group)
-{
-    // block = (run, plane group, sample), run fastest: `pieces` x (256 lanes x 16 B = 4 KiB) contiguous per
-    // plane; walks the `group` planes of its plane group (group == planes: the tile kernel's pattern)
-    typedef unsigned int probe_u32x4 __attribute__((ext_vector_type(4)));
-    const long long run = blockIdx.x % runs_per_plane;
-    const int pg = (int)(blockIdx.x / runs_per_plane);
-    probe_u32x4 *p = (probe_u32x4 *)out + ((size_t)blockIdx.y * planes + (size_t)pg * group) * plane_vec +
-                     run * 256 * pieces + threadIdx.x;
-    const probe_u32x4 z = {0u, 0u, 0u, 0u};
-    const int n = min(group, planes - pg * group);
-    for (int c = 0; c < n; ++c)
-        for (int k = 0; k < pieces; ++k) __builtin_nontemporal_store(z, p + (size_t)c * plane_vec + k * 256);
-}
-
-DFM_API int dfm_store_probe(void *out, int32_t batch, int32_t planes, int64_t plane_bytes, int32_t run_bytes,
-                            int32_t planes_per_workgroup, void *stream)
-{
-    if (!out || batch <= 0 || planes <= 0 || plane_bytes < 4096 || ((uintptr_t)out & 15) || (plane_bytes & 15))
-        return fail(DFM_ERR_INVALID_ARG, "store probe: aligned buffer of batch x planes x plane_bytes%s");
-    const int pieces = run_bytes > 0 ? run_bytes / 4096 : 1;  // 0: the tile kernel's 4 KiB runs
-    if (pieces < 1 || pieces * 4096 != (run_bytes > 0 ? run_bytes : 4096) || plane_bytes < 4096ll * pieces)
-        return fail(DFM_ERR_INVALID_ARG, "store probe: run_bytes must be a multiple of 4096%s");
-    const int group = planes_per_workgroup > 0 ? std::min(planes_per_workgroup, planes) : planes;  // 0: all planes
-    const long long plane_vec = plane_bytes / 16, runs = plane_vec / (256 * pieces);  // (a plane's tail is skipped)
-    const long long nblk = runs * ((planes + group - 1) / group);
-    if (nblk > 2147483647ll || batch > 65535) return fail(DFM_ERR_UNSUPPORTED, "store probe: grid too large%s");
-    hipLaunchKernelGGL(store_probe_kernel, dim3((unsigned)nblk, batch), dim3(256), 0, (hipStream_t)stream,
-                       (uint4 *)out, plane_vec, runs, planes, pieces, group);
-    HIP_TRY(hipGetLastError());
-    return DFM_OK;
-}
-
-// the shader clock this part sustains with every CU busy: cycles (s_memtime) and 100 MHz reference
-// ticks (s_memrealtime) across `iterations` dependent FMAs per lane, written by workgroup 0
-__global__ __launch_bounds__(256) void clock_probe_kernel(unsigned long long *out, int iterations, float seed)
-{
-    const unsigned long long c0 = __builtin_readcyclecounter(), r0 = __builtin_amdgcn_s_memrealtime();
-    float x0 = seed + threadIdx.x, x1 = seed * 2.0f, x2 = seed * 3.0f, x3 = seed * 4.0f;
-    for (int i = 0; i < iterations; ++i) {
-        x0 = __builtin_fmaf(x0, 0.999f, 0.5f);
-        x1 = __builtin_fmaf(x1, 0.998f, 0.25f);
-        x2 = __builtin_fmaf(x2, 0.997f, 0.125f);
-        x3 = __builtin_fmaf(x3, 0.996f, 0.0625f);
-    }
-    const unsigned long long c1 = __builtin_readcyclecounter(), r1 = __builtin_amdgcn_s_memrealtime();
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        out[0] = c1 - c0;
-        out[1] = r1 - r0;
-    }
-    if (x0 + x1 + x2 + x3 == 12345.678f) out[2] = 1;  // keeps the loop
-}
-
-DFM_API int dfm_clock_probe(void *out3, int32_t iterations, void *stream)
-{
-    if (!out3 || iterations <= 0 || ((uintptr_t)out3 & 7)) return fail(DFM_ERR_INVALID_ARG, "clock probe: 3 x u64 device buffer%s");
-    hipLaunchKernelGGL(clock_probe_kernel, dim3(256 * 8), dim3(256), 0, (hipStream_t)stream, (unsigned long long *)out3,
-                       iterations, 1.0f);
-    HIP_TRY(hipGetLastError());
-    return DFM_OK;
-}
-
 DFM_API void dfm_plane_sweep_reset_tuning(void)
 {
     std::lock_guard<std::mutex> lk(g_tune_mu);
     g_tuned.clear();
 }
-
-DFM_API int dfm_plane_sweep_bwd(const dfm_sweep_desc *desc, const void *grad_out,
-                                const float *depths, const float *cam2img,
-                                const float *cam2img_inv, const float *cur2prev, float *grad_cur,
-                                float *grad_prev, void *stream)
-{
-    return dfm_plane_sweep_bwd_opts(desc, grad_out, depths, cam2img, cam2img_inv, cur2prev, grad_cur,
-                                    grad_prev, stream, nullptr);
-}
-
-}  // extern "C"
-namespace {
-int sweep_bwd_impl(const dfm_sweep_desc *desc, const void *grad_out, const float *depths, const float *cam2img,
-                   const float *cam2img_inv, const float *cur2prev, float *grad_cur, float *grad_prev, void *stream,
-                   const dfm_sweep_opts *opts, bool grad_cl);
-
-// (n, P, C) pixel-major -> (n, C, P) planar: 64 pixels x 8 16-byte channel pieces per workgroup through an
-// LDS tile; 16-byte loads along the channels of a pixel, 16-byte stores along the pixels of a channel.
-// C and P are whole 16-byte runs (checked by the caller).  grid = (ceil(P / 64), ceil(C / (8 * VEC)), n)
-template <typename T>
-__global__ __launch_bounds__(256) void unpack_pixel_major_kernel(const T *__restrict__ src, T *__restrict__ dst,
-                                                                 int C, long long P)
-{
-    constexpr int VEC = 16 / sizeof(T);   // elements per 16-byte piece
-    constexpr int TC = 8 * VEC;           // channels per tile
-    constexpr int PITCH = 64 + VEC;       // tile row: 64 pixels (+ one piece: rows stay 16-byte aligned)
-    __shared__ __attribute__((aligned(16))) T tile[TC * PITCH];
-    const long long p0 = (long long)blockIdx.x * 64;
-    const int c0 = blockIdx.y * TC;
-    const size_t n = blockIdx.z;
-    const T *s = src + n * (size_t)P * C;
-    T *d = dst + n * (size_t)C * P;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int q = threadIdx.x + 256 * k;          // piece: pixel q / 8, channel piece q % 8
-        const int p = q >> 3, cp = q & 7;
-        if (p0 + p < P && c0 + cp * VEC < C) {
-            const uint4 v = *(const uint4 *)(s + (size_t)(p0 + p) * C + c0 + cp * VEC);
-            T e[VEC];
-            __builtin_memcpy(e, &v, 16);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) tile[(cp * VEC + j) * PITCH + p] = e[j];
-        }
-    }
-    __syncthreads();
-    constexpr int PPR = 64 / VEC;  // 16-byte pieces per tile row
-#pragma unroll
-    for (int k = 0; k < (TC * PPR) / 256; ++k) {
-        const int q = threadIdx.x + 256 * k;
-        const int c = q / PPR, pp = (q % PPR) * VEC;
-        if (c0 + c < C && p0 + pp < P)
-            *(uint4 *)(d + (size_t)(c0 + c) * P + p0 + pp) = *(const uint4 *)(tile + c * PITCH + pp);
-    }
-}
-}
-extern "C" {
-DFM_API int dfm_plane_sweep_bwd_opts(const dfm_sweep_desc *desc, const void *grad_out,
-                                     const float *depths, const float *cam2img,
-                                     const float *cam2img_inv, const float *cur2prev,
-                                     float *grad_cur, float *grad_prev, void *stream,
-                                     const dfm_sweep_opts *opts)
-{
-    return sweep_bwd_impl(desc, grad_out, depths, cam2img, cam2img_inv, cur2prev, grad_cur, grad_prev, stream, opts,
-                          false);
-}
-
-DFM_API int dfm_plane_sweep_bwd_channels_last(const dfm_sweep_desc *desc, const void *grad_out,
-                                              const float *depths, const float *cam2img,
-                                              const float *cam2img_inv, const float *cur2prev,
-                                              float *grad_cur, float *grad_prev, void *workspace,
-                                              size_t workspace_bytes, void *stream)
-{
-    int rc = check_desc(desc);
-    if (rc != DFM_OK) return rc;
-    if (!grad_out) return fail(DFM_ERR_INVALID_ARG, "NULL device pointer%s");
-    const size_t esz = desc->dtype == DFM_BF16 ? 2 : 4;
-    const long long P = (long long)desc->num_depths * desc->h_out * desc->w_out;
-    const int C2 = 2 * desc->channels, vec = (int)(16 / esz);
-    const size_t vol = (size_t)desc->batch * C2 * P * esz;
-    if (workspace && workspace_bytes >= vol && C2 % vec == 0 && P % vec == 0 && !((uintptr_t)grad_out & 15) &&
-        !((uintptr_t)workspace & 15) && desc->batch <= 65535) {
-        // (B, P, 2C) -> (B, 2C, P) through an LDS tile at copy speed, then the backward on the reference
-        // layout: its lanes are consecutive lattice points, which the planar layout serves with one
-        // coalesced load per (plane, channel); read in place, a wave's 2-byte loads land 4C bytes apart
-        // and every channel pass re-fetches the lines (config K: 2.2 ms instead of 1.2 ms)
-        const dim3 grid((unsigned)((P + 63) / 64), (unsigned)((C2 + 8 * vec - 1) / (8 * vec)), desc->batch);
-        if (desc->dtype == DFM_BF16)
-            hipLaunchKernelGGL(unpack_pixel_major_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream,
-                               (const bf16_t *)grad_out, (bf16_t *)workspace, C2, P);
-        else
-            hipLaunchKernelGGL(unpack_pixel_major_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream,
-                               (const float *)grad_out, (float *)workspace, C2, P);
-        HIP_TRY(hipGetLastError());
-        return sweep_bwd_impl(desc, workspace, depths, cam2img, cam2img_inv, cur2prev, grad_cur, grad_prev, stream,
-                              nullptr, false);
-    }
-    return sweep_bwd_impl(desc, grad_out, depths, cam2img, cam2img_inv, cur2prev, grad_cur, grad_prev, stream,
-                          nullptr, true);
-}
-}  // extern "C"
-namespace {
-int sweep_bwd_impl(const dfm_sweep_desc *desc, const void *grad_out, const float *depths, const float *cam2img,
-                   const float *cam2img_inv, const float *cur2prev, float *grad_cur, float *grad_prev, void *stream,
-                   const dfm_sweep_opts *opts, bool grad_cl)
-{
-    const bool force_scatter = opts && opts->kernel == 1;
-    // 8: the tile kernel for the prev map only (the caller has the cur map from dfm_plane_sweep_bwd_cur_nhwc)
-    const bool skip_cur = opts && opts->kernel == 8;
-    int rc = check_desc(desc);
-    if (rc != DFM_OK) return rc;
-    if (!grad_out || !depths || !cam2img || !cam2img_inv || !cur2prev || !grad_cur || !grad_prev)
-        return fail(DFM_ERR_INVALID_ARG, "NULL device pointer%s");
-    const SweepGeom g = make_geom(desc);
-    hipStream_t st = (hipStream_t)stream;
-    // dense sweeps whose feature rows fit the LDS: accumulate there (see sweep_bwd_tile_kernel).
-    // One 1024-lane workgroup per CU: the LDS holds the footprint table of the chunk
-    // (planes x 256 points x 12 B) and the slab of 64-bit accumulators (CW channels x rows x W).
-    int planes = std::max(1, std::min(BWD_MAXP, (g.D + 3) / 4));
-    int cw_max = 4;
-#ifdef DFM_DEBUG_HOOKS
-    if (const char *e = getenv("DFM_BWD_PLANES")) planes = std::max(1, std::min(BWD_MAXP, atoi(e)));
-    if (const char *e = getenv("DFM_BWD_CW")) cw_max = atoi(e);
-#endif
-    const int table_bytes = planes * BWD_PTS * 12;
-    const int budget = 160 * 1024 - 1024 - table_bytes;  // 1 KiB for the static LDS
-    // channels per pass: as many (of 4) as leave >= 4 rows in the budget
-    auto pick_cw = [&](int cw) {
-        while (cw > 2 && (long long)budget / ((long long)cw * desc->w_in * 8) < 4) cw >>= 1;
-        return cw;
-    };
-    const int cw_cur = pick_cw(cw_max), cw_prev = cw_cur;
-    int row_cap = 8;
-#ifdef DFM_DEBUG_HOOKS
-    if (const char *e = getenv("DFM_BWD_ROWCAP")) row_cap = atoi(e);
-#endif
-    int rows_cur = (int)std::min<long long>(std::min(desc->h_in, row_cap),
-                                            (long long)budget / ((long long)cw_cur * desc->w_in * 8));
-#ifdef DFM_DEBUG_HOOKS
-    if (const char *e = getenv("DFM_BWD_ROWS")) rows_cur = std::min(rows_cur, std::max(4, atoi(e)));
-#endif
-    const int rows_prev = rows_cur;
-    const long long hw = (long long)g.h_out * g.w_out;
-    if (!force_scatter && rows_cur >= 4 && desc->h_in < 4096 && desc->w_in < 8192) {
-        BwdGrid tg;
-        tg.batch = desc->batch;
-        tg.band_pts = BWD_PTS;
-        tg.row_tiles = desc->cost_sample_factor < 1.5f ? 0 : (g.w_out + tg.band_pts - 1) / tg.band_pts;
-        tg.bands = tg.row_tiles ? g.h_out * tg.row_tiles : (int)((hw + tg.band_pts - 1) / tg.band_pts);
-        tg.planes = planes;
-        tg.ablate = 0;
-        tg.grad_cl = grad_cl ? 1 : 0;
-#ifdef DFM_DEBUG_HOOKS
-        {
-            const char *ab = getenv("DFM_BWD_ABLATE");
-            tg.ablate = ab ? atoi(ab) : 0;
-        }
-#endif
-        tg.dchunks = (g.D + tg.planes - 1) / tg.planes;
-        const long long nb = (long long)tg.bands * tg.dchunks * desc->batch;
-        if (nb > 2147483647ll) return fail(DFM_ERR_UNSUPPORTED, "too many lattice points%s");
-        const SweepFast fast = make_fast(desc);
-        // dense bf16 sweeps: the matrix-product backward (plane_sweep_bwd_mfma.hip) takes the cur map and
-        // the prev map's planes up to a zoom of SWEEP_BWD_ZOOM_FOUR map pixels per lattice point; this
-        // kernel keeps the (nearest) planes beyond that (opts->kernel: 5 = never, 6 = whenever it applies
-        // [the default])
-        tg.split = 0;
-        const bool mfma = !(opts && (opts->kernel == 5 || skip_cur)) && !grad_cl && sweep_bwd_mfma_supported(desc, grad_out);
-        if (mfma) {
-            tg.split = 1;
-            rc = sweep_bwd_mfma_launch(desc, 0, grad_out, depths, cam2img, cam2img_inv, cur2prev, grad_cur, grad_prev,
-                                       stream);
-            if (rc != DFM_OK) return rc;
-            rc = sweep_bwd_mfma_launch(desc, 1, grad_out, depths, cam2img, cam2img_inv, cur2prev, grad_cur, grad_prev,
-                                       stream);
-            if (rc != DFM_OK) return rc;
-        }
-#define DFM_BWD_LAUNCH(T, CW, HALF, ROWS)                                                            \
-    do {                                                                                             \
-        tg.rows = (ROWS);                                                                            \
-        const int lds_bytes = (CW) * (ROWS) * desc->w_in * 8 + table_bytes;                          \
-        rc = ensure_dynamic_lds((const void *)sweep_bwd_tile_kernel<T, CW, HALF>, lds_bytes);        \
-        if (rc != DFM_OK) return rc;                                                                 \
-        hipLaunchKernelGGL((sweep_bwd_tile_kernel<T, CW, HALF>), dim3((unsigned)nb),                 \
-                           dim3(BWD_PTS * bwd_groups(HALF)),                                         \
-                           lds_bytes, st, g, fast, tg, (const T *)grad_out, depths, cam2img,         \
-                           cam2img_inv, cur2prev, grad_cur, grad_prev);                              \
-    } while (0)
-#define DFM_BWD_HALF(T, HALF, CWV, ROWS)                                                             \
-    do {                                                                                             \
-        if ((CWV) == 8) DFM_BWD_LAUNCH(T, 8, HALF, ROWS);                                            \
-        else if ((CWV) == 4) DFM_BWD_LAUNCH(T, 4, HALF, ROWS);                                       \
-        else DFM_BWD_LAUNCH(T, 2, HALF, ROWS);                                                       \
-    } while (0)
-        if (desc->dtype == DFM_F32) {
-            if (!skip_cur) DFM_BWD_HALF(float, 0, cw_cur, rows_cur);
-            DFM_BWD_HALF(float, 1, cw_prev, rows_prev);
-        } else {
-            if (!mfma && !skip_cur) DFM_BWD_HALF(bf16_t, 0, cw_cur, rows_cur);
-            DFM_BWD_HALF(bf16_t, 1, cw_prev, rows_prev);
-        }
-#undef DFM_BWD_HALF
-#undef DFM_BWD_LAUNCH
-        HIP_TRY(hipGetLastError());
-        g_last_bwd_kernel.store(mfma ? 6 : 5);
-        return DFM_OK;
-    }
-    if (grad_cl)  // the scatter kernel reads the reference layout only: the caller converts and calls dfm_plane_sweep_bwd
-        return fail(DFM_ERR_UNSUPPORTED, "channels-last gradient: the LDS-tile backward does not take this shape%s");
-    if (skip_cur) return fail(DFM_ERR_UNSUPPORTED, "prev-only backward: the LDS-tile kernel does not take this shape%s");
-    const long long nb = (g.N + 255) / 256;
-    if (nb > 2147483647ll) return fail(DFM_ERR_UNSUPPORTED, "too many lattice points%s");
-    dim3 grid((unsigned)nb, desc->batch);
-    if (desc->dtype == DFM_F32)
-        hipLaunchKernelGGL(sweep_bwd_kernel<float>, grid, dim3(256), 0, st, g,
-                           (const float *)grad_out, depths, cam2img, cam2img_inv, cur2prev,
-                           grad_cur, grad_prev);
-    else
-        hipLaunchKernelGGL(sweep_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, g,
-                           (const bf16_t *)grad_out, depths, cam2img, cam2img_inv, cur2prev,
-                           grad_cur, grad_prev);
-    HIP_TRY(hipGetLastError());
-    g_last_bwd_kernel.store(1);
-    return DFM_OK;
-}
-}  // namespace
-extern "C" {
 
 DFM_API int dfm_plane_sweep_grid(const dfm_sweep_desc *desc, int32_t b, const float *depths,
                                  const float *cam2img, const float *cam2img_inv,
@@ -2575,12 +1732,12 @@ DFM_API int dfm_plane_sweep_grid(const dfm_sweep_desc *desc, int32_t b, const fl
 {
     int rc = check_desc(desc);
     if (rc != DFM_OK) return rc;
-    if (b < 0 || b >= desc->batch) return fail(DFM_ERR_INVALID_ARG, "sample index out of range%s");
+    if (b < 0 || b >= desc->batch) return set_error(DFM_ERR_INVALID_ARG, "sample index out of range");
     if (!depths || !cam2img || !cam2img_inv || !cur2prev || !cur_grid || !prev_grid)
-        return fail(DFM_ERR_INVALID_ARG, "NULL device pointer%s");
+        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     const SweepGeom g = make_geom(desc);
     const long long nb = (g.N + 255) / 256;
-    if (nb > 2147483647ll) return fail(DFM_ERR_UNSUPPORTED, "too many lattice points%s");
+    if (nb > 2147483647ll) return set_error(DFM_ERR_UNSUPPORTED, "too many lattice points");
     hipLaunchKernelGGL(sweep_grid_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, g,
                        b, depths, cam2img, cam2img_inv, cur2prev, cur_grid, prev_grid);
     HIP_TRY(hipGetLastError());

@@ -40,7 +40,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "dfm_common.h"
+#include "plane_sweep_common.h"
 
 using namespace dfm;
 

@@ -3,7 +3,7 @@
 // Replaces (for cost_sample_factor == 1, bf16 gradients) the scatter-add of
 //   grad_cur/prev[c, y, x] += weight(d, h, w; y, x) * grad_out[c, d, h, w]
 // i.e. autograd of F.grid_sample in build_dfm_cost (reference dfm_backbone.py:296-311), which
-// sweep_bwd_tile_kernel (plane_sweep.hip) does with four 64-bit fixed-point LDS atomics per value.
+// sweep_bwd_tile_kernel (plane_sweep_bwd.hip) does with four 64-bit fixed-point LDS atomics per value.
 //
 // The bilinear weights of the 32 lattice points of one lattice-row segment at one depth plane form a
 // banded 32 x (pixels) matrix with two non-zeros per point and image row; it does not depend on the
@@ -39,7 +39,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "dfm_common.h"
+#include "plane_sweep_common.h"
 
 namespace dfm {
 namespace {

@@ -24,7 +24,7 @@
 //            map share them), blend in ATen's order, one 16-byte nt store -- a wave
 //            stores 1 KiB contiguous per point.
 // Bound: HBM write.  No LDS staging: the taps of a point are whole cache lines.
-#include "dfm_common.h"
+#include "plane_sweep_common.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(256, DFM_WALK_WAVES) void sweep_cltw_kernel(
 // Backward of strided fp32 sweeps, CUR map (autograd of F.grid_sample at dfm_backbone.py:296-311 with
 // cost_sample_factor >= 2: config K).
 //
-// The LDS-atomic tile kernel (plane_sweep.hip) stages whole feature rows per depth chunk: for a
+// The LDS-atomic tile kernel (plane_sweep_bwd.hip) stages whole feature rows per depth chunk: for a
 // strided sweep 15 of 16 staged pixels receive nothing, and config K takes 10.7 ms, half of it for the
 // cur map -- whose sample position does not move with depth at all: it is the lattice pixel up to
 // rounding noise, so over ALL planes a point's taps stay inside one 3x3 pixel window.  A WAVE owns 16

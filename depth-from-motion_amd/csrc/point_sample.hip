@@ -16,7 +16,7 @@
 //               of Cp*sizeof(T) bytes, not C/CB pieces a plane apart
 //   out       : volume (C*F', Nx, Ny, Nz) or flat (N, C)
 // Bound: HBM write of the volume + L2-resident gathers; no reuse to stage.
-#include "dfm_common.h"
+#include "plane_sweep_common.h"
 
 // The lifted volume (hundreds of MB, written once, read by a later kernel) leaves the CU with
 // non-temporal 16-byte stores: the batched channels-last kernel writes whole contiguous KiBs per

@@ -29,7 +29,7 @@
 // no cross-wave reduction.  Two barriers per plane: X(d) "slab d-1 is free" after everyone's kd = 0
 // taps, Y(d) "slab d+1 is complete" before anyone's kd = 2 taps; the M waves fill slab d+2 between X(d)
 // and Y(d+1).
-#include "dfm_common.h"
+#include "plane_sweep_common.h"
 
 #include <stdlib.h>
 
@@ -134,7 +134,7 @@ struct Taps {
     int swz;
 };
 
-// sweep_point_map (dfm_common.h) for a lane that samples either map: the same fp32 operations in the
+// sweep_point_map (plane_sweep_common.h) for a lane that samples either map: the same fp32 operations in the
 // same order -- the prev map's extra cur2prev transform is computed by every lane and selected -- and no
 // branch in the FAST specialisation (no flip, img_scale_factor 1, feat_sample_factor a power of two: the
 // reference's un-augmented test-time geometry), so that two chunks' footprint arithmetic is ONE basic

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""How many tiles of the N* workload the LDS tile kernel hands to the direct-tap pass."""
+"""How many tiles of the N* workload the serial LDS tile kernel queues for its second-chance pass, by LDS budget.
+(The pipelined body -- the default -- takes its second chances in place and queues nothing.)"""
 import ctypes, importlib, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,11 +15,11 @@ desc = sweep._make_desc(cur, w['D'], w['fsf'], w['csf'], (375, 1242), False, (0,
 P, Pinv, T = sweep.camera_matrices(torch.from_numpy(np.stack([bench.KITTI_P2] * B)), torch.from_numpy(bench.poses(B, 2)), B, dev)
 out = torch.empty((B, 2 * w['C'], w['D'], desc.h_out, desc.w_out), dtype=torch.bfloat16, device=dev)
 for kib in (36, 52, 64, 78, 100, 150):
-    pkg._capi.check(lib.dfm_plane_sweep_tune(256, kib, 1 << 20, 2))
-    sweep.plane_sweep_forward(desc, cur, prev, depths, P, Pinv, T, out=out)
+    with sweep.launch_options(kernel=2, lanes=256, lds_kib=kib, planes=2, pipeline=1):
+        sweep.plane_sweep_forward(desc, cur, prev, depths, P, Pinv, T, out=out)
     torch.cuda.synchronize()
     nbytes = lib.dfm_plane_sweep_workspace_bytes(ctypes.byref(desc))
     ws = sweep._Workspace.get(dev, nbytes)
     blocked = ((B * 32 * w['H'] * w['W'] * 16 + 255) // 256) * 256
     count = int(ws[2 * blocked: 2 * blocked + 4].view(torch.int32).item())
-    print(f'lds {kib:3d} KiB: {count} tiles queued for the direct-tap pass')
+    print(f'lds {kib:3d} KiB: {count} tiles queued for the second-chance pass')
