@@ -116,6 +116,9 @@ EXPORTS = (
     'dfm_batch_norm_apply_gathered_channels_last',
     'dfm_batch_norm_bwd_reduce_channels_last',
     'dfm_batch_norm_bwd_apply_channels_last',
+    'dfm_imitation_loss_workspace_bytes',
+    'dfm_imitation_loss_fwd',
+    'dfm_imitation_loss_bwd',
 )
 
 
@@ -227,6 +230,16 @@ class DepthLossDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('batch', 'num_depths', 'h', 'w', 'target', 'focal')] + \
         [(n, ctypes.c_float) for n in ('min_depth', 'max_depth', 'interval', 'sigma', 'alpha', 'gamma')] + \
         [('dtype', ctypes.c_int32)]
+
+
+class ImitationDesc(ctypes.Structure):
+    """struct dfm_imitation_desc"""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        'batch', 'channels', 'nz', 'ny', 'nx', 'num_boxes', 'points_batch', 'mode', 'pred_dtype', 'target_dtype',
+        'pred_channels_last', 'target_channels_last', 'center_len', 'scale_len')]
+
+
+IMI_INBOX, IMI_FULL = 0, 1
 
 
 class Conv3dDesc(ctypes.Structure):
@@ -490,6 +503,13 @@ def lib():
     h.dfm_batch_norm_bwd_apply_channels_last.restype = ctypes.c_int
     h.dfm_batch_norm_bwd_apply_channels_last.argtypes = [i32, i64, i32, i32, vp, vp, vp, fp, fp, fp, fp, fp, fp, vp,
                                                          vp, vp, sz, vp]
+    ip = ctypes.POINTER(ImitationDesc)
+    h.dfm_imitation_loss_workspace_bytes.restype = sz
+    h.dfm_imitation_loss_workspace_bytes.argtypes = [ip]
+    h.dfm_imitation_loss_fwd.restype = ctypes.c_int
+    h.dfm_imitation_loss_fwd.argtypes = [ip, vp, vp, fp, fp, fp, fp, fp, vp, vp, vp, sz, vp]
+    h.dfm_imitation_loss_bwd.restype = ctypes.c_int
+    h.dfm_imitation_loss_bwd.argtypes = [ip, vp, vp, vp, fp, fp, fp, vp, vp]
     _lib = h
     return h
 

@@ -249,6 +249,22 @@ class MultiViewDfMMixin:
         return out
 
 
+class DfMImitationMixin:
+    """``get_imitation_reg_layer_loss`` of ``DfM`` (dfm.py:468-540) on the HIP path, for a subclass of the
+    reference detector (``class FastDfM(DfMImitationMixin, DfM)``): one fused launch instead of
+    ``points_in_boxes_part`` and the gather / normalise / reduce passes.  The host class provides
+    ``bbox_head_3d.anchors``, ``norm_imitation`` and ``normalizer_clamp_value`` as the reference does; the
+    second return value is the info dict of ``imitation_reg_layer_loss`` (no ``.item()`` logging values)."""
+
+    def get_imitation_reg_layer_loss(self, features_preds, features_targets, imitation_cfg, gt_bboxes_3d):
+        from .imitation import imitation_reg_layer_loss
+        points = self.bbox_head_3d.anchors[0][:, :, :, 0, 0, :3]
+        return imitation_reg_layer_loss(
+            features_preds, features_targets, imitation_cfg, gt_bboxes_3d, points,
+            norm_layer=self.norm_imitation[imitation_cfg['stereo_feature_layer']],
+            normalizer_clamp_value=self.normalizer_clamp_value, training=self.training)
+
+
 class MultiViewVoxelPath(MultiViewDfMMixin, nn.Module):
     """The multi-view path of ``MultiViewDfM`` from its config ``model`` dict (neck_3d,
     voxel_size, anchor_generator.ranges, temporal_aggregate, optionally depth_head + depth_cfg), without

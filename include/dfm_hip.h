@@ -951,6 +951,52 @@ DFM_API int dfm_depth_loss_fused_bwd(const dfm_depth_loss_desc *desc, const void
                                      const float *grad_pixel_loss, float *grad_cost, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* LiDAR-teacher feature-imitation loss                                     */
+/* DfM.get_imitation_reg_layer_loss (detectors/dfm.py:468-540) with         */
+/* NormalizeLayer / WeightedL2WithSigmaLoss (detectors/imitation_utils.py)  */
+/* ---------------------------------------------------------------------- */
+typedef enum dfm_imitation_mode {
+    DFM_IMI_INBOX = 0, /* BEV cells whose point lies in a ground-truth box (z ignored) */
+    DFM_IMI_FULL = 1   /* every BEV cell                                               */
+} dfm_imitation_mode;
+
+typedef struct dfm_imitation_desc {
+    int32_t batch, channels;
+    int32_t nz, ny, nx;    /* nz = 1 for a 2-D pair (B, C, ny, nx)                         */
+    int32_t num_boxes;     /* T of boxes (batch, T, 7); may be 0; ignored with DFM_IMI_FULL */
+    int32_t points_batch;  /* leading size of points: 1 (shared by all samples) or batch    */
+    int32_t mode;          /* dfm_imitation_mode                                            */
+    int32_t pred_dtype, target_dtype;                 /* DFM_F32 / DFM_BF16, independently   */
+    int32_t pred_channels_last, target_channels_last; /* 0: NC[D]HW, 1: N[D]HWC              */
+    int32_t center_len, scale_len; /* 0 (the layer has none), 1 or channels                 */
+} dfm_imitation_desc;
+
+/* positives = in-box cells (every z of them) whose target is non-zero in some channel (a NaN is non-zero).
+ * Over the positives, t' = (t - center) / scale (each step only with a non-zero length):
+ *   stats[0] = their count, stats[1] = S = sum_c 0.5 (pred - t')^2 (0 where t' is NaN),
+ *   stats[2 .. 2+C) = sum t, stats[2+C .. 2+2C) = sum |t| per channel         (fp64, 2 + 2 channels values)
+ * and mask (batch, nz, ny, nx) = 1 at positives, 0 elsewhere.  Cells outside every box cost no read of pred
+ * or target.  Fixed-order reduction (partial rows in the workspace, merged in index order by the last
+ * workgroup to finish; no floating-point atomics): the same bits run after run.
+ * The box test is mmcv 1.6's points_in_boxes_part with point z and box z forced to 0 (dfm.py:485-486); a
+ * zero-size box contains nothing (padding).  points (points_batch, ny, nx, 3), boxes (batch, T, 7) =
+ * x, y, z, x_size, y_size, z_size, yaw, both FP32.
+ * Stats-only mode, new_center != NULL (channels values): stats[0 .. C) = sum |t - new_center| over the same
+ * positives; pred and mask are not touched and may be NULL.
+ * channels <= 1024 (DFM_ERR_UNSUPPORTED above). */
+DFM_API size_t dfm_imitation_loss_workspace_bytes(const dfm_imitation_desc *desc);
+DFM_API int dfm_imitation_loss_fwd(const dfm_imitation_desc *desc, const void *pred, const void *target,
+                                   const float *points, const float *boxes, const float *center,
+                                   const float *scale, const float *new_center, unsigned char *mask,
+                                   double *stats, void *workspace, size_t workspace_bytes, void *stream);
+/* grad_pred = coef[0] * (pred - t') at the positives of `mask` (as written by dfm_imitation_loss_fwd), 0
+ * elsewhere and where t' is NaN; written densely in pred's layout and dtype.  coef is one FP32 in device
+ * memory (no host sync).  target gets no gradient (the teacher is frozen). */
+DFM_API int dfm_imitation_loss_bwd(const dfm_imitation_desc *desc, const void *pred, const void *target,
+                                   const unsigned char *mask, const float *center, const float *scale,
+                                   const float *coef, void *grad_pred, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* fused GroupNorm (+ReLU) of the aggregation stacks                        */
 /* mmcv ConvModule(conv -> GN -> ReLU) at dfm_backbone.py:50-66,118-128,     */
 /* feature_transformation.py:55-62; convbn_3d at utils/conv_modules.py:27-43 */
