@@ -23,6 +23,7 @@ from .conv3d import MfmaPathError, fallback_policy, set_fallback_policy, set_fp3
 from .depth_head import depth_distribution_loss  # noqa: F401
 from .imitation import (ImitationLoss, NormalizeLayer, imitation_reg_layer_loss,  # noqa: F401
                         reduce_imitation_statistics)
+from .box_nms import box3d_multiclass_nms, box_iou_rotated, nms_bev, nms_normal_bev  # noqa: F401
 from .data_geometry import (fold_ref_frame_matrices, select_ref_frames, stage_geometry,  # noqa: F401
                             video_cur2prevs)
 from .point_sample import (mv_feature_transformation, point_sample, voxel_centers,  # noqa: F401
@@ -35,4 +36,5 @@ __all__ = ['build_dfm_cost', 'plane_sweep_grid', 'point_sample', 'mv_feature_tra
            'fallback_policy', 'MfmaPathError', 'select_ref_frames', 'fold_ref_frame_matrices', 'video_cur2prevs',
            'stage_geometry', 'depth_distribution_loss',
            'depth_head_statistics', 'LazyDepthDistribution', 'ImitationLoss', 'NormalizeLayer',
-           'imitation_reg_layer_loss', 'reduce_imitation_statistics', 'DfMImitationMixin']
+           'imitation_reg_layer_loss', 'reduce_imitation_statistics', 'DfMImitationMixin', 'box3d_multiclass_nms',
+           'nms_bev', 'nms_normal_bev', 'box_iou_rotated']

@@ -119,6 +119,10 @@ EXPORTS = (
     'dfm_imitation_loss_workspace_bytes',
     'dfm_imitation_loss_fwd',
     'dfm_imitation_loss_bwd',
+    'dfm_box_nms_workspace_bytes',
+    'dfm_box_nms_rotated',
+    'dfm_box_nms_aligned',
+    'dfm_box_iou_rotated',
 )
 
 
@@ -263,6 +267,7 @@ DL_LINEAR, DL_HARD, DL_GAUSSIAN, DL_LAPLACIAN = 0, 1, 2, 3
 
 
 DFM_ERR_UNSUPPORTED = -2  # include/dfm_hip.h
+BOX_NMS_MAX_N = 16384  # DFM_BOX_NMS_MAX_N
 
 
 class DfmHipError(RuntimeError):
@@ -510,6 +515,14 @@ def lib():
     h.dfm_imitation_loss_fwd.argtypes = [ip, vp, vp, fp, fp, fp, fp, fp, vp, vp, vp, sz, vp]
     h.dfm_imitation_loss_bwd.restype = ctypes.c_int
     h.dfm_imitation_loss_bwd.argtypes = [ip, vp, vp, vp, fp, fp, fp, vp, vp]
+    h.dfm_box_nms_workspace_bytes.restype = sz
+    h.dfm_box_nms_workspace_bytes.argtypes = [i32, i32]
+    h.dfm_box_nms_rotated.restype = ctypes.c_int
+    h.dfm_box_nms_rotated.argtypes = [fp, i32, i32, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp]
+    h.dfm_box_nms_aligned.restype = ctypes.c_int
+    h.dfm_box_nms_aligned.argtypes = [fp, i32, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp]
+    h.dfm_box_iou_rotated.restype = ctypes.c_int
+    h.dfm_box_iou_rotated.argtypes = [fp, i32, fp, i32, i32, fp, vp]
     _lib = h
     return h
 

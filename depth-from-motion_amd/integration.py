@@ -22,12 +22,14 @@ Three ways to use this package from there, all routed to the HIP kernels:
 """
 import importlib
 import inspect
+import sys
 
 import numpy as np
 import torch
 from torch import nn
 
 from . import registry
+from .box_nms import box3d_multiclass_nms, nms_bev, nms_normal_bev
 from .geometry import prepare_coordinates_3d, prepare_depth
 from .conv3d import MfmaConv3dTo1
 from .graphs import GraphedCallable
@@ -328,6 +330,26 @@ _FUNCTION_PATCHES = (
 )
 
 
+# the BEV NMS functions (mmcv CUDA ops behind them in the reference) and every module that holds them by
+# name.  Rebound only where the module is ALREADY imported: importing box3d_nms.py for this would drag in
+# numba and mmcv.ops.
+_NMS_MODULES = ('mmdet3d.core.post_processing.box3d_nms', 'mmdet3d.core.post_processing', 'mmdet3d.core',
+                'mmdet3d.models.dense_heads.anchor3d_head')
+_NMS_FUNCTIONS = (('box3d_multiclass_nms', box3d_multiclass_nms), ('nms_bev', nms_bev),
+                  ('nms_normal_bev', nms_normal_bev))
+
+
+def _patch_nms_functions():
+    done = []
+    for mod_name in _NMS_MODULES:
+        mod = sys.modules.get(mod_name)
+        for attr, fn in _NMS_FUNCTIONS:
+            if mod is not None and hasattr(mod, attr):
+                setattr(mod, attr, fn)
+                done.append(f'{mod_name}.{attr}')
+    return done
+
+
 def patch_reference(precision=None, strict=False):
     """Route a real mmdet3d (the reference fork) to the HIP path.  Call once after
     ``import mmdet3d`` and before building the model from ``configs/dfm/*``.  Returns a report
@@ -350,6 +372,7 @@ def patch_reference(precision=None, strict=False):
         if hasattr(mod, attr):
             setattr(mod, attr, fn)
             report['functions'].append(f'{mod_name}.{attr}')
+    report['functions'] += _patch_nms_functions()
     try:
         det = importlib.import_module('mmdet3d.models.detectors.multiview_dfm')
         det.MultiViewDfM.feature_transformation = MultiViewDfMMixin.feature_transformation

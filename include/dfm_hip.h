@@ -997,6 +997,51 @@ DFM_API int dfm_imitation_loss_bwd(const dfm_imitation_desc *desc, const void *p
                                    const float *coef, void *grad_pred, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* BEV non-maximum suppression and rotated-box IoU                          */
+/* box3d_multiclass_nms / nms_bev / nms_normal_bev                          */
+/* (core/post_processing/box3d_nms.py), whose nms_rotated / nms are CUDA    */
+/* ops of mmcv; box_iou_rotated is what BaseInstance3DBoxes.overlaps needs  */
+/* ---------------------------------------------------------------------- */
+/* Most candidates per class.  The suppression mask costs n * ceil(n / 64) * 8 bytes per class (32 MiB at the
+ * cap); n * classes combinations whose mask would exceed 1 GiB are refused as well. */
+#define DFM_BOX_NMS_MAX_N 16384
+
+/* Semantics.  A rotated box is (cx, cy, w, h, angle), angle in radians.  IoU = intersection area /
+ * (area1 + area2 - intersection), exact (convex clipping, FP32, both boxes taken relative to the midpoint of
+ * their centres first), and 0 when either area is below 1e-14.  Mirroring both boxes leaves the IoU unchanged,
+ * so it does not matter whether the angle is counted clockwise or counter-clockwise.
+ * The candidates of class c are order[c][0 .. counts[c]) -- indices into `boxes`, in the order they are to be
+ * visited (descending score).  A candidate is dropped when an earlier candidate that was kept has an IoU with
+ * it STRICTLY greater than iou_threshold.  keep[c][0 .. kept_counts[c]) receives the kept candidates' entries
+ * of `order` -- indices into the caller's `boxes` -- in the same order.
+ *
+ * boxes       : (num_boxes, 5) FP32                                              [device]
+ *               rotated: (cx, cy, w, h, angle), or with xyxyr != 0 (x1, y1, x2, y2, angle), converted as
+ *               nms_bev does: ((x1+x2)/2, (y1+y2)/2, x2-x1, y2-y1, angle);
+ *               aligned: (x1, y1, x2, y2, ignored), IoU of the axis-aligned boxes without a +1 offset
+ * order       : (classes, n) int64; counts: (classes) int32, clamped to [0, n]   [device]
+ *               (read on the device: launching needs no host value; an entry of `order` outside
+ *               [0, num_boxes) is a zero-size box)
+ * keep        : (classes, n) int64; kept_counts: (classes) int32                 [device, written]
+ * workspace   : dfm_box_nms_workspace_bytes(n, classes) = classes * n * ceil(n / 64) * 8 bytes, caller-owned
+ * Two launches on `stream` (mask: one wave per 64 x 64 block on or above the diagonal; reduce: one wave per
+ * class), no atomics, no host synchronisation.  n = 0 returns DFM_OK and launches and writes nothing.
+ * DFM_ERR_UNSUPPORTED for n > DFM_BOX_NMS_MAX_N or a mask above 1 GiB (workspace_bytes returns 0 there). */
+DFM_API size_t dfm_box_nms_workspace_bytes(int32_t n, int32_t classes);
+DFM_API int dfm_box_nms_rotated(const float *boxes, int32_t num_boxes, int32_t xyxyr, const int64_t *order,
+                                const int32_t *counts, int32_t n, int32_t classes, float iou_threshold,
+                                int64_t *keep, int32_t *kept_counts, void *workspace, size_t workspace_bytes,
+                                void *stream);
+DFM_API int dfm_box_nms_aligned(const float *boxes, int32_t num_boxes, const int64_t *order,
+                                const int32_t *counts, int32_t n, int32_t classes, float iou_threshold,
+                                int64_t *keep, int32_t *kept_counts, void *workspace, size_t workspace_bytes,
+                                void *stream);
+/* out (n, m) FP32 = IoU(boxes1[i], boxes2[j]), or out (n) = IoU(boxes1[i], boxes2[i]) when aligned (then
+ * m == n); boxes (., 5) FP32 (cx, cy, w, h, angle).  n == 0 or m == 0 returns DFM_OK and launches nothing. */
+DFM_API int dfm_box_iou_rotated(const float *boxes1, int32_t n, const float *boxes2, int32_t m, int32_t aligned,
+                                float *out, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* fused GroupNorm (+ReLU) of the aggregation stacks                        */
 /* mmcv ConvModule(conv -> GN -> ReLU) at dfm_backbone.py:50-66,118-128,     */
 /* feature_transformation.py:55-62; convbn_3d at utils/conv_modules.py:27-43 */
