@@ -24,6 +24,8 @@ from .depth_head import depth_distribution_loss  # noqa: F401
 from .imitation import (ImitationLoss, NormalizeLayer, imitation_reg_layer_loss,  # noqa: F401
                         reduce_imitation_statistics)
 from .box_nms import box3d_multiclass_nms, box_iou_rotated, nms_bev, nms_normal_bev  # noqa: F401
+from .iou3d_loss import (IOU3DLoss, diff_iou_rotated_2d, diff_iou_rotated_3d, iou3d_loss,  # noqa: F401
+                         iou3d_loss_from_deltas)
 from .data_geometry import (fold_ref_frame_matrices, select_ref_frames, stage_geometry,  # noqa: F401
                             video_cur2prevs)
 from .point_sample import (mv_feature_transformation, point_sample, voxel_centers,  # noqa: F401
@@ -37,4 +39,5 @@ __all__ = ['build_dfm_cost', 'plane_sweep_grid', 'point_sample', 'mv_feature_tra
            'stage_geometry', 'depth_distribution_loss',
            'depth_head_statistics', 'LazyDepthDistribution', 'ImitationLoss', 'NormalizeLayer',
            'imitation_reg_layer_loss', 'reduce_imitation_statistics', 'DfMImitationMixin', 'box3d_multiclass_nms',
-           'nms_bev', 'nms_normal_bev', 'box_iou_rotated']
+           'nms_bev', 'nms_normal_bev', 'box_iou_rotated', 'diff_iou_rotated_3d', 'diff_iou_rotated_2d', 'iou3d_loss',
+           'IOU3DLoss', 'iou3d_loss_from_deltas']

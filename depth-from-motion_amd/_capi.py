@@ -123,6 +123,8 @@ EXPORTS = (
     'dfm_box_nms_rotated',
     'dfm_box_nms_aligned',
     'dfm_box_iou_rotated',
+    'dfm_diff_iou_rotated',
+    'dfm_iou3d_loss_from_deltas',
 )
 
 
@@ -523,6 +525,10 @@ def lib():
     h.dfm_box_nms_aligned.argtypes = [fp, i32, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp]
     h.dfm_box_iou_rotated.restype = ctypes.c_int
     h.dfm_box_iou_rotated.argtypes = [fp, i32, fp, i32, i32, fp, vp]
+    h.dfm_diff_iou_rotated.restype = ctypes.c_int
+    h.dfm_diff_iou_rotated.argtypes = [fp, fp, i32, i32, fp, fp, fp, vp]
+    h.dfm_iou3d_loss_from_deltas.restype = ctypes.c_int
+    h.dfm_iou3d_loss_from_deltas.argtypes = [fp, fp, fp, vp, i32, i32, i32, fp, fp, vp]
     _lib = h
     return h
 

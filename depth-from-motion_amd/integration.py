@@ -10,9 +10,10 @@ Three ways to use this package from there, all routed to the HIP kernels:
 
 1. ``patch_reference()`` -- inside a real mmdet3d installation: re-registers the module
    classes (``DfMBackbone``, ``FrustumToVoxel``, ``DepthHead``, ``OutdoorImVoxelNeck``,
-   ``DfMNeck``, ``BEVHourglass``, ``SPPUNetNeck``) under the same ``type`` names (force=True) so
-   ``configs/dfm/*`` build them unchanged, rebinds the functions the reference modules call
-   (``build_dfm_cost``, ``point_sample``, ``voxel_sample``) and replaces
+   ``DfMNeck``, ``BEVHourglass``, ``SPPUNetNeck``, and the loss ``IOU3DLoss``) under the same
+   ``type`` names (force=True) so ``configs/dfm/*`` build them unchanged, rebinds the functions
+   the reference modules call (``build_dfm_cost``, ``point_sample``, ``voxel_sample``, the NMS
+   functions and ``diff_iou_rotated_3d`` where their modules are already imported) and replaces
    ``MultiViewDfM.feature_transformation`` by ``MultiViewDfMMixin.feature_transformation``.
 2. ``DfMStereoPath`` -- the KITTI student's path (neck -> backbone_stereo -> depth_head ->
    feature_transformation -> height compression -> backbone_3d) built from the ``model`` dict of
@@ -30,6 +31,7 @@ from torch import nn
 
 from . import registry
 from .box_nms import box3d_multiclass_nms, nms_bev, nms_normal_bev
+from .iou3d_loss import diff_iou_rotated_3d
 from .geometry import prepare_coordinates_3d, prepare_depth
 from .conv3d import MfmaConv3dTo1
 from .graphs import GraphedCallable
@@ -350,6 +352,21 @@ def _patch_nms_functions():
     return done
 
 
+# the reference's iou3d_loss.py holds mmcv's differentiable IoU by name (``from mmcv.ops import diff_iou_rotated_3d``);
+# its IOU3DLoss class itself is replaced through the registry.  Rebound only where already imported, as above.
+_IOU_MODULES = ('mmdet3d.models.losses.iou3d_loss',)
+
+
+def _patch_iou_functions():
+    done = []
+    for mod_name in _IOU_MODULES:
+        mod = sys.modules.get(mod_name)
+        if mod is not None and hasattr(mod, 'diff_iou_rotated_3d'):
+            mod.diff_iou_rotated_3d = diff_iou_rotated_3d
+            done.append(f'{mod_name}.diff_iou_rotated_3d')
+    return done
+
+
 def patch_reference(precision=None, strict=False):
     """Route a real mmdet3d (the reference fork) to the HIP path.  Call once after
     ``import mmdet3d`` and before building the model from ``configs/dfm/*``.  Returns a report
@@ -373,6 +390,7 @@ def patch_reference(precision=None, strict=False):
             setattr(mod, attr, fn)
             report['functions'].append(f'{mod_name}.{attr}')
     report['functions'] += _patch_nms_functions()
+    report['functions'] += _patch_iou_functions()
     try:
         det = importlib.import_module('mmdet3d.models.detectors.multiview_dfm')
         det.MultiViewDfM.feature_transformation = MultiViewDfMMixin.feature_transformation
@@ -489,7 +507,7 @@ def enable_fast_path(model, dtype=torch.bfloat16, strict=True, boundary_casts=Tr
     Idempotent.  ``state_dict`` keys are unchanged; ``load_state_dict`` of an fp32 checkpoint casts
     on copy as usual."""
     from . import modules as _m
-    path_classes = tuple(registry.registered().values())
+    path_classes = registry.path_classes()
     names = dict((m, n) for n, m in model.named_modules())
     roots, inside = [], set()
     for n, m in model.named_modules():

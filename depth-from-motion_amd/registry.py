@@ -5,12 +5,17 @@ reference's config dicts without mmcv installed.  When mmdet3d IS importable,
 registry (force=True) and `configs/dfm/*` resolve to these implementations."""
 
 _MODULES = {}
+_NOT_ON_THE_PATH = set()
 
 
-def register_module(cls=None, *, name=None):
+def register_module(cls=None, *, name=None, on_path=True):
+    """``on_path=False``: a class that is built by ``type`` name but is no stage of the feature path (a loss):
+    ``enable_fast_path`` does not treat it as a path root."""
 
     def _do(c):
         _MODULES[name or c.__name__] = c
+        if not on_path:
+            _NOT_ON_THE_PATH.add(name or c.__name__)
         return c
 
     return _do(cls) if cls is not None else _do
@@ -35,6 +40,11 @@ build_backbone = build_neck = build_head = build
 
 def registered():
     return dict(_MODULES)
+
+
+def path_classes():
+    """the registered classes that are stages of the feature path (``enable_fast_path``'s path roots)"""
+    return tuple(c for n, c in _MODULES.items() if n not in _NOT_ON_THE_PATH)
 
 
 def register_into_mmdet3d():

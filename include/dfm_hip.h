@@ -1042,6 +1042,52 @@ DFM_API int dfm_box_iou_rotated(const float *boxes1, int32_t n, const float *box
                                 float *out, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* differentiable IoU of rotated boxes and the head's IoU loss              */
+/* IOU3DLoss (models/losses/iou3d_loss.py), whose diff_iou_rotated_3d is a  */
+/* CUDA op of mmcv; called from LIGAAnchor3DHead.loss_single                */
+/* (dense_heads/liga_anchor3d_head.py:210-224)                              */
+/* ---------------------------------------------------------------------- */
+/* Semantics.  A 3-D box is (x, y, z, dx, dy, dz, yaw):
+ *   BEV rectangle : centre (x, y), size (dx, dy), turned counter-clockwise by yaw (radians) -- the convention
+ *                   of dfm_box_iou_rotated;
+ *   z interval    : [z - dz / 2, z + dz / 2]   (z is the CENTRE of the interval);
+ *   IoU3D         = I Z / (V1 + V2 - I Z),  I = the exact area of the two rectangles' intersection,
+ *                   Z = max(0, min(zmax) - max(zmin)),  V = dx dy dz.
+ * The gradient is that of this function -- defined almost everywhere -- with respect to all 14 inputs.  Where a
+ * top or bottom face of the two boxes coincides, box 1's face counts as the one that bounds Z.  IoU is 0 and
+ * every gradient component is 0 when a BEV area or a volume is below 1e-14, and when I or Z is 0 (disjoint or
+ * touching boxes; also any comparison a NaN input fails): mmcv's NaN from 0 / 0 is not reproduced.  On the
+ * measure-zero set where the gradient is undefined (coincident edges) the value is exact and the gradient finite.
+ * The 2-D box (x, y, w, h, angle), width 5, is the 3-D box with z = 0, dz = 1: IoU = I / (A1 + A2 - I).
+ *
+ * FP32 arithmetic, both boxes taken relative to the midpoint of their centres first.  One launch on `stream`, one
+ * lane per pair, no atomics, no workspace: bit-identical run to run.
+ *
+ * boxes1, boxes2 : (n, width) FP32, width 7 or 5                                  [device]
+ * iou            : (n) FP32                                                        [device, written]
+ * grad1, grad2   : (n, width) FP32 = d iou[p] / d boxes1[p], d iou[p] / d boxes2[p], or both NULL: values only
+ * n == 0 returns DFM_OK and launches nothing. */
+DFM_API int dfm_diff_iou_rotated(const float *boxes1, const float *boxes2, int32_t n, int32_t width, float *iou,
+                                 float *grad1, float *grad2, void *stream);
+/* The IoU term of loss_single in one launch: for p in [0, num_pos), i = pos_inds[p],
+ *   pred   = decode(anchors[i], bbox_pred[i]),  target = decode(anchors[i], bbox_targets[i])
+ *   target = where(isnan(target), pred, target)          (iou3d_loss.py:24; per decoded component)
+ *   loss[p] = 1 - IoU3D(pred, target)
+ *   jac[p]  = d loss[p] / d bbox_pred[i][0 .. 7), the chain rule through the decode included; the gradient of a
+ *             replaced target component reaches bbox_pred through both arguments
+ * decode = DeltaXYZWLHRBBoxCoder.decode (core/bbox/coders/delta_xyzwhlr_bbox_coder.py:58-91), the same FP32
+ * operations: with the anchor (xa, ya, za, wa, la, ha, ra) and the deltas (xt, yt, zt, wt, lt, ht, rt),
+ *   x = xt sqrt(la^2 + wa^2) + xa,  y likewise,  dx = exp(wt) wa,  dy = exp(lt) la,  dz = exp(ht) ha,
+ *   z = zt ha + (za + ha / 2) - dz / 2,  yaw = rt + ra.
+ * anchors, bbox_pred, bbox_targets : (num_rows, code_size) FP32, code_size >= 7, columns beyond 7 ignored
+ * pos_inds : (num_pos) int64 rows, read on the device; an index outside [0, num_rows) gives loss 1, jac 0
+ * loss     : (num_pos) FP32; jac: (num_pos, 7) FP32 or NULL (values only)         [device, written]
+ * num_pos == 0 returns DFM_OK and launches nothing. */
+DFM_API int dfm_iou3d_loss_from_deltas(const float *anchors, const float *bbox_pred, const float *bbox_targets,
+                                       const int64_t *pos_inds, int32_t num_rows, int32_t code_size,
+                                       int32_t num_pos, float *loss, float *jac, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* fused GroupNorm (+ReLU) of the aggregation stacks                        */
 /* mmcv ConvModule(conv -> GN -> ReLU) at dfm_backbone.py:50-66,118-128,     */
 /* feature_transformation.py:55-62; convbn_3d at utils/conv_modules.py:27-43 */
