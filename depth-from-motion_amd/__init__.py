@@ -26,6 +26,8 @@ from .imitation import (ImitationLoss, NormalizeLayer, imitation_reg_layer_loss,
 from .box_nms import box3d_multiclass_nms, box_iou_rotated, nms_bev, nms_normal_bev  # noqa: F401
 from .iou3d_loss import (IOU3DLoss, diff_iou_rotated_2d, diff_iou_rotated_3d, iou3d_loss,  # noqa: F401
                          iou3d_loss_from_deltas)
+from .anchor_target import (BboxOverlapsNearest3D, HipAnchorTrainMixin, anchor_target_3d,  # noqa: F401
+                            bbox_overlaps_nearest_3d)
 from .data_geometry import (fold_ref_frame_matrices, select_ref_frames, stage_geometry,  # noqa: F401
                             video_cur2prevs)
 from .point_sample import (mv_feature_transformation, point_sample, voxel_centers,  # noqa: F401
@@ -40,4 +42,5 @@ __all__ = ['build_dfm_cost', 'plane_sweep_grid', 'point_sample', 'mv_feature_tra
            'depth_head_statistics', 'LazyDepthDistribution', 'ImitationLoss', 'NormalizeLayer',
            'imitation_reg_layer_loss', 'reduce_imitation_statistics', 'DfMImitationMixin', 'box3d_multiclass_nms',
            'nms_bev', 'nms_normal_bev', 'box_iou_rotated', 'diff_iou_rotated_3d', 'diff_iou_rotated_2d', 'iou3d_loss',
-           'IOU3DLoss', 'iou3d_loss_from_deltas']
+           'IOU3DLoss', 'iou3d_loss_from_deltas', 'bbox_overlaps_nearest_3d', 'BboxOverlapsNearest3D',
+           'anchor_target_3d', 'HipAnchorTrainMixin']

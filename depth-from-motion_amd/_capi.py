@@ -125,6 +125,9 @@ EXPORTS = (
     'dfm_box_iou_rotated',
     'dfm_diff_iou_rotated',
     'dfm_iou3d_loss_from_deltas',
+    'dfm_nearest_bev_overlaps',
+    'dfm_anchor_target_workspace_bytes',
+    'dfm_anchor_target_3d',
 )
 
 
@@ -266,6 +269,20 @@ class Conv3dWgradDesc(ctypes.Structure):
 
 
 DL_LINEAR, DL_HARD, DL_GAUSSIAN, DL_LAPLACIAN = 0, 1, 2, 3
+
+OVERLAP_IOU, OVERLAP_IOF = 0, 1  # DFM_OVERLAP_*
+ANCHOR_TARGET_MAX_SLOTS, ANCHOR_TARGET_MAX_BATCH = 8, 64  # DFM_ANCHOR_TARGET_MAX_*
+SAMPLER_PSEUDO = 0  # DFM_SAMPLER_PSEUDO
+
+
+class AnchorTargetDesc(ctypes.Structure):
+    """struct dfm_anchor_target_desc"""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        'num_locations', 'num_slots', 'num_rotations', 'box_width', 'batch', 'num_classes', 'has_labels',
+        'assign_per_class', 'match_low_quality', 'gt_max_assign_all', 'sampler', 'neg_iou_thr_is_range',
+        'num_ignore_boxes')] + [('ignore_iof_thr', ctypes.c_float)] + \
+        [(n, ctypes.c_float * ANCHOR_TARGET_MAX_SLOTS) for n in ('pos_iou_thr', 'neg_iou_thr', 'min_pos_iou')] + \
+        [(n, ctypes.c_float) for n in ('dir_offset', 'dir_limit_offset', 'pos_weight')]
 
 
 DFM_ERR_UNSUPPORTED = -2  # include/dfm_hip.h
@@ -529,6 +546,13 @@ def lib():
     h.dfm_diff_iou_rotated.argtypes = [fp, fp, i32, i32, fp, fp, fp, vp]
     h.dfm_iou3d_loss_from_deltas.restype = ctypes.c_int
     h.dfm_iou3d_loss_from_deltas.argtypes = [fp, fp, fp, vp, i32, i32, i32, fp, fp, vp]
+    h.dfm_nearest_bev_overlaps.restype = ctypes.c_int
+    h.dfm_nearest_bev_overlaps.argtypes = [fp, i32, fp, i32, i32, i32, i32, fp, vp]
+    h.dfm_anchor_target_workspace_bytes.restype = sz
+    h.dfm_anchor_target_workspace_bytes.argtypes = [i32, i32]
+    h.dfm_anchor_target_3d.restype = ctypes.c_int
+    h.dfm_anchor_target_3d.argtypes = [ctypes.POINTER(AnchorTargetDesc), fp, fp, vp, ctypes.POINTER(ctypes.c_int32),
+                                       vp, fp, fp, fp, vp, fp, vp, vp, sz, vp]
     _lib = h
     return h
 

@@ -13,8 +13,10 @@ Three ways to use this package from there, all routed to the HIP kernels:
    ``DfMNeck``, ``BEVHourglass``, ``SPPUNetNeck``, and the loss ``IOU3DLoss``) under the same
    ``type`` names (force=True) so ``configs/dfm/*`` build them unchanged, rebinds the functions
    the reference modules call (``build_dfm_cost``, ``point_sample``, ``voxel_sample``, the NMS
-   functions and ``diff_iou_rotated_3d`` where their modules are already imported) and replaces
-   ``MultiViewDfM.feature_transformation`` by ``MultiViewDfMMixin.feature_transformation``.
+   functions, ``diff_iou_rotated_3d`` and ``bbox_overlaps_nearest_3d`` where their modules are already
+   imported), replaces ``MultiViewDfM.feature_transformation`` by
+   ``MultiViewDfMMixin.feature_transformation`` and, where ``train_mixins`` is already imported,
+   ``AnchorTrainMixin.anchor_target_3d`` by ``HipAnchorTrainMixin.anchor_target_3d``.
 2. ``DfMStereoPath`` -- the KITTI student's path (neck -> backbone_stereo -> depth_head ->
    feature_transformation -> height compression -> backbone_3d) built from the ``model`` dict of
    ``configs/dfm/dfm_r34_1x8_kitti-3d-3class.py`` with the detector's attribute injection;
@@ -32,6 +34,8 @@ from torch import nn
 from . import registry
 from .box_nms import box3d_multiclass_nms, nms_bev, nms_normal_bev
 from .iou3d_loss import diff_iou_rotated_3d
+from . import anchor_target as _anchor_target
+from .anchor_target import HipAnchorTrainMixin, bbox_overlaps_nearest_3d
 from .geometry import prepare_coordinates_3d, prepare_depth
 from .conv3d import MfmaConv3dTo1
 from .graphs import GraphedCallable
@@ -367,6 +371,38 @@ def _patch_iou_functions():
     return done
 
 
+# the anchor head's target assignment: the reference's train_mixins.py defines AnchorTrainMixin, whose
+# anchor_target_3d is rebound (the replaced method is kept for the fallback policy), and the modules that hold
+# bbox_overlaps_nearest_3d by name.  Only where already imported, as above: these files import mmdet.
+_TRAIN_MIXIN_MODULES = ('mmdet3d.models.dense_heads.train_mixins',)
+_OVERLAP_MODULES = ('mmdet3d.core.bbox.iou_calculators.iou3d_calculator', 'mmdet3d.core.bbox.iou_calculators',
+                    'mmdet3d.core.bbox', 'mmdet3d.core')
+
+
+def _patch_anchor_target():
+    """-> (functions, methods) rebound"""
+    functions, methods = [], []
+    for mod_name in _OVERLAP_MODULES:
+        mod = sys.modules.get(mod_name)
+        if mod is not None and hasattr(mod, 'bbox_overlaps_nearest_3d'):
+            mod.bbox_overlaps_nearest_3d = bbox_overlaps_nearest_3d
+            functions.append(f'{mod_name}.bbox_overlaps_nearest_3d')
+    for mod_name in _TRAIN_MIXIN_MODULES:
+        mod = sys.modules.get(mod_name)
+        cls = getattr(mod, 'AnchorTrainMixin', None) if mod is not None else None
+        if cls is not None and hasattr(cls, 'anchor_target_3d'):
+            current = vars(cls).get('anchor_target_3d')
+            ours = vars(HipAnchorTrainMixin)['anchor_target_3d']
+            if current is not ours:
+                _anchor_target._REFERENCE['anchor_target_3d'] = current
+                cls.anchor_target_3d = ours
+                # the two helpers the rebound method calls on ``self``
+                cls._anchor_target_unsupported = vars(HipAnchorTrainMixin)['_anchor_target_unsupported']
+                cls._anchor_target_fallback = vars(HipAnchorTrainMixin)['_anchor_target_fallback']
+            methods.append('AnchorTrainMixin.anchor_target_3d')
+    return functions, methods
+
+
 def patch_reference(precision=None, strict=False):
     """Route a real mmdet3d (the reference fork) to the HIP path.  Call once after
     ``import mmdet3d`` and before building the model from ``configs/dfm/*``.  Returns a report
@@ -391,6 +427,9 @@ def patch_reference(precision=None, strict=False):
             report['functions'].append(f'{mod_name}.{attr}')
     report['functions'] += _patch_nms_functions()
     report['functions'] += _patch_iou_functions()
+    functions, methods = _patch_anchor_target()
+    report['functions'] += functions
+    report['methods'] += methods
     try:
         det = importlib.import_module('mmdet3d.models.detectors.multiview_dfm')
         det.MultiViewDfM.feature_transformation = MultiViewDfMMixin.feature_transformation
@@ -571,4 +610,4 @@ def enable_fast_path(model, dtype=torch.bfloat16, strict=True, boundary_casts=Tr
 
 
 __all__ = ['inject_detector_attributes', 'DfMStereoPath', 'MultiViewDfMMixin', 'MultiViewVoxelPath',
-           'patch_reference', 'enable_fast_path', 'voxel_centers']
+           'patch_reference', 'enable_fast_path', 'voxel_centers', 'HipAnchorTrainMixin']

@@ -1088,6 +1088,91 @@ DFM_API int dfm_iou3d_loss_from_deltas(const float *anchors, const float *bbox_p
                                        int32_t num_pos, float *loss, float *jac, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* nearest-BEV overlaps and the 3-D anchor head's training targets         */
+/* bbox_overlaps_nearest_3d (core/bbox/iou_calculators/iou3d_calculator.py  */
+/* :99-145) and AnchorTrainMixin.anchor_target_3d (models/dense_heads/      */
+/* train_mixins.py:12-350) over mmdet's MaxIoUAssigner and PseudoSampler    */
+/* ---------------------------------------------------------------------- */
+/* Semantics, all FP32, one IEEE rounding per operation listed.
+ *   Nearest BEV box of (x, y, z, dx, dy, dz, yaw, ...) (base_box3d.py:144-162):
+ *       r = |yaw - floor(yaw / pi + 0.5) * pi|;  (w, h) = (dy, dx) when r > pi / 4, else (dx, dy);
+ *       box = (x - w/2, y - h/2, x + w/2, y + h/2), area = (x2 - x1) * (y2 - y1).
+ *   Overlap (mmdet's bbox_overlaps):
+ *       overlap = max(0, min x2 - max x1) * max(0, min y2 - max y1);
+ *       DFM_OVERLAP_IOU: union = max(a1 + a2 - overlap, 1e-6);  DFM_OVERLAP_IOF: union = max(a1, 1e-6);
+ *       result = overlap / union.
+ * out (n, m) = overlap(boxes1[i], boxes2[j]), or out (n) = overlap(boxes1[i], boxes2[i]) when aligned (then
+ * m == n); boxes (., width) FP32, width >= 7, columns beyond 7 ignored.  One launch, one lane per element.
+ * n == 0 or m == 0 returns DFM_OK and launches nothing. */
+#define DFM_OVERLAP_IOU 0
+#define DFM_OVERLAP_IOF 1
+DFM_API int dfm_nearest_bev_overlaps(const float *boxes1, int32_t n, const float *boxes2, int32_t m, int32_t width,
+                                     int32_t mode, int32_t aligned, float *out, void *stream);
+
+#define DFM_ANCHOR_TARGET_MAX_SLOTS 8   /* class slots (one assigner each) */
+#define DFM_ANCHOR_TARGET_MAX_BATCH 64  /* images per call */
+#define DFM_SAMPLER_PSEUDO 0
+typedef struct dfm_anchor_target_desc {
+    int32_t num_locations;        /* H * W of the BEV map */
+    int32_t num_slots;            /* C: class slots of the anchor generator = number of assigners */
+    int32_t num_rotations;        /* R */
+    int32_t box_width;            /* 7; anything else: DFM_ERR_UNSUPPORTED */
+    int32_t batch;                /* images, <= DFM_ANCHOR_TARGET_MAX_BATCH */
+    int32_t num_classes;          /* the label of an anchor that is not positive */
+    int32_t has_labels;           /* 0: no gt_labels (positives get 1, the others 0; train_mixins.py:287-305) */
+    int32_t assign_per_class;     /* slot c sees only the GT boxes labelled c */
+    int32_t match_low_quality;    /* MaxIoUAssigner.match_low_quality */
+    int32_t gt_max_assign_all;    /* MaxIoUAssigner.gt_max_assign_all */
+    int32_t sampler;              /* DFM_SAMPLER_PSEUDO; anything else: DFM_ERR_UNSUPPORTED */
+    int32_t neg_iou_thr_is_range; /* a (low, high) tuple neg_iou_thr: DFM_ERR_UNSUPPORTED */
+    int32_t num_ignore_boxes;     /* with ignore_iof_thr > 0: DFM_ERR_UNSUPPORTED */
+    float ignore_iof_thr;
+    float pos_iou_thr[DFM_ANCHOR_TARGET_MAX_SLOTS];
+    float neg_iou_thr[DFM_ANCHOR_TARGET_MAX_SLOTS];
+    float min_pos_iou[DFM_ANCHOR_TARGET_MAX_SLOTS];
+    float dir_offset, dir_limit_offset;
+    float pos_weight;             /* train_cfg.pos_weight: <= 0 means 1 */
+} dfm_anchor_target_desc;
+/* anchor_target_3d for a batch and all class slots, in two launches, the overlap matrix never in memory.
+ *
+ * anchors   : (num_locations, num_slots, num_rotations, 7) FP32, what Anchor3DRangeGenerator(reshape_out=False)
+ *             lays out; one set, shared by every image.  Anchor a = (location * C + slot) * R + rotation.
+ * gt_boxes  : (total_gt, 7) FP32, the images' GT boxes packed;  gt_labels: (total_gt) int64       [device]
+ * gt_offsets: (batch + 1) int32 on the HOST, gt_offsets[0] = 0: image b owns rows [gt_offsets[b], gt_offsets[b+1])
+ * Per image and slot c the GT list is the image's boxes (those labelled c when assign_per_class), in their order;
+ * ov(a, i) is the DFM_OVERLAP_IOU overlap above.  MaxIoUAssigner.assign_wrt_overlaps, then PseudoSampler:
+ *   assigned = -1;  max = the largest ov(a, .), argmax its LOWEST index (torch's CPU rule for ties);
+ *   0 <= max < neg_iou_thr[c]  -> assigned = 0;      max >= pos_iou_thr[c] -> assigned = argmax + 1;
+ *   match_low_quality: for GT i in increasing order with gt_max[i] = max over the slot's anchors of ov(., i)
+ *   >= min_pos_iou[c]:  assigned = i + 1 for every anchor with ov(a, i) == gt_max[i] (gt_max_assign_all), else
+ *   for the first such anchor only.  A later GT overrides an earlier one and the argmax.
+ *   A slot whose GT list is empty: every anchor negative (train_mixins.py:279-285).
+ * Outputs, image-major, each image in the reference's final order (location, slot, rotation), EVERY element written
+ * exactly once (allocate with empty):
+ *   positive (assigned > 0): bbox_targets = DeltaXYZWLHRBBoxCoder.encode(anchor, gt) = ((xg - xa) / d, (yg - ya) /
+ *     d, ((zg + hg/2) - (za + ha/2)) / ha, log(wg / wa), log(lg / la), log(hg / ha), rg - ra), d = sqrt(la^2 + wa^2);
+ *     dir_targets = clamp(floor(limit_period(rt + ra - dir_offset, dir_limit_offset, 2 pi) / pi), 0, 1);
+ *     labels = the GT's label; label_weights = pos_weight if > 0 else 1; bbox_weights = dir_weights = 1.
+ *   negative (assigned == 0): labels = num_classes, label_weights = 1, the rest 0.
+ *   ignored  (assigned < 0) : labels = num_classes, everything else 0.
+ * labels, dir_targets : (batch, A) int64;  label_weights, dir_weights : (batch, A) FP32;
+ * bbox_targets, bbox_weights : (batch, A, 7) FP32;  A = num_locations * num_slots * num_rotations  [device, written]
+ * counts    : (batch, 2) int32 = positives, negatives per image (set by the first launch, added to by the second)
+ * workspace : dfm_anchor_target_workspace_bytes(num_slots, total_gt) = num_slots * total_gt * 8 bytes, 16-byte
+ *             aligned, caller-owned; zeroed on `stream` by the call (may be NULL when total_gt == 0).
+ * Launch 1: per (slot, GT) the maximum overlap and the first anchor that has it, by one 64-bit atomic max per GT
+ * and wave of (overlap bits << 32 | ~anchor).  Launch 2: assignment, encoding, output.  Integer atomics only: the
+ * same bits run after run.  No host synchronisation.  batch == 0 or A == 0 returns DFM_OK and launches nothing.
+ * DFM_ERR_UNSUPPORTED, before any HIP call: box_width != 7, a sampler other than DFM_SAMPLER_PSEUDO,
+ * neg_iou_thr_is_range, ignore_iof_thr > 0 with num_ignore_boxes > 0, num_slots or batch above their maxima. */
+DFM_API size_t dfm_anchor_target_workspace_bytes(int32_t num_slots, int32_t total_gt);
+DFM_API int dfm_anchor_target_3d(const dfm_anchor_target_desc *desc, const float *anchors, const float *gt_boxes,
+                                 const int64_t *gt_labels, const int32_t *gt_offsets, int64_t *labels,
+                                 float *label_weights, float *bbox_targets, float *bbox_weights,
+                                 int64_t *dir_targets, float *dir_weights, int32_t *counts, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* fused GroupNorm (+ReLU) of the aggregation stacks                        */
 /* mmcv ConvModule(conv -> GN -> ReLU) at dfm_backbone.py:50-66,118-128,     */
 /* feature_transformation.py:55-62; convbn_3d at utils/conv_modules.py:27-43 */
