@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _capi
+from .derived import Derived, derived, note_derived_build
 from .plane_sweep import _Workspace, _ptr, _stream_ptr
 
 _WDT = {torch.float32: _capi.DFM_F32, torch.bfloat16: _capi.DFM_BF16}
@@ -187,52 +188,10 @@ class _MfmaConvFn(torch.autograd.Function):
         return gx, gw, None, None
 
 
-# Per-module state DERIVED from parameters or from tensors the detector injects: packed weight fragments, folded
-# norms, device copies of host tensors (some entries hold weak references, which do not pickle).  None of it is part
-# of a module's identity: `torch.save(model)`, `pickle` and `copy.deepcopy` (EMA hooks, `mp.spawn` arguments) leave
-# it behind and the copy rebuilds it on its first forward.  Names initialised in __init__ go back to their initial
-# value, the rest is dropped.
-_DERIVED_RESET = {'_packs': None, '_pack_key': None, '_sweep_conv_pack': (None, None)}
-_DERIVED_DROP = frozenset((
-    '_split_packs', '_split_key', '_pack2d', '_pack2d_key', '_gate_pack', '_dev_cache', '_coords_ref', '_coords_key',
-    '_coords_dev', '_spp_params', '_spp_key', '_fold', '_fold_key'))
-
-# Derived state is built lazily by the FIRST call that needs it, with kernels on that call's HIP stream.  A module
-# that runs on two streams (DfMStereoPath: the same 2-D neck for the previous frame on a side stream and for the
-# current frame on the main stream) would let the second stream read packed weights the first has not finished
-# writing.  Every build site bumps this counter; a caller that forks streams compares it around the first call and
-# makes the other stream wait when anything was built (integration.DfMStereoPath.forward).
-_DERIVED_BUILDS = [0]
-
-
-def note_derived_build():
-    _DERIVED_BUILDS[0] += 1
-
-
-def derived_builds():
-    return _DERIVED_BUILDS[0]
-
-
-class DerivedStateMixin:
-    """first base of the path's modules: their pickled state carries parameters, buffers and configuration only"""
-
-    def __getstate__(self):
-        state = super().__getstate__()
-        state = {k: v for k, v in state.items() if k not in _DERIVED_DROP}
-        for k, v in _DERIVED_RESET.items():
-            if k in state:
-                state[k] = v
-        return state
-
-
-class MfmaConv3d(DerivedStateMixin, nn.Conv3d):
+class MfmaConv3d(nn.Conv3d):
     """nn.Conv3d(C_in in {32, 64, ...}, 32, 3, stride=1, padding=1, bias=False) whose bf16 / NDHWC
     forward is the hand-written MFMA kernel.  Packed weight fragments are cached and rebuilt when
-    the parameter changes (version counter)."""
-
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        self._packs, self._pack_key = None, None
+    the parameter changes (derived.Derived)."""
 
     def why_not(self, x):
         """None when the MFMA kernel takes ``x``, else the reason it does not"""
@@ -251,11 +210,8 @@ class MfmaConv3d(DerivedStateMixin, nn.Conv3d):
         return self.why_not(x) is None
 
     def _packed(self):
-        key = (self.weight._version, self.weight.data_ptr(), self.weight.device)
-        if self._pack_key != key:
-            self._packs = [pack_conv3d_weights(self.weight, 32 * i) for i in range(self.in_channels // 32)]
-            self._pack_key = key
-        return self._packs
+        return derived(self).get('packs', (self.weight,), lambda: [
+            pack_conv3d_weights(self.weight, 32 * i) for i in range(self.in_channels // 32)])
 
     def forward(self, x):
         why = self.why_not(x)
@@ -509,22 +465,6 @@ def channel_slice(x, lo, hi):
     return x[:, lo:hi]
 
 
-class _PackCache:
-    """packed weight fragments of a module's parameter, rebuilt when the parameter changes"""
-
-    def __init__(self):
-        self._pack, self._key = None, None
-
-    def __getstate__(self):  # a pickled / deep-copied module packs again on its first forward
-        return {'_pack': None, '_key': None}
-
-    def get(self, weight, make):
-        key = (weight._version, weight.data_ptr(), weight.device)
-        if self._key != key:
-            self._pack, self._key = make(), key
-        return self._pack
-
-
 def conv3d_to1_norm(y, partials, gamma, beta, eps, weight, relu=True, depth_chunk=0):
     """GroupNorm(32 groups of one channel)(+ReLU) applied ON LOAD inside the Conv3d(32 -> 1, 3, 1, 1) that consumes it
     (csrc/conv3d_to1n.hip; dfm_backbone.py:120-127, inference).  ``y``: (N, 32, D, H, W) bf16 channels_last_3d, the RAW
@@ -550,7 +490,7 @@ def conv3d_to1_norm(y, partials, gamma, beta, eps, weight, relu=True, depth_chun
     return out
 
 
-_IDENTITY_COEF = {}
+_identity_coef = Derived(capacity=64)
 
 
 def conv3d_to1(x, weight, depth_chunk=0):
@@ -563,14 +503,8 @@ def conv3d_to1(x, weight, depth_chunk=0):
     w = weight.detach().contiguous()
     if w.dtype not in _WDT:
         w = w.float()
-    key = (str(x.device), N)
-    coef = _IDENTITY_COEF.get(key)
-    if coef is None:
-        coef = torch.tensor([1.0, 0.0], dtype=torch.float32, device=x.device).repeat(N * 32).view(N, 32, 2).contiguous()
-        if len(_IDENTITY_COEF) > 64:
-            _IDENTITY_COEF.clear()
-        _IDENTITY_COEF[key] = coef
-        note_derived_build()
+    coef = _identity_coef.get((x.device, N), (), lambda: torch.tensor(
+        [1.0, 0.0], dtype=torch.float32, device=x.device).repeat(N * 32).view(N, 32, 2).contiguous())
     out = torch.empty((N, 1, D, H, W), dtype=torch.bfloat16, device=x.device)
     with torch.cuda.device(x.device):
         _capi.check(_capi.lib().dfm_conv3d_to1_norm_fwd(N, D, H, W, _ptr(x), _ptr(coef), _ptr(w), _WDT[w.dtype], 0, 0,
@@ -638,15 +572,11 @@ class _MfmaConvTo1Fn(torch.autograd.Function):
         return gx, gw, None
 
 
-class MfmaConv3dTo1(DerivedStateMixin, nn.Conv3d):
+class MfmaConv3dTo1(nn.Conv3d):
     """nn.Conv3d(32, 1, 3, 1, 1, bias=False): the prediction convolutions of DfMBackbone
     (dfm_backbone.py:120-127).  bf16 / NDHWC input: the 32 -> 32 MFMA kernel with a zero-padded
     weight, storing channel 0 only (MIOpen's untuned kernel for this shape takes 3.4 ms at config K,
     this one 0.12 ms)."""
-
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        self._cache = _PackCache()
 
     def why_not(self, x):
         if not x.is_cuda:
@@ -668,7 +598,7 @@ class MfmaConv3dTo1(DerivedStateMixin, nn.Conv3d):
             w = torch.zeros((32, 32, 3, 3, 3), dtype=torch.float32, device=self.weight.device)
             w[0] = self.weight.detach().float()[0]
             return pack_conv3d_weights(w)
-        return self._cache.get(self.weight, make)
+        return derived(self).get('pack', (self.weight,), make)
 
     def forward(self, x):
         why = self.why_not(x)
@@ -996,12 +926,9 @@ def _split_why_not(module, x, kind):
 
 def _split_packs(module, cin, cout, swap):
     """(hi, lo) fragment buffers of the module's fp32 weight, cached per weight version"""
-    key = (module.weight._version, module.weight.data_ptr(), str(module.weight.device), _FP32_MODE['mode'])
-    if module.__dict__.get('_split_key') != key:
-        module.__dict__['_split_packs'] = [pack_conv3d_g_weights(w, cin, cout, swap=swap)
-                                           for w in split_pieces(module.weight.detach().float())]
-        module.__dict__['_split_key'] = key
-    return module.__dict__['_split_packs']
+    return derived(module).get('split_packs', (module.weight,), lambda: [
+        pack_conv3d_g_weights(w, cin, cout, swap=swap) for w in split_pieces(module.weight.detach().float())],
+        (_FP32_MODE['mode'], swap))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1136,14 +1063,11 @@ class _Mfma2dMixin:
     """packs the 2-D weight once per version (inference: the weights do not change between calls)"""
 
     def _packed2d(self, cin, cout, swap):
-        key = (self.weight._version, self.weight.data_ptr(), str(self.weight.device))
-        if self.__dict__.get('_pack2d_key') != key:
-            self.__dict__['_pack2d'] = pack_conv2d_g_weights(self.weight, cin, cout, swap=swap)
-            self.__dict__['_pack2d_key'] = key
-        return self.__dict__['_pack2d']
+        return derived(self).get('pack2d', (self.weight,),
+                                 lambda: pack_conv2d_g_weights(self.weight, cin, cout, swap=swap))
 
 
-class MfmaConv2d(DerivedStateMixin, nn.Conv2d, _Mfma2dMixin):
+class MfmaConv2d(nn.Conv2d, _Mfma2dMixin):
     """nn.Conv2d (same parameters / state_dict keys).  kernel 3, padding 1, stride 1 | 2, dilation 1,
     groups 1, channels = 32 k, bf16 channels_last input under no_grad: the hand-written MFMA kernel
     (csrc/conv3d_g.hip with a (1, 3, 3) kernel); anything else: torch's convolution, the module's other
@@ -1216,14 +1140,12 @@ class MfmaConv2d(DerivedStateMixin, nn.Conv2d, _Mfma2dMixin):
         return None
 
     def _packed2d_padded(self):
-        key = (self.weight._version, self.weight.data_ptr(), str(self.weight.device))
-        if self.__dict__.get('_pack2d_key') != key:
+        def make():
             w = self.weight.detach()
             if self.in_channels < 32:
                 w = torch.cat([w, w.new_zeros(w.shape[0], 32 - self.in_channels, 3, 3)], 1)
-            self.__dict__['_pack2d'] = pack_conv2d_g_weights(w, self._cin_padded(), self.out_channels)
-            self.__dict__['_pack2d_key'] = key
-        return self.__dict__['_pack2d']
+            return pack_conv2d_g_weights(w, self._cin_padded(), self.out_channels)
+        return derived(self).get('pack2d_padded', (self.weight,), make)
 
     def forward_fused(self, x, scale=None, shift=None, residual=None, relu=False):
         if self.bias is not None:
@@ -1289,7 +1211,7 @@ class MfmaConv2d(DerivedStateMixin, nn.Conv2d, _Mfma2dMixin):
         return y if keep_cl else y.contiguous()
 
 
-class MfmaConvTranspose2d(DerivedStateMixin, nn.ConvTranspose2d, _Mfma2dMixin):
+class MfmaConvTranspose2d(nn.ConvTranspose2d, _Mfma2dMixin):
     """nn.ConvTranspose2d kernel 3, stride 2, padding 1, output_padding 1 (hourglass2d's up-convs,
     conv_modules.py:196-214) through the MFMA kernel under the conditions of ``MfmaConv2d``."""
 
@@ -1402,15 +1324,11 @@ class _ConvGFn(torch.autograd.Function):
         return gx, gw, None, None, None, None
 
 
-class MfmaConv3dG(DerivedStateMixin, nn.Conv3d):
+class MfmaConv3dG(nn.Conv3d):
     """nn.Conv3d(32 j, 32 k, 3, stride in {1, 2}, padding in {0, 1, 2}, bias=False) whose bf16 /
     NDHWC forward is the general MFMA kernel; any other input takes torch's convolution (MIOpen),
     the module's other documented path.  ``forward_fused`` folds a per-channel scale / shift (an
     eval-mode BatchNorm3d), a residual and the ReLU into the epilogue (inference)."""
-
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        self._cache = _PackCache()
 
     def why_not(self, x):
         if not x.is_cuda:
@@ -1437,7 +1355,7 @@ class MfmaConv3dG(DerivedStateMixin, nn.Conv3d):
         return self.why_not(x) is None
 
     def _packed(self):
-        return self._cache.get(self.weight, lambda: pack_conv3d_g_weights(
+        return derived(self).get('pack', (self.weight,), lambda: pack_conv3d_g_weights(
             self.weight, self.in_channels, self.out_channels))
 
     def forward(self, x):
@@ -1461,14 +1379,10 @@ class MfmaConv3dG(DerivedStateMixin, nn.Conv3d):
                         scale=scale, shift=shift, residual=residual)
 
 
-class MfmaConvTranspose3d(DerivedStateMixin, nn.ConvTranspose3d):
+class MfmaConvTranspose3d(nn.ConvTranspose3d):
     """nn.ConvTranspose3d(32 j, 32 k, 3, stride=2, padding=1, output_padding=1, bias=False) of the
     hourglass (conv_modules.py:101-117): evaluated per output parity class on the low-resolution
     input by the general MFMA kernel when the input is bf16 / NDHWC."""
-
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        self._cache = _PackCache()
 
     def why_not(self, x):
         if not x.is_cuda:
@@ -1489,7 +1403,7 @@ class MfmaConvTranspose3d(DerivedStateMixin, nn.ConvTranspose3d):
         return self.why_not(x) is None
 
     def _packed(self):
-        return self._cache.get(self.weight, lambda: pack_conv3d_g_weights(
+        return derived(self).get('pack', (self.weight,), lambda: pack_conv3d_g_weights(
             self.weight, self.in_channels, self.out_channels, swap=True))
 
     def forward(self, x, output_size=None):

@@ -4,12 +4,12 @@
 ``voxel_convs``."""
 import contextlib
 import ctypes
-import weakref
 
 import numpy as np
 import torch
 
 from . import _capi
+from .derived import Derived
 from .depth_head import LazyDepthDistribution
 from .geometry import stack_meta
 from .plane_sweep import _DTYPES, _Workspace, _ptr, _require_gpu, _stream_ptr, _upload
@@ -114,7 +114,7 @@ class _F2vFusedFn(torch.autograd.Function):
                 None, None)
 
 
-_GRID_CACHE = {}
+_grid_cache = Derived(capacity=16)
 # native: the gradient of a channels-last cost volume in that layout and type
 _BWD_GATHER = {'on': True, 'native': True}
 
@@ -142,11 +142,12 @@ def _regular_grid(coords, desc):
     # caching allocator hands a freed address to the next coordinate tensor of the same shape, version 0 again, and
     # an address-only key would serve it the previous tensor's verdict
     owner = coords._base if coords._base is not None else coords
-    key = (id(owner), coords.data_ptr(), coords._version, tuple(coords.shape), desc.nz, desc.ny, desc.nx)
-    hit = _GRID_CACHE.get(key)
-    if hit is not None and hit[1]() is owner:
-        return hit[0]
     nz, ny, nx = desc.nz, desc.ny, desc.nx
+    return _grid_cache.get((id(owner), coords.data_ptr(), tuple(coords.shape), nz, ny, nx), (owner,),
+                           lambda: _check_regular_grid(coords, nz, ny, nx))
+
+
+def _check_regular_grid(coords, nz, ny, nx):
     grid = None
     if coords.numel() == 3 * nz * ny * nx and min(nz, ny, nx) >= 1:
         c = coords.reshape(nz, ny, nx, 3)
@@ -165,9 +166,6 @@ def _regular_grid(coords, desc):
         if max(vals[6:]) <= 1e-3 * step and all(np.isfinite(vals)) and step > 0:
             # (an axis of extent 1 has no step: any non-zero value serves the index arithmetic)
             grid = tuple(v if (i % 2 == 0 or v != 0.0) else 1.0 for i, v in enumerate(vals[:6]))
-    if len(_GRID_CACHE) > 16:
-        _GRID_CACHE.clear()
-    _GRID_CACHE[key] = (grid, weakref.ref(owner))
     return grid
 
 

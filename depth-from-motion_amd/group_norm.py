@@ -7,16 +7,16 @@ GroupNorm kernel followed by a separate ReLU.
 touching checkpoints.
 """
 import ctypes
-import weakref
 
 import torch
 from torch import nn
 
 from . import _capi
+from .derived import Derived
 from .plane_sweep import _DTYPES, _Workspace, _ptr, _stream_ptr
 
 
-_F32_CACHE = {}
+_f32_cache = Derived(capacity=1024)
 
 
 def _f32_params(weight, bias):
@@ -24,17 +24,8 @@ def _f32_params(weight, bias):
     conversion kernels per call (36 per DfMBackbone forward).  Cached per parameter and version."""
     if weight.dtype == torch.float32 and bias.dtype == torch.float32:
         return weight.detach().contiguous(), bias.detach().contiguous()
-    key = (id(weight), id(bias))
-    ver = (weight._version, bias._version, weight.device, weight.data_ptr(), bias.data_ptr())
-    hit = _F32_CACHE.get(key)
-    # the entry holds weak references: an id() reused by a new tensor never matches a dead one
-    if hit is None or hit[0] != ver or hit[3]() is not weight or hit[4]() is not bias:
-        if len(_F32_CACHE) > 1024:
-            _F32_CACHE.clear()
-        hit = (ver, weight.detach().float().contiguous(), bias.detach().float().contiguous(),
-               weakref.ref(weight), weakref.ref(bias))
-        _F32_CACHE[key] = hit
-    return hit[1], hit[2]
+    return _f32_cache.get((id(weight), id(bias)), (weight, bias), lambda: (
+        weight.detach().float().contiguous(), bias.detach().float().contiguous()))
 
 
 _XMASK = True   # False: the backward reads the ReLU mask from the kept output, as the fused-residual case does (tests)

@@ -137,7 +137,7 @@ class DfMStereoPath(nn.Module):
         if (self.two_streams and cur_feats[0].is_cuda and not torch.is_grad_enabled() and not self.training and
                 not torch.cuda.is_current_stream_capturing()):
             from .modules import DfMBackbone
-            from .conv3d import derived_builds
+            from .derived import derived_builds
             d0 = cur_feats[0].device
             main = torch.cuda.current_stream(d0)
             side = DfMBackbone._side_streams.get(d0)

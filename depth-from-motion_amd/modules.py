@@ -22,15 +22,15 @@ The 3x3 2-D convolutions of SPPUNetNeck / BEVHourglass run in the same MFMA kern
 along depth); 1x1 convolutions and bilinear up-sampling outside the fused SPP tail are torch ops.
 """
 import ctypes
-import weakref
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .conv3d import (DerivedStateMixin, conv3d_to1_norm, long_axis_gram, note_derived_build, MfmaConv2d, MfmaConv3d, MfmaConv3dG, MfmaConv3dTo1, MfmaConvTranspose2d,
+from .conv3d import (conv3d_to1_norm, long_axis_gram, MfmaConv2d, MfmaConv3d, MfmaConv3dG, MfmaConv3dTo1, MfmaConvTranspose2d,
                      MfmaConvTranspose3d, channel_slice, channel_split)
+from .derived import Derived, derived
 from .depth_head import depth_distribution_loss, depth_head_forward, depth_head_statistics
 from .frustum_to_voxel import frustum_to_voxel_sample
 from .geometry import stack_meta
@@ -47,15 +47,8 @@ def _on_device(owner, name, device):
     t = getattr(owner, name)
     if not torch.is_tensor(t) or t.device == device:
         return t
-    # the entry holds a weak reference to the host tensor: a re-injected tensor that reuses a freed
-    # id() (version 0 again) must not hit a stale device copy
-    key = (t._version, str(device))
-    cache = owner.__dict__.setdefault('_dev_cache', {})
-    hit = cache.get(name)
-    if hit is None or hit[0]() is not t or hit[1] != key:
-        hit = cache[name] = (weakref.ref(t), key, t.to(device=device, dtype=torch.float32).contiguous())
-        note_derived_build()
-    return hit[2]
+    return derived(owner).get(('on_device', name), (t,),
+                              lambda: t.to(device=device, dtype=torch.float32).contiguous(), device)
 
 
 # --------------------------------------------------------------------------
@@ -79,7 +72,7 @@ def _make_norm(norm_cfg, channels):
     return name, layer
 
 
-class ConvModule(DerivedStateMixin, nn.Module):
+class ConvModule(nn.Module):
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0,
                  conv_cfg=None, norm_cfg=None, act_cfg=dict(type='ReLU')):
@@ -157,17 +150,16 @@ class ConvModule(DerivedStateMixin, nn.Module):
         tiny kernels per block and forward otherwise: launch-bound on the 9-block necks)"""
         norm = getattr(self, self.norm_name)
         ts = [norm.running_mean, norm.running_var] + ([norm.weight, norm.bias] if norm.affine else [])
-        key = tuple((t._version, t.data_ptr()) for t in ts) + (norm.eps,)
-        if getattr(self, '_fold_key', None) != key:
+
+        def make():
             scale = torch.rsqrt(norm.running_var.float() + norm.eps)
             if norm.affine:
                 scale = scale * norm.weight.float()
             shift = -norm.running_mean.float() * scale
             if norm.affine:
                 shift = shift + norm.bias.float()
-            self._fold, self._fold_key = (scale.contiguous(), shift.contiguous()), key
-            note_derived_build()
-        return self._fold
+            return scale.contiguous(), shift.contiguous()
+        return derived(self).get('fold', tuple(ts), make, norm.eps)
 
     def forward_fused(self, x, residual=None, relu=None):
         scale, shift = self._folded_norm()
@@ -305,7 +297,7 @@ class hourglass(nn.Module):  # noqa: N801  (reference class name)
 # DfMBackbone
 # --------------------------------------------------------------------------
 @register_module
-class DfMBackbone(DerivedStateMixin, nn.Module):
+class DfMBackbone(nn.Module):
 
     def __init__(self,
                  in_channels,
@@ -349,7 +341,6 @@ class DfMBackbone(DerivedStateMixin, nn.Module):
         # dres0_mono.conv run as ONE kernel and the (B, 2C, D, H, W) volume is never written
         # (csrc/sweep_conv.hip); False keeps the materialised volume
         self.fuse_sweep_dres0 = True
-        self._sweep_conv_pack = (None, None)
 
     def init_weights(self):
         pass
@@ -511,11 +502,7 @@ class DfMBackbone(DerivedStateMixin, nn.Module):
 
     def _sweep_conv_packed(self):
         ws, wm = self.dres0.conv.weight, self.dres0_mono.conv.weight
-        key = (ws._version, ws.data_ptr(), wm._version, wm.data_ptr(), str(ws.device))
-        if self._sweep_conv_pack[0] != key:
-            self._sweep_conv_pack = (key, pack_sweep_conv_weights(ws, wm))
-            note_derived_build()
-        return self._sweep_conv_pack[1]
+        return derived(self).get('sweep_conv_pack', (ws, wm), lambda: pack_sweep_conv_weights(ws, wm))
 
     def forward(self, cur_stereo_feats, prev_stereo_feats, img_metas, cur_sem_feats=None):
         # (matrices staged on the device by data_geometry.stage_geometry are read where they lie)
@@ -581,23 +568,21 @@ class DfMBackbone(DerivedStateMixin, nn.Module):
         # bf16 costs and a bf16 weight (the fast path's model): the product on the matrix cores (round 6; every
         # bf16 x bf16 product is exact, sums in fp32); other types take the VALU kernel
         mfma = (self.mfma_gate and s_cost.dtype == torch.bfloat16 and w.dtype == torch.bfloat16)
-        key = (w._version, w.data_ptr(), str(w.device), w.dtype, mfma)
+
+        def make():
+            nb = lib.dfm_cost_gate_mfma_weight_bytes(D) if mfma else lib.dfm_cost_gate_weight_bytes(D)
+            packed = torch.empty(nb, dtype=torch.uint8, device=w.device)
+            pack = lib.dfm_cost_gate_mfma_pack_weights if mfma else lib.dfm_cost_gate_pack_weights
+            _capi.check(pack(_ptr(w.detach()), _DTYPES[w.dtype], D, _ptr(packed), _stream_ptr(s_cost.device)))
+            return packed
         with torch.cuda.device(s_cost.device):
-            if self.__dict__.get('_gate_pack', (None, None))[0] != key:  # packed once per weight version
-                nb = lib.dfm_cost_gate_mfma_weight_bytes(D) if mfma else lib.dfm_cost_gate_weight_bytes(D)
-                packed = torch.empty(nb, dtype=torch.uint8, device=w.device)
-                pack = lib.dfm_cost_gate_mfma_pack_weights if mfma else lib.dfm_cost_gate_pack_weights
-                _capi.check(pack(_ptr(w.detach()), _DTYPES[w.dtype], D, _ptr(packed), _stream_ptr(s_cost.device)))
-                self.__dict__['_gate_pack'] = (key, packed)
-                note_derived_build()
+            packed = derived(self).get('gate_pack', (w,), make, (w.dtype, mfma, D))  # packed once per weight version
             if mfma:
-                _capi.check(lib.dfm_cost_gate_mfma_fwd(B, D, H * W, _ptr(s_cost), _ptr(m_cost),
-                                                       _ptr(self.__dict__['_gate_pack'][1]), _ptr(out),
-                                                       _stream_ptr(s_cost.device)))
+                _capi.check(lib.dfm_cost_gate_mfma_fwd(B, D, H * W, _ptr(s_cost), _ptr(m_cost), _ptr(packed),
+                                                       _ptr(out), _stream_ptr(s_cost.device)))
             else:
                 _capi.check(lib.dfm_cost_gate_fwd(B, D, H * W, _DTYPES[s_cost.dtype], _ptr(s_cost), _ptr(m_cost),
-                                                  _ptr(self.__dict__['_gate_pack'][1]), _ptr(out),
-                                                  _stream_ptr(s_cost.device)))
+                                                  _ptr(packed), _ptr(out), _stream_ptr(s_cost.device)))
         return out
 
     def _predict(self, stereo, s_cost, mono, m_cost):
@@ -644,7 +629,7 @@ class _GateLogitsFn(torch.autograd.Function):
 # DepthHead (forward path; the loss is outside SURVEY.md 8a)
 # --------------------------------------------------------------------------
 @register_module
-class DepthHead(DerivedStateMixin, nn.Module):
+class DepthHead(nn.Module):
 
     def __init__(self, depth_cfg, in_channels=32, with_convs=True,
                  depth_loss=dict(type='ce', loss_weight=1.0), downsample_factor=4, num_views=5,
@@ -739,7 +724,7 @@ class DepthHead(DerivedStateMixin, nn.Module):
 # FrustumToVoxel
 # --------------------------------------------------------------------------
 @register_module
-class FrustumToVoxel(DerivedStateMixin, nn.Module):
+class FrustumToVoxel(nn.Module):
 
     def __init__(self, num_3dconvs=1, cv_channels=32, out_channels=32, in_sem_channels=32,
                  sem_atten_feat=True, stereo_atten_feat=False, cat_img_feature=True,
@@ -774,13 +759,8 @@ class FrustumToVoxel(DerivedStateMixin, nn.Module):
         # the detector injects a host tensor (dfm.py:99-100) and the reference uploads it every
         # forward (.cuda(), feature_transformation.py:82): 21 MB at config K; uploaded once here
         c = self.coordinates_3d
-        key = (c._version, str(device))
-        ref = self.__dict__.get('_coords_ref')
-        if ref is None or ref() is not c or self.__dict__.get('_coords_key') != key:
-            self.__dict__['_coords_dev'] = c.to(device=device, dtype=torch.float32).contiguous()
-            self.__dict__['_coords_ref'], self.__dict__['_coords_key'] = weakref.ref(c), key
-            note_derived_build()
-        return self._coords_dev
+        return derived(self).get('coords', (c,), lambda: c.to(device=device, dtype=torch.float32).contiguous(),
+                                 device)
 
     def forward(self, stereo_feat, stereo_feat_softmax, img_metas, cur_sem_feats=None):
         voxel = frustum_to_voxel_sample(stereo_feat, stereo_feat_softmax, img_metas,
@@ -834,7 +814,7 @@ def _to_bev(x):
 
 
 @register_module
-class OutdoorImVoxelNeck(DerivedStateMixin, nn.Module):
+class OutdoorImVoxelNeck(nn.Module):
 
     def __init__(self, in_channels, out_channels, norm_cfg=dict(type='BN3d'), output_bev=True):
         super().__init__()
@@ -852,7 +832,7 @@ class OutdoorImVoxelNeck(DerivedStateMixin, nn.Module):
 
 
 @register_module
-class DfMNeck(DerivedStateMixin, nn.Module):
+class DfMNeck(nn.Module):
 
     def __init__(self, in_channels, out_channels, norm_cfg=dict(type='BN3d'), num_frames=2):
         super().__init__()
@@ -924,13 +904,11 @@ def _conv_norm_2d(seq, x, residual=None, relu=False):
             not norm.training and norm.track_running_stats and norm.affine and conv.eligible(x) and
             (residual is None or (residual.dtype == x.dtype and
                                   residual.is_contiguous(memory_format=torch.channels_last)))):
-        key = tuple((t._version, t.data_ptr()) for t in (norm.weight, norm.bias, norm.running_mean, norm.running_var))
-        if seq.__dict__.get('_fold_key') != key:
+        def make():
             scale = norm.weight.float() / torch.sqrt(norm.running_var.float() + norm.eps)
-            seq.__dict__['_fold'] = (scale, norm.bias.float() - norm.running_mean.float() * scale)
-            seq.__dict__['_fold_key'] = key
-            note_derived_build()
-        scale, shift = seq.__dict__['_fold']
+            return scale, norm.bias.float() - norm.running_mean.float() * scale
+        scale, shift = derived(seq).get('fold', (norm.weight, norm.bias, norm.running_mean, norm.running_var), make,
+                                        norm.eps)
         return conv.forward_fused(x, scale, shift, residual=residual, relu=relu)
     y = conv(x)
     if isinstance(norm, nn.modules.batchnorm._BatchNorm):
@@ -947,33 +925,23 @@ def _conv_norm_2d(seq, x, residual=None, relu=False):
     return F.relu(y) if relu else y
 
 
-_INTERP_MATRICES = {}
+_interp_matrices, _interp_tables = Derived(capacity=256), Derived(capacity=256)
 
 
 def _interp_matrix(n_in, n_out, align_corners, scale, device):
     """(n_out, n_in) fp32 matrix of 1-D bilinear interpolation, taken from ATen itself (its forward on
     the identity), so it carries exactly the weights F.interpolate applies"""
-    key = (n_in, n_out, bool(align_corners), scale, str(device))
-    m = _INTERP_MATRICES.get(key)
-    if m is None:
+    def make():
         eye = torch.eye(n_in, dtype=torch.float32, device=device).view(1, n_in, 1, n_in)
         kw = dict(scale_factor=(1.0, scale)) if scale is not None else dict(size=(1, n_out))
-        m = F.interpolate(eye, mode='bilinear', align_corners=align_corners, **kw).view(n_in, n_out).t().contiguous()
-        if len(_INTERP_MATRICES) > 256:
-            _INTERP_MATRICES.clear()
-        _INTERP_MATRICES[key] = m
-    return m
-
-
-_INTERP_TABLES = {}
+        return F.interpolate(eye, mode='bilinear', align_corners=align_corners, **kw).view(n_in, n_out).t().contiguous()
+    return _interp_matrices.get((n_in, n_out, bool(align_corners), scale, str(device)), (), make)
 
 
 def _interp_table(n_in, n_out, align_corners, scale, device):
     """the non-zeros of the transposed interpolation matrix, padded: (idx (n_in, K) int32, w (n_in, K) fp32, K) --
     for input index i the outputs that interpolate from it and their weights (dfm_bilinear_resize_bwd_nhwc)"""
-    key = (n_in, n_out, bool(align_corners), scale, str(device))
-    t = _INTERP_TABLES.get(key)
-    if t is None:
+    def make():
         m = _interp_matrix(n_in, n_out, align_corners, scale, device).t().cpu().numpy()   # (n_in, n_out)
         nz = m != 0
         K = max(1, int(nz.sum(1).max()))
@@ -983,12 +951,8 @@ def _interp_table(n_in, n_out, align_corners, scale, device):
             j = np.nonzero(nz[i])[0]
             idx[i, :len(j)] = j
             w[i, :len(j)] = m[i, j]
-        t = (torch.from_numpy(idx).to(device), torch.from_numpy(w).to(device), K)
-        if len(_INTERP_TABLES) > 256:
-            _INTERP_TABLES.clear()
-        _INTERP_TABLES[key] = t
-        note_derived_build()
-    return t
+        return torch.from_numpy(idx).to(device), torch.from_numpy(w).to(device), K
+    return _interp_tables.get((n_in, n_out, bool(align_corners), scale, str(device)), (), make)
 
 
 class _BilinearResizeFn(torch.autograd.Function):
@@ -1148,7 +1112,7 @@ class hourglass2d(nn.Module):  # noqa: N801  (reference class name)
 
 
 @register_module
-class BEVHourglass(DerivedStateMixin, nn.Module):
+class BEVHourglass(nn.Module):
 
     def __init__(self, in_channels, out_channels, norm_cfg=None, output_prehg_feat=True,
                  init_cfg=None):
@@ -1172,7 +1136,7 @@ class BEVHourglass(DerivedStateMixin, nn.Module):
 
 
 @register_module
-class SPPUNetNeck(DerivedStateMixin, nn.Module):
+class SPPUNetNeck(nn.Module):
 
     def __init__(self, in_channels, start_level, sem_channels=[128, 32], stereo_channels=[32, 32],
                  spp_channel=32, with_upconv=True, cat_img_feature=True, norm_cfg=None,
@@ -1263,16 +1227,12 @@ class SPPUNetNeck(DerivedStateMixin, nn.Module):
                 max(p.shape[1] * p.shape[2] for p in pooled) * self.spp_channel * 2 > 62 * 1024 or
                 256 % self.spp_channel):
             return None
-        key = tuple((m.conv.weight._version, m.conv.weight.data_ptr()) for m in cms) + \
-            tuple((getattr(m, m.norm_name).weight._version, getattr(m, m.norm_name).bias._version) for m in cms)
-        if self.__dict__.get('_spp_key') != key:
-            self.__dict__['_spp_params'] = [
-                (m.conv.weight.detach().float().reshape(m.conv.out_channels, -1).contiguous(),
-                 getattr(m, m.norm_name).weight.detach().float().contiguous(),
-                 getattr(m, m.norm_name).bias.detach().float().contiguous()) for m in cms]
-            self.__dict__['_spp_key'] = key
-            note_derived_build()
-        params = self.__dict__['_spp_params']
+        norms = [getattr(m, m.norm_name) for m in cms]
+        params = derived(self).get(
+            'spp_params', tuple(t for m, n in zip(cms, norms) for t in (m.conv.weight, n.weight, n.bias)),
+            lambda: [(m.conv.weight.detach().float().reshape(m.conv.out_channels, -1).contiguous(),
+                      n.weight.detach().float().contiguous(), n.bias.detach().float().contiguous())
+                     for m, n in zip(cms, norms)])
         B, _, H, W = srcs[0].shape
         d = _capi.SppDesc()
         d.batch, d.h, d.w = B, H, W
