@@ -11,125 +11,6 @@ LIB_PATH = os.environ.get('DFM_HIP_LIB', os.path.join(_HERE, 'lib', 'libdfm_hip.
 
 DFM_F32, DFM_BF16 = 0, 1
 
-# every symbol include/dfm_hip.h declares (tests/test_capi_symbols.py checks
-# the header against this list and against the built library)
-EXPORTS = (
-    'dfm_version',
-    'dfm_last_error',
-    'dfm_profile_begin',
-    'dfm_profile_end',
-    'dfm_camera_prepare',
-    'dfm_plane_sweep_workspace_bytes',
-    'dfm_plane_sweep_fwd',
-    'dfm_plane_sweep_cl_workspace_bytes',
-    'dfm_plane_sweep_fwd_channels_last',
-    'dfm_plane_sweep_fwd_nhwc',
-    'dfm_plane_sweep_fwd_from_nhwc',
-    'dfm_plane_sweep_bwd',
-    'dfm_plane_sweep_grid',
-    'dfm_plane_sweep_last_kernel',
-    'dfm_plane_sweep_bwd_last_kernel',
-    'dfm_plane_sweep_fwd_opts',
-    'dfm_plane_sweep_bwd_opts',
-    'dfm_plane_sweep_bwd_channels_last',
-    'dfm_plane_sweep_bwd_cur_nhwc',
-    'dfm_plane_sweep_bwd_prev_gather_workspace_bytes',
-    'dfm_plane_sweep_bwd_prev_gather',
-    'dfm_plane_sweep_bwd_gather',
-    'dfm_plane_sweep_autotune',
-    'dfm_plane_sweep_tuning',
-    'dfm_plane_sweep_reset_tuning',
-    'dfm_store_probe',
-    'dfm_clock_probe',
-    'dfm_point_sample_mv_workspace_bytes',
-    'dfm_point_sample_mv_fwd',
-    'dfm_frustum_to_voxel_workspace_bytes',
-    'dfm_frustum_to_voxel_fwd',
-    'dfm_depth_head_fwd',
-    'dfm_depth_head_stats_fwd',
-    'dfm_frustum_to_voxel_fused_fwd',
-    'dfm_frustum_to_voxel_bwd_workspace_bytes',
-    'dfm_frustum_to_voxel_bwd',
-    'dfm_frustum_to_voxel_fused_bwd',
-    'dfm_frustum_to_voxel_bwd_gather_workspace_bytes',
-    'dfm_frustum_to_voxel_bwd_gather',
-    'dfm_frustum_to_voxel_bwd_gather_cl',
-    'dfm_point_sample_mv_fwd_batched',
-    'dfm_point_sample_mv_bwd_workspace_bytes',
-    'dfm_point_sample_mv_bwd',
-    'dfm_depth_head_bwd',
-    'dfm_sweep_conv_weight_bytes',
-    'dfm_sweep_conv_pack_weights',
-    'dfm_sweep_conv_stats_splits',
-    'dfm_sweep_conv_fwd',
-    'dfm_cost_gate_weight_bytes',
-    'dfm_cost_gate_pack_weights',
-    'dfm_cost_gate_fwd',
-    'dfm_conv3d_k3_c32_weight_bytes',
-    'dfm_conv3d_k3_c32_pack_weights',
-    'dfm_conv3d_k3_c32_stats_splits',
-    'dfm_conv3d_k3_c32_fwd',
-    'dfm_conv3d_k3_c32_fwd_strided',
-    'dfm_conv3d_k3_c32_fwd_slices',
-    'dfm_conv3d_k3_c32_to1_fwd',
-    'dfm_group_norm_coefficients',
-    'dfm_conv3d_to1_norm_fwd',
-    'dfm_conv3d_to1_bwd_data',
-    'dfm_conv3d_to1_wgrad_workspace_bytes',
-    'dfm_conv3d_to1_wgrad',
-    'dfm_bilinear_resize_bwd_nhwc',
-    'dfm_depth_pool_fwd',
-    'dfm_depth_pool_bwd',
-    'dfm_cost_gate_mfma_weight_bytes',
-    'dfm_cost_gate_mfma_pack_weights',
-    'dfm_cost_gate_mfma_fwd',
-    'dfm_conv3d_g_weight_bytes',
-    'dfm_conv3d_g_pack_weights',
-    'dfm_conv3d_g_pack_weights_2d',
-    'dfm_conv3d_g_fwd',
-    'dfm_conv3d_g_fwd_f32',
-    'dfm_conv3d_g_plan',
-    'dfm_conv3d_wgrad_workspace_bytes',
-    'dfm_conv3d_wgrad',
-    'dfm_conv3d_wgrad_to',
-    'dfm_depth_loss_fwd',
-    'dfm_depth_loss_bwd',
-    'dfm_depth_loss_fused_fwd',
-    'dfm_depth_loss_fused_bwd',
-    'dfm_voxel_sample_fwd',
-    'dfm_voxel_sample_bwd',
-    'dfm_voxel_sample_mv_fwd',
-    'dfm_voxel_sample_mv_bwd',
-    'dfm_spp_tail_workspace_bytes',
-    'dfm_spp_tail_fwd',
-    'dfm_group_norm_workspace_bytes',
-    'dfm_group_norm_fwd',
-    'dfm_group_norm_fwd_channels_last',
-    'dfm_group_norm_apply_channels_last',
-    'dfm_group_norm_fwd_channels_last_res',
-    'dfm_group_norm_apply_channels_last_res',
-    'dfm_group_norm_bwd',
-    'dfm_group_norm_bwd_channels_last',
-    'dfm_group_norm_bwd_channels_last_xmask',
-    'dfm_batch_norm_workspace_bytes',
-    'dfm_batch_norm_stats_channels_last',
-    'dfm_batch_norm_apply_gathered_channels_last',
-    'dfm_batch_norm_bwd_reduce_channels_last',
-    'dfm_batch_norm_bwd_apply_channels_last',
-    'dfm_imitation_loss_workspace_bytes',
-    'dfm_imitation_loss_fwd',
-    'dfm_imitation_loss_bwd',
-    'dfm_box_nms_workspace_bytes',
-    'dfm_box_nms_rotated',
-    'dfm_box_nms_aligned',
-    'dfm_box_iou_rotated',
-    'dfm_diff_iou_rotated',
-    'dfm_iou3d_loss_from_deltas',
-    'dfm_nearest_bev_overlaps',
-    'dfm_anchor_target_workspace_bytes',
-    'dfm_anchor_target_3d',
-)
-
 
 class SweepDesc(ctypes.Structure):
     """struct dfm_sweep_desc"""
@@ -293,6 +174,149 @@ class DfmHipError(RuntimeError):
     pass
 
 
+def _signatures():
+    """name -> (restype, argtypes) of every symbol include/dfm_hip.h declares: the whole binding (tests/
+    test_capi_symbols.py and tests/test_launch.py check it against the header -- names, parameter counts, void
+    returns -- and against the built library).  vp: a ``void *`` of the header (dtype-dependent memory, the stream),
+    fp: a typed pointer (``float *``, ``int32_t *``, ...); both are c_void_p here."""
+    P = ctypes.POINTER
+    vp = fp = ctypes.c_void_p
+    ci, i32, i64, sz, f32, f64 = (ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float,
+                                  ctypes.c_double)
+    dp, op, mp, f2p, spp, pp = P(SweepDesc), P(SweepOpts), P(MvDesc), P(F2vDesc), P(SppDesc), P(vp)
+    vsp, vmp, cp, wp, lp = P(VsDesc), P(VsMvDesc), P(Conv3dDesc), P(Conv3dWgradDesc), P(DepthLossDesc)
+    ip, atp = P(ImitationDesc), P(AnchorTargetDesc)
+    return {
+        'dfm_version': (ci, []),
+        'dfm_last_error': (ctypes.c_char_p, []),
+        'dfm_profile_begin': (ci, [ci]),
+        'dfm_profile_end': (ci, [P(f64), P(ci)]),
+        'dfm_camera_prepare': (ci, [fp, i32, i32, i32, fp, fp, vp]),
+        'dfm_plane_sweep_workspace_bytes': (sz, [dp]),
+        'dfm_plane_sweep_fwd': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
+        'dfm_plane_sweep_cl_workspace_bytes': (sz, [dp]),
+        'dfm_plane_sweep_fwd_channels_last': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
+        'dfm_plane_sweep_fwd_nhwc': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
+        'dfm_plane_sweep_fwd_from_nhwc': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
+        'dfm_plane_sweep_bwd': (ci, [dp, vp, fp, fp, fp, fp, fp, fp, vp]),
+        'dfm_plane_sweep_grid': (ci, [dp, i32, fp, fp, fp, fp, fp, fp, vp]),
+        'dfm_plane_sweep_last_kernel': (ci, []),
+        'dfm_plane_sweep_bwd_last_kernel': (ci, []),
+        'dfm_plane_sweep_fwd_opts': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp, op]),
+        'dfm_plane_sweep_bwd_opts': (ci, [dp, vp, fp, fp, fp, fp, fp, fp, vp, op]),
+        'dfm_plane_sweep_bwd_channels_last': (ci, [dp, vp, fp, fp, fp, fp, fp, fp, vp, sz, vp]),
+        'dfm_plane_sweep_bwd_cur_nhwc': (ci, [dp, vp, fp, fp, fp, fp, fp, vp]),
+        'dfm_plane_sweep_bwd_prev_gather_workspace_bytes': (sz, [dp]),
+        'dfm_plane_sweep_bwd_prev_gather': (ci, [dp, vp, fp, fp, fp, fp, fp, vp, sz, vp]),
+        'dfm_plane_sweep_bwd_gather': (ci, [dp, i32, vp, i32, fp, fp, fp, fp, fp, i32, vp, sz, vp]),
+        'dfm_plane_sweep_autotune': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp, op]),
+        'dfm_plane_sweep_tuning': (ci, [dp, op]),
+        'dfm_plane_sweep_reset_tuning': (None, []),
+        'dfm_store_probe': (ci, [vp, i32, i32, i64, i32, i32, vp]),
+        'dfm_clock_probe': (ci, [vp, i32, vp]),
+        'dfm_point_sample_mv_workspace_bytes': (sz, [mp]),
+        'dfm_point_sample_mv_fwd': (ci, [mp, vp, fp, fp, fp, vp, vp, vp, sz, vp]),
+        'dfm_frustum_to_voxel_workspace_bytes': (sz, [f2p]),
+        'dfm_frustum_to_voxel_fwd': (ci, [f2p, vp, vp, vp, fp, fp, vp, vp, sz, vp]),
+        'dfm_depth_head_fwd': (ci, [i32, i32, i32, i32, i32, i32, vp, fp, vp, vp, vp, vp]),
+        'dfm_depth_head_stats_fwd': (ci, [i32, i32, i32, i32, i32, i32, vp, fp, fp, fp, vp, vp]),
+        'dfm_frustum_to_voxel_fused_fwd': (ci, [f2p, vp, vp, fp, fp, i32, vp, fp, fp, vp, vp, sz, vp]),
+        'dfm_frustum_to_voxel_bwd_workspace_bytes': (sz, [f2p]),
+        'dfm_frustum_to_voxel_bwd': (ci, [f2p, vp, vp, fp, fp, fp, fp, vp, sz, vp]),
+        'dfm_frustum_to_voxel_fused_bwd': (ci, [f2p, vp, vp, fp, fp, i32, fp, fp, fp, fp, vp, sz, vp]),
+        'dfm_frustum_to_voxel_bwd_gather_workspace_bytes': (sz, [f2p]),
+        'dfm_frustum_to_voxel_bwd_gather': (ci, [f2p, vp, vp, vp, fp, fp, i32, fp, P(f32), fp, fp, fp, vp, sz, vp]),
+        'dfm_frustum_to_voxel_bwd_gather_cl': (ci, [f2p, vp, vp, vp, fp, fp, i32, fp, P(f32), fp, vp, fp, vp, sz, vp]),
+        'dfm_point_sample_mv_fwd_batched': (ci, [vp, i32, vp, fp, i32, fp, fp, vp, vp, vp]),
+        'dfm_point_sample_mv_bwd_workspace_bytes': (sz, [mp]),
+        'dfm_point_sample_mv_bwd': (ci, [mp, vp, fp, fp, fp, fp, vp, sz, vp]),
+        'dfm_depth_head_bwd': (ci, [i32, i32, i32, i32, i32, i32, vp, fp, vp, vp, vp, fp, vp]),
+        'dfm_sweep_conv_weight_bytes': (sz, []),
+        'dfm_sweep_conv_pack_weights': (ci, [vp, vp, i32, vp, vp]),
+        'dfm_sweep_conv_stats_splits': (ci, [dp, i32]),
+        'dfm_sweep_conv_fwd': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, vp, fp, fp, i32, vp]),
+        'dfm_cost_gate_weight_bytes': (sz, [i32]),
+        'dfm_cost_gate_pack_weights': (ci, [vp, i32, i32, vp, vp]),
+        'dfm_cost_gate_fwd': (ci, [i32, i32, i64, i32, vp, vp, vp, vp, vp]),
+        'dfm_conv3d_k3_c32_weight_bytes': (sz, []),
+        'dfm_conv3d_k3_c32_pack_weights': (ci, [vp, i32, i32, i32, i32, vp, vp]),
+        'dfm_conv3d_k3_c32_stats_splits': (ci, [i32, i32, i32, i32, i32]),
+        'dfm_conv3d_k3_c32_fwd': (ci, [i32, i32, i32, i32, vp, vp, fp, vp, i32, i32, i32, fp, vp]),
+        'dfm_conv3d_k3_c32_fwd_strided': (ci, [i32, i32, i32, i32, vp, i32, vp, fp, vp, i32, i32, i32, fp, vp]),
+        'dfm_conv3d_k3_c32_fwd_slices': (ci, [i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp]),
+        'dfm_conv3d_k3_c32_to1_fwd': (ci, [i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]),
+        'dfm_group_norm_coefficients': (ci, [i32, i32, i32, f32, vp, i32, vp, vp, vp, vp]),
+        'dfm_conv3d_to1_norm_fwd': (ci, [i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp]),
+        'dfm_conv3d_to1_bwd_data': (ci, [i32, i32, i32, i32, vp, vp, i32, vp, vp]),
+        'dfm_conv3d_to1_wgrad_workspace_bytes': (sz, []),
+        'dfm_conv3d_to1_wgrad': (ci, [i32, i32, i32, i32, vp, vp, vp, i32, vp, sz, vp]),
+        'dfm_bilinear_resize_bwd_nhwc': (ci, [i32, i32, i32, i32, i32, i32, i32, vp, vp, fp, i32, vp, fp, i32, vp, vp]),
+        'dfm_depth_pool_fwd': (ci, [i64, i32, i64, i32, vp, vp, vp]),
+        'dfm_depth_pool_bwd': (ci, [i64, i32, i64, i32, vp, vp, vp]),
+        'dfm_cost_gate_mfma_weight_bytes': (sz, [i32]),
+        'dfm_cost_gate_mfma_pack_weights': (ci, [vp, i32, i32, vp, vp]),
+        'dfm_cost_gate_mfma_fwd': (ci, [i32, i32, i64, vp, vp, vp, vp, vp]),
+        'dfm_conv3d_g_weight_bytes': (sz, [i32, i32]),
+        'dfm_conv3d_g_pack_weights': (ci, [vp, i32, i32, i32, i32, i32, vp, vp]),
+        'dfm_conv3d_g_pack_weights_2d': (ci, [vp, i32, i32, i32, i32, i32, vp, vp]),
+        'dfm_conv3d_g_fwd': (ci, [cp, vp, vp, fp, fp, vp, vp, vp]),
+        'dfm_conv3d_g_fwd_f32': (ci, [cp, vp, vp, vp, vp, vp]),
+        'dfm_conv3d_g_plan': (ci, [cp, P(i64)]),
+        'dfm_conv3d_wgrad_workspace_bytes': (sz, [wp]),
+        'dfm_conv3d_wgrad': (ci, [wp, vp, vp, fp, vp, sz, vp]),
+        'dfm_conv3d_wgrad_to': (ci, [wp, vp, vp, vp, i32, vp, sz, vp]),
+        'dfm_depth_loss_fwd': (ci, [lp, vp, fp, fp, fp, vp, vp]),
+        'dfm_depth_loss_bwd': (ci, [lp, vp, fp, fp, fp, vp, vp]),
+        'dfm_depth_loss_fused_fwd': (ci, [lp, vp, i32, fp, fp, fp, vp, vp]),
+        'dfm_depth_loss_fused_bwd': (ci, [lp, vp, i32, fp, fp, fp, fp, vp]),
+        'dfm_voxel_sample_fwd': (ci, [vsp, vp, fp, vp, vp]),
+        'dfm_voxel_sample_bwd': (ci, [vsp, vp, fp, fp, vp]),
+        'dfm_voxel_sample_mv_fwd': (ci, [vmp, fp, vp, fp, vp, vp]),
+        'dfm_voxel_sample_mv_bwd': (ci, [vmp, fp, vp, fp, fp, vp]),
+        'dfm_spp_tail_workspace_bytes': (sz, [spp]),
+        'dfm_spp_tail_fwd': (ci, [spp, pp, pp, pp, pp, pp, vp, vp, sz, vp]),
+        'dfm_group_norm_workspace_bytes': (sz, [i32, i32, i64, i32]),
+        'dfm_group_norm_fwd': (ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, fp, vp, sz, vp]),
+        'dfm_group_norm_fwd_channels_last': (ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, fp, vp, sz,
+            vp]),
+        'dfm_group_norm_apply_channels_last': (ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, fp, fp, i32,
+            vp, sz, vp]),
+        'dfm_group_norm_fwd_channels_last_res': (ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, vp, fp, fp, vp,
+            sz, vp]),
+        'dfm_group_norm_apply_channels_last_res': (ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, vp, fp, fp,
+            fp, i32, vp, sz, vp]),
+        'dfm_group_norm_bwd': (ci, [i32, i32, i64, i32, i32, i32, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp, sz, vp]),
+        'dfm_group_norm_bwd_channels_last': (ci, [i32, i32, i64, i32, i32, i32, vp, vp, vp, fp, fp, fp, vp, vp, fp, fp,
+            vp, sz, vp]),
+        'dfm_group_norm_bwd_channels_last_xmask': (ci, [i32, i32, i64, i32, i32, vp, vp, fp, fp, fp, fp, vp, fp, fp, vp,
+            sz, vp]),
+        'dfm_batch_norm_workspace_bytes': (sz, [i32, i64]),
+        'dfm_batch_norm_stats_channels_last': (ci, [i32, i64, i32, vp, fp, vp, sz, vp]),
+        'dfm_batch_norm_apply_gathered_channels_last': (ci, [i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, vp, fp,
+            fp, fp, vp]),
+        'dfm_batch_norm_bwd_reduce_channels_last': (ci, [i32, i64, i32, i32, vp, vp, vp, fp, fp, fp, fp, fp, vp, sz,
+            vp]),
+        'dfm_batch_norm_bwd_apply_channels_last': (ci, [i32, i64, i32, i32, vp, vp, vp, fp, fp, fp, fp, fp, fp, vp, vp,
+            vp, sz, vp]),
+        'dfm_imitation_loss_workspace_bytes': (sz, [ip]),
+        'dfm_imitation_loss_fwd': (ci, [ip, vp, vp, fp, fp, fp, fp, fp, vp, vp, vp, sz, vp]),
+        'dfm_imitation_loss_bwd': (ci, [ip, vp, vp, vp, fp, fp, fp, vp, vp]),
+        'dfm_box_nms_workspace_bytes': (sz, [i32, i32]),
+        'dfm_box_nms_rotated': (ci, [fp, i32, i32, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp]),
+        'dfm_box_nms_aligned': (ci, [fp, i32, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp]),
+        'dfm_box_iou_rotated': (ci, [fp, i32, fp, i32, i32, fp, vp]),
+        'dfm_diff_iou_rotated': (ci, [fp, fp, i32, i32, fp, fp, fp, vp]),
+        'dfm_iou3d_loss_from_deltas': (ci, [fp, fp, fp, vp, i32, i32, i32, fp, fp, vp]),
+        'dfm_nearest_bev_overlaps': (ci, [fp, i32, fp, i32, i32, i32, i32, fp, vp]),
+        'dfm_anchor_target_workspace_bytes': (sz, [i32, i32]),
+        'dfm_anchor_target_3d': (ci, [atp, fp, fp, vp, P(i32), vp, fp, fp, fp, vp, fp, vp, vp, sz, vp]),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTS = tuple(SIGNATURES)
+
+
 _lib = None
 
 
@@ -307,252 +331,9 @@ def lib():
             '`python -c "import __graft_entry__ as g; g.build()"` '
             '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
     h = ctypes.CDLL(LIB_PATH)
-    vp, fp, i32, sz = ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_size_t
-    dp = ctypes.POINTER(SweepDesc)
-    h.dfm_version.restype = ctypes.c_int
-    h.dfm_last_error.restype = ctypes.c_char_p
-    h.dfm_profile_begin.restype = ctypes.c_int
-    h.dfm_profile_begin.argtypes = [ctypes.c_int]
-    h.dfm_profile_end.restype = ctypes.c_int
-    h.dfm_profile_end.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
-    h.dfm_camera_prepare.restype = ctypes.c_int
-    h.dfm_camera_prepare.argtypes = [fp, i32, i32, i32, fp, fp, vp]
-    h.dfm_plane_sweep_workspace_bytes.restype = sz
-    h.dfm_plane_sweep_workspace_bytes.argtypes = [dp]
-    h.dfm_plane_sweep_fwd.restype = ctypes.c_int
-    h.dfm_plane_sweep_fwd.argtypes = [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]
-    h.dfm_plane_sweep_cl_workspace_bytes.restype = sz
-    h.dfm_plane_sweep_cl_workspace_bytes.argtypes = [dp]
-    h.dfm_plane_sweep_fwd_channels_last.restype = ctypes.c_int
-    h.dfm_plane_sweep_fwd_channels_last.argtypes = [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]
-    h.dfm_plane_sweep_fwd_nhwc.restype = ctypes.c_int
-    h.dfm_plane_sweep_fwd_nhwc.argtypes = [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]
-    h.dfm_plane_sweep_fwd_from_nhwc.restype = ctypes.c_int
-    h.dfm_plane_sweep_fwd_from_nhwc.argtypes = [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]
-    h.dfm_plane_sweep_bwd.restype = ctypes.c_int
-    h.dfm_plane_sweep_bwd.argtypes = [dp, vp, fp, fp, fp, fp, fp, fp, vp]
-    h.dfm_plane_sweep_grid.restype = ctypes.c_int
-    h.dfm_plane_sweep_grid.argtypes = [dp, i32, fp, fp, fp, fp, fp, fp, vp]
-    h.dfm_plane_sweep_last_kernel.restype = ctypes.c_int
-    h.dfm_plane_sweep_bwd_last_kernel.restype = ctypes.c_int
-    h.dfm_plane_sweep_bwd_last_kernel.argtypes = []
-    op = ctypes.POINTER(SweepOpts)
-    h.dfm_plane_sweep_fwd_opts.restype = ctypes.c_int
-    h.dfm_plane_sweep_fwd_opts.argtypes = [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp, op]
-    h.dfm_plane_sweep_bwd_opts.restype = ctypes.c_int
-    h.dfm_plane_sweep_bwd_opts.argtypes = [dp, vp, fp, fp, fp, fp, fp, fp, vp, op]
-    h.dfm_store_probe.restype = ctypes.c_int
-    h.dfm_store_probe.argtypes = [vp, i32, i32, ctypes.c_int64, i32, i32, vp]
-    h.dfm_clock_probe.restype = ctypes.c_int
-    h.dfm_clock_probe.argtypes = [vp, i32, vp]
-    h.dfm_plane_sweep_bwd_channels_last.restype = ctypes.c_int
-    h.dfm_plane_sweep_bwd_channels_last.argtypes = [dp, vp, fp, fp, fp, fp, fp, fp, vp, sz, vp]
-    h.dfm_plane_sweep_bwd_cur_nhwc.restype = ctypes.c_int
-    h.dfm_plane_sweep_bwd_cur_nhwc.argtypes = [dp, vp, fp, fp, fp, fp, fp, vp]
-    h.dfm_plane_sweep_bwd_prev_gather_workspace_bytes.restype = ctypes.c_size_t
-    h.dfm_plane_sweep_bwd_prev_gather_workspace_bytes.argtypes = [dp]
-    h.dfm_plane_sweep_bwd_prev_gather.restype = ctypes.c_int
-    h.dfm_plane_sweep_bwd_prev_gather.argtypes = [dp, vp, fp, fp, fp, fp, fp, vp, sz, vp]
-    h.dfm_plane_sweep_bwd_gather.restype = ctypes.c_int
-    h.dfm_plane_sweep_bwd_gather.argtypes = [dp, i32, vp, i32, fp, fp, fp, fp, fp, i32, vp, sz, vp]
-    h.dfm_plane_sweep_autotune.restype = ctypes.c_int
-    h.dfm_plane_sweep_autotune.argtypes = [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp, op]
-    h.dfm_plane_sweep_tuning.restype = ctypes.c_int
-    h.dfm_plane_sweep_tuning.argtypes = [dp, op]
-    h.dfm_plane_sweep_reset_tuning.restype = None
-    mp = ctypes.POINTER(MvDesc)
-    h.dfm_point_sample_mv_workspace_bytes.restype = sz
-    h.dfm_point_sample_mv_workspace_bytes.argtypes = [mp]
-    h.dfm_point_sample_mv_fwd.restype = ctypes.c_int
-    h.dfm_point_sample_mv_fwd.argtypes = [mp, vp, fp, fp, fp, vp, vp, vp, sz, vp]
-    h.dfm_point_sample_mv_fwd_batched.restype = ctypes.c_int
-    h.dfm_point_sample_mv_fwd_batched.argtypes = [vp, i32, vp, fp, i32, fp, fp, vp, vp, vp]
-    h.dfm_frustum_to_voxel_fwd.restype = ctypes.c_int
-    h.dfm_frustum_to_voxel_fwd.argtypes = [ctypes.POINTER(F2vDesc), vp, vp, vp, fp, fp, vp, vp,
-                                           ctypes.c_size_t, vp]
-    h.dfm_frustum_to_voxel_workspace_bytes.restype = ctypes.c_size_t
-    h.dfm_frustum_to_voxel_workspace_bytes.argtypes = [ctypes.POINTER(F2vDesc)]
-    h.dfm_depth_head_fwd.restype = ctypes.c_int
-    h.dfm_depth_head_fwd.argtypes = [i32, i32, i32, i32, i32, i32, vp, fp, vp, vp, vp, vp]
-    h.dfm_depth_head_stats_fwd.restype = ctypes.c_int
-    h.dfm_depth_head_stats_fwd.argtypes = [i32, i32, i32, i32, i32, i32, vp, fp, fp, fp, vp, vp]
-    h.dfm_frustum_to_voxel_fused_fwd.restype = ctypes.c_int
-    h.dfm_frustum_to_voxel_fused_fwd.argtypes = [ctypes.POINTER(F2vDesc), vp, vp, fp, fp, i32, vp, fp, fp, vp, vp,
-                                                 ctypes.c_size_t, vp]
-    h.dfm_frustum_to_voxel_bwd.restype = ctypes.c_int
-    h.dfm_frustum_to_voxel_bwd.argtypes = [ctypes.POINTER(F2vDesc), vp, vp, fp, fp, fp, fp, vp,
-                                           ctypes.c_size_t, vp]
-    h.dfm_frustum_to_voxel_fused_bwd.restype = ctypes.c_int
-    h.dfm_frustum_to_voxel_fused_bwd.argtypes = [ctypes.POINTER(F2vDesc), vp, vp, fp, fp, i32, fp, fp, fp, fp, vp,
-                                                 ctypes.c_size_t, vp]
-    h.dfm_frustum_to_voxel_bwd_gather_workspace_bytes.restype = ctypes.c_size_t
-    h.dfm_frustum_to_voxel_bwd_gather_workspace_bytes.argtypes = [ctypes.POINTER(F2vDesc)]
-    h.dfm_frustum_to_voxel_bwd_gather.restype = ctypes.c_int
-    h.dfm_frustum_to_voxel_bwd_gather.argtypes = [ctypes.POINTER(F2vDesc), vp, vp, vp, fp, fp, i32, fp,
-                                                  ctypes.POINTER(ctypes.c_float), fp, fp, fp, vp, sz, vp]
-    h.dfm_frustum_to_voxel_bwd_gather_cl.restype = ctypes.c_int
-    h.dfm_frustum_to_voxel_bwd_gather_cl.argtypes = [ctypes.POINTER(F2vDesc), vp, vp, vp, fp, fp, i32, fp,
-                                                     ctypes.POINTER(ctypes.c_float), fp, vp, fp, vp, sz, vp]
-    h.dfm_frustum_to_voxel_bwd_workspace_bytes.restype = ctypes.c_size_t
-    h.dfm_frustum_to_voxel_bwd_workspace_bytes.argtypes = [ctypes.POINTER(F2vDesc)]
-    h.dfm_point_sample_mv_bwd.restype = ctypes.c_int
-    h.dfm_point_sample_mv_bwd.argtypes = [mp, vp, fp, fp, fp, fp, vp, sz, vp]
-    h.dfm_point_sample_mv_bwd_workspace_bytes.restype = sz
-    h.dfm_point_sample_mv_bwd_workspace_bytes.argtypes = [mp]
-    h.dfm_depth_head_bwd.restype = ctypes.c_int
-    h.dfm_depth_head_bwd.argtypes = [i32, i32, i32, i32, i32, i32, vp, fp, vp, vp, vp, fp, vp]
-    h.dfm_sweep_conv_weight_bytes.restype = sz
-    h.dfm_sweep_conv_pack_weights.restype = ctypes.c_int
-    h.dfm_sweep_conv_pack_weights.argtypes = [vp, vp, i32, vp, vp]
-    h.dfm_sweep_conv_stats_splits.restype = ctypes.c_int
-    h.dfm_sweep_conv_stats_splits.argtypes = [dp, i32]
-    h.dfm_sweep_conv_fwd.restype = ctypes.c_int
-    h.dfm_sweep_conv_fwd.argtypes = [dp, vp, vp, fp, fp, fp, fp, vp, vp, vp, fp, fp, i32, vp]
-    h.dfm_cost_gate_fwd.restype = ctypes.c_int
-    h.dfm_cost_gate_fwd.argtypes = [i32, i32, ctypes.c_int64, i32, vp, vp, vp, vp, vp]
-    h.dfm_cost_gate_weight_bytes.restype = sz
-    h.dfm_cost_gate_weight_bytes.argtypes = [i32]
-    h.dfm_cost_gate_pack_weights.restype = ctypes.c_int
-    h.dfm_cost_gate_pack_weights.argtypes = [vp, i32, i32, vp, vp]
-    h.dfm_conv3d_k3_c32_weight_bytes.restype = sz
-    h.dfm_conv3d_k3_c32_pack_weights.restype = ctypes.c_int
-    h.dfm_conv3d_k3_c32_pack_weights.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    h.dfm_conv3d_k3_c32_fwd.restype = ctypes.c_int
-    h.dfm_conv3d_k3_c32_fwd.argtypes = [i32, i32, i32, i32, vp, vp, fp, vp, i32, i32, i32, fp, vp]
-    h.dfm_conv3d_k3_c32_fwd_slices.restype = ctypes.c_int
-    h.dfm_conv3d_k3_c32_fwd_slices.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp]
-    h.dfm_conv3d_k3_c32_fwd_strided.restype = ctypes.c_int
-    h.dfm_conv3d_k3_c32_fwd_strided.argtypes = [i32, i32, i32, i32, vp, i32, vp, fp, vp, i32, i32, i32, fp, vp]
-    h.dfm_conv3d_k3_c32_to1_fwd.restype = ctypes.c_int
-    h.dfm_conv3d_k3_c32_to1_fwd.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]
-    h.dfm_group_norm_coefficients.restype = ctypes.c_int
-    h.dfm_group_norm_coefficients.argtypes = [i32, i32, i32, ctypes.c_float, vp, i32, vp, vp, vp, vp]
-    h.dfm_conv3d_to1_bwd_data.restype = ctypes.c_int
-    h.dfm_conv3d_to1_bwd_data.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp]
-    h.dfm_conv3d_to1_wgrad_workspace_bytes.restype = sz
-    h.dfm_conv3d_to1_wgrad_workspace_bytes.argtypes = []
-    h.dfm_conv3d_to1_wgrad.restype = ctypes.c_int
-    h.dfm_conv3d_to1_wgrad.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, vp, sz, vp]
-    h.dfm_conv3d_to1_norm_fwd.restype = ctypes.c_int
-    h.dfm_conv3d_to1_norm_fwd.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp]
-    h.dfm_cost_gate_mfma_weight_bytes.restype = sz
-    h.dfm_cost_gate_mfma_weight_bytes.argtypes = [i32]
-    h.dfm_cost_gate_mfma_pack_weights.restype = ctypes.c_int
-    h.dfm_cost_gate_mfma_pack_weights.argtypes = [vp, i32, i32, vp, vp]
-    h.dfm_cost_gate_mfma_fwd.restype = ctypes.c_int
-    h.dfm_cost_gate_mfma_fwd.argtypes = [i32, i32, ctypes.c_int64, vp, vp, vp, vp, vp]
-    h.dfm_bilinear_resize_bwd_nhwc.restype = ctypes.c_int
-    h.dfm_bilinear_resize_bwd_nhwc.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, fp, i32, vp, fp, i32, vp, vp]
-    for fn in (h.dfm_depth_pool_fwd, h.dfm_depth_pool_bwd):
-        fn.restype = ctypes.c_int
-        fn.argtypes = [ctypes.c_int64, i32, ctypes.c_int64, i32, vp, vp, vp]
-    h.dfm_conv3d_k3_c32_stats_splits.restype = ctypes.c_int
-    h.dfm_conv3d_k3_c32_stats_splits.argtypes = [i32, i32, i32, i32, i32]
-    cp = ctypes.POINTER(Conv3dDesc)
-    h.dfm_conv3d_g_weight_bytes.restype = sz
-    h.dfm_conv3d_g_weight_bytes.argtypes = [i32, i32]
-    h.dfm_conv3d_g_pack_weights.restype = ctypes.c_int
-    h.dfm_conv3d_g_pack_weights.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
-    h.dfm_conv3d_g_pack_weights_2d.restype = ctypes.c_int
-    h.dfm_conv3d_g_pack_weights_2d.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
-    h.dfm_conv3d_g_fwd.restype = ctypes.c_int
-    h.dfm_conv3d_g_fwd.argtypes = [cp, vp, vp, fp, fp, vp, vp, vp]
-    h.dfm_conv3d_g_fwd_f32.restype = ctypes.c_int
-    h.dfm_conv3d_g_fwd_f32.argtypes = [cp, vp, vp, vp, vp, vp]
-    h.dfm_conv3d_g_plan.restype = ctypes.c_int
-    h.dfm_conv3d_g_plan.argtypes = [cp, ctypes.POINTER(ctypes.c_int64)]
-    wp = ctypes.POINTER(Conv3dWgradDesc)
-    h.dfm_conv3d_wgrad_workspace_bytes.restype = sz
-    h.dfm_conv3d_wgrad_workspace_bytes.argtypes = [wp]
-    h.dfm_conv3d_wgrad_to.restype = ctypes.c_int
-    h.dfm_conv3d_wgrad_to.argtypes = [wp, vp, vp, vp, i32, vp, sz, vp]
-    h.dfm_conv3d_wgrad.restype = ctypes.c_int
-    h.dfm_conv3d_wgrad.argtypes = [wp, vp, vp, fp, vp, sz, vp]
-    lp = ctypes.POINTER(DepthLossDesc)
-    h.dfm_depth_loss_fwd.restype = ctypes.c_int
-    h.dfm_depth_loss_fwd.argtypes = [lp, vp, fp, fp, fp, vp, vp]
-    h.dfm_depth_loss_bwd.restype = ctypes.c_int
-    h.dfm_depth_loss_bwd.argtypes = [lp, vp, fp, fp, fp, vp, vp]
-    h.dfm_depth_loss_fused_fwd.restype = ctypes.c_int
-    h.dfm_depth_loss_fused_fwd.argtypes = [lp, vp, i32, fp, fp, fp, vp, vp]
-    h.dfm_depth_loss_fused_bwd.restype = ctypes.c_int
-    h.dfm_depth_loss_fused_bwd.argtypes = [lp, vp, i32, fp, fp, fp, fp, vp]
-    h.dfm_voxel_sample_fwd.restype = ctypes.c_int
-    h.dfm_voxel_sample_fwd.argtypes = [ctypes.POINTER(VsDesc), vp, fp, vp, vp]
-    h.dfm_voxel_sample_bwd.restype = ctypes.c_int
-    h.dfm_voxel_sample_bwd.argtypes = [ctypes.POINTER(VsDesc), vp, fp, fp, vp]
-    h.dfm_voxel_sample_mv_fwd.restype = ctypes.c_int
-    h.dfm_voxel_sample_mv_fwd.argtypes = [ctypes.POINTER(VsMvDesc), fp, vp, fp, vp, vp]
-    h.dfm_voxel_sample_mv_bwd.restype = ctypes.c_int
-    h.dfm_voxel_sample_mv_bwd.argtypes = [ctypes.POINTER(VsMvDesc), fp, vp, fp, fp, vp]
-    h.dfm_spp_tail_workspace_bytes.restype = ctypes.c_size_t
-    h.dfm_spp_tail_workspace_bytes.argtypes = [ctypes.POINTER(SppDesc)]
-    h.dfm_spp_tail_fwd.restype = ctypes.c_int
-    pp = ctypes.POINTER(ctypes.c_void_p)
-    h.dfm_spp_tail_fwd.argtypes = [ctypes.POINTER(SppDesc), pp, pp, pp, pp, pp, vp, vp, sz, vp]
-    i64, f32 = ctypes.c_int64, ctypes.c_float
-    h.dfm_group_norm_workspace_bytes.restype = sz
-    h.dfm_group_norm_workspace_bytes.argtypes = [i32, i32, i64, i32]
-    h.dfm_group_norm_fwd.restype = ctypes.c_int
-    h.dfm_group_norm_fwd.argtypes = [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, fp, vp, sz, vp]
-    h.dfm_group_norm_fwd_channels_last.restype = ctypes.c_int
-    h.dfm_group_norm_fwd_channels_last.argtypes = h.dfm_group_norm_fwd.argtypes
-    h.dfm_group_norm_apply_channels_last.restype = ctypes.c_int
-    h.dfm_group_norm_apply_channels_last.argtypes = [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, fp, fp,
-                                                     i32, vp, sz, vp]
-    h.dfm_group_norm_fwd_channels_last_res.restype = ctypes.c_int
-    h.dfm_group_norm_fwd_channels_last_res.argtypes = [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, vp, fp, fp,
-                                                       vp, sz, vp]
-    h.dfm_group_norm_apply_channels_last_res.restype = ctypes.c_int
-    h.dfm_group_norm_apply_channels_last_res.argtypes = [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, vp, fp,
-                                                         fp, fp, i32, vp, sz, vp]
-    h.dfm_group_norm_bwd.restype = ctypes.c_int
-    h.dfm_group_norm_bwd.argtypes = [i32, i32, i64, i32, i32, i32, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp, sz,
-                                     vp]
-    h.dfm_group_norm_bwd_channels_last_xmask.restype = ctypes.c_int
-    h.dfm_group_norm_bwd_channels_last_xmask.argtypes = [i32, i32, i64, i32, i32, vp, vp, fp, fp, fp, fp, vp, fp, fp, vp, sz, vp]
-    h.dfm_group_norm_bwd_channels_last.restype = ctypes.c_int
-    h.dfm_group_norm_bwd_channels_last.argtypes = [i32, i32, i64, i32, i32, i32, vp, vp, vp, fp, fp, fp, vp, vp, fp,
-                                                   fp, vp, sz, vp]
-    h.dfm_batch_norm_workspace_bytes.restype = sz
-    h.dfm_batch_norm_workspace_bytes.argtypes = [i32, i64]
-    h.dfm_batch_norm_stats_channels_last.restype = ctypes.c_int
-    h.dfm_batch_norm_stats_channels_last.argtypes = [i32, i64, i32, vp, fp, vp, sz, vp]
-    h.dfm_batch_norm_apply_gathered_channels_last.restype = ctypes.c_int
-    h.dfm_batch_norm_apply_gathered_channels_last.argtypes = [i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, vp, fp,
-                                                              fp, fp, vp]
-    h.dfm_batch_norm_bwd_reduce_channels_last.restype = ctypes.c_int
-    h.dfm_batch_norm_bwd_reduce_channels_last.argtypes = [i32, i64, i32, i32, vp, vp, vp, fp, fp, fp, fp, fp, vp, sz,
-                                                          vp]
-    h.dfm_batch_norm_bwd_apply_channels_last.restype = ctypes.c_int
-    h.dfm_batch_norm_bwd_apply_channels_last.argtypes = [i32, i64, i32, i32, vp, vp, vp, fp, fp, fp, fp, fp, fp, vp,
-                                                         vp, vp, sz, vp]
-    ip = ctypes.POINTER(ImitationDesc)
-    h.dfm_imitation_loss_workspace_bytes.restype = sz
-    h.dfm_imitation_loss_workspace_bytes.argtypes = [ip]
-    h.dfm_imitation_loss_fwd.restype = ctypes.c_int
-    h.dfm_imitation_loss_fwd.argtypes = [ip, vp, vp, fp, fp, fp, fp, fp, vp, vp, vp, sz, vp]
-    h.dfm_imitation_loss_bwd.restype = ctypes.c_int
-    h.dfm_imitation_loss_bwd.argtypes = [ip, vp, vp, vp, fp, fp, fp, vp, vp]
-    h.dfm_box_nms_workspace_bytes.restype = sz
-    h.dfm_box_nms_workspace_bytes.argtypes = [i32, i32]
-    h.dfm_box_nms_rotated.restype = ctypes.c_int
-    h.dfm_box_nms_rotated.argtypes = [fp, i32, i32, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp]
-    h.dfm_box_nms_aligned.restype = ctypes.c_int
-    h.dfm_box_nms_aligned.argtypes = [fp, i32, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp]
-    h.dfm_box_iou_rotated.restype = ctypes.c_int
-    h.dfm_box_iou_rotated.argtypes = [fp, i32, fp, i32, i32, fp, vp]
-    h.dfm_diff_iou_rotated.restype = ctypes.c_int
-    h.dfm_diff_iou_rotated.argtypes = [fp, fp, i32, i32, fp, fp, fp, vp]
-    h.dfm_iou3d_loss_from_deltas.restype = ctypes.c_int
-    h.dfm_iou3d_loss_from_deltas.argtypes = [fp, fp, fp, vp, i32, i32, i32, fp, fp, vp]
-    h.dfm_nearest_bev_overlaps.restype = ctypes.c_int
-    h.dfm_nearest_bev_overlaps.argtypes = [fp, i32, fp, i32, i32, i32, i32, fp, vp]
-    h.dfm_anchor_target_workspace_bytes.restype = sz
-    h.dfm_anchor_target_workspace_bytes.argtypes = [i32, i32]
-    h.dfm_anchor_target_3d.restype = ctypes.c_int
-    h.dfm_anchor_target_3d.argtypes = [ctypes.POINTER(AnchorTargetDesc), fp, fp, vp, ctypes.POINTER(ctypes.c_int32),
-                                       vp, fp, fp, fp, vp, fp, vp, vp, sz, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(h, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = h
     return h
 

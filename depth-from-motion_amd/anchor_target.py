@@ -24,7 +24,7 @@ import torch
 
 from . import _capi
 from .conv3d import MfmaPathError, module_fallback_policy
-from .plane_sweep import _Workspace, _ptr, _require_gpu, _stream_ptr
+from ._launch import STREAM, WS, launch, require_gpu
 from .registry import register_module
 
 __all__ = ['bbox_overlaps_nearest_3d', 'BboxOverlapsNearest3D', 'anchor_target_3d', 'HipAnchorTrainMixin']
@@ -42,8 +42,8 @@ def bbox_overlaps_nearest_3d(bboxes1, bboxes2, mode='iou', is_aligned=False, coo
     function's signature, iou3d_calculator.py:99-145).  ``coordinate`` only selects the box class in the
     reference; the nearest-BEV box is the same for all three."""
     assert coordinate in ['camera', 'lidar', 'depth']
-    _require_gpu(bboxes1, 'bboxes1')
-    _require_gpu(bboxes2, 'bboxes2')
+    require_gpu(bboxes1, 'bboxes1')
+    require_gpu(bboxes2, 'bboxes2')
     if mode not in ('iou', 'iof'):
         raise ValueError(f"mode must be 'iou' or 'iof', got {mode!r}")
     if bboxes1.dim() != 2 or bboxes2.dim() != 2 or not bboxes1.size(-1) == bboxes2.size(-1) >= 7:
@@ -56,10 +56,8 @@ def bbox_overlaps_nearest_3d(bboxes1, bboxes2, mode='iou', is_aligned=False, coo
     out = torch.empty((n,) if is_aligned else (n, m), dtype=torch.float32, device=device)
     if out.numel():
         b1, b2 = _f32(bboxes1), _f32(bboxes2)
-        with torch.cuda.device(device):
-            _capi.check(_capi.lib().dfm_nearest_bev_overlaps(
-                _ptr(b1), n, _ptr(b2), m, width, _capi.OVERLAP_IOF if mode == 'iof' else _capi.OVERLAP_IOU,
-                int(bool(is_aligned)), _ptr(out), _stream_ptr(device)))
+        launch('dfm_nearest_bev_overlaps', b1, n, b2, m, width,
+               _capi.OVERLAP_IOF if mode == 'iof' else _capi.OVERLAP_IOU, int(bool(is_aligned)), out, STREAM)
     return out
 
 
@@ -108,7 +106,7 @@ def _assigner_fields(assigners):
 def _gt_tensor(boxes, device):
     if not torch.is_tensor(boxes):
         boxes = boxes.tensor
-    _require_gpu(boxes, 'gt_bboxes')
+    require_gpu(boxes, 'gt_bboxes')
     return _f32(boxes.to(device)).view(-1, boxes.shape[-1] if boxes.dim() > 1 else 7)
 
 
@@ -129,7 +127,7 @@ def anchor_target_3d(anchors, gt_bboxes_list, gt_labels_list, assigners, *, num_
     image, on the device.  Nothing is copied to the host.  A setting the kernel does not cover (an ignore
     threshold with ignore boxes, a tuple ``neg_iou_thr``, boxes that are not 7 wide, another sampler) raises
     ``DfmHipError`` from the C entry."""
-    _require_gpu(anchors, 'anchors')
+    require_gpu(anchors, 'anchors')
     device = anchors.device
     f = _assigner_fields(assigners)
     if anchors.dim() < 3:
@@ -156,7 +154,7 @@ def anchor_target_3d(anchors, gt_bboxes_list, gt_labels_list, assigners, *, num_
     has_labels = gt_labels_list is not None
     if has_labels:
         for g, l in zip(gts, gt_labels_list):
-            _require_gpu(l, 'gt_labels')
+            require_gpu(l, 'gt_labels')
             if l.shape[0] != g.shape[0]:
                 raise ValueError('one label per GT box')
     tuple_neg = any(isinstance(v, (tuple, list)) for v in f['neg'])
@@ -193,14 +191,9 @@ def anchor_target_3d(anchors, gt_bboxes_list, gt_labels_list, assigners, *, num_
         if has_labels and total:
             gl = torch.cat([l.detach().to(device=device, dtype=torch.int64).view(-1)
                             for l in gt_labels_list[b0:b0 + nb]]).contiguous()
-        with torch.cuda.device(device):
-            nbytes = lib.dfm_anchor_target_workspace_bytes(slots, total)
-            ws = _Workspace.get(device, nbytes) if nbytes else None
-            _capi.check(lib.dfm_anchor_target_3d(
-                ctypes.byref(d), _ptr(a), _ptr(gt) if total else None, _ptr(gl) if gl is not None else None, offsets,
-                _ptr(labels[b0:]), _ptr(label_weights[b0:]), _ptr(bbox_targets[b0:]), _ptr(bbox_weights[b0:]),
-                _ptr(dir_targets[b0:]), _ptr(dir_weights[b0:]), _ptr(counts[b0:]),
-                _ptr(ws) if ws is not None else None, nbytes, _stream_ptr(device)))
+        launch('dfm_anchor_target_3d', d, a, gt if total else None, gl, offsets, labels[b0:], label_weights[b0:],
+               bbox_targets[b0:], bbox_weights[b0:], dir_targets[b0:], dir_weights[b0:], counts[b0:], WS, STREAM,
+               ws_bytes=lib.dfm_anchor_target_workspace_bytes(slots, total))
     return labels, label_weights, bbox_targets, bbox_weights, dir_targets, dir_weights, counts
 
 

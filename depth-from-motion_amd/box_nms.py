@@ -21,7 +21,7 @@ refused: there is no CPU path.
 import torch
 
 from . import _capi
-from .plane_sweep import _Workspace, _ptr, _require_gpu, _stream_ptr
+from ._launch import STREAM, WS, launch, require_gpu
 
 __all__ = ['nms_bev', 'nms_normal_bev', 'box3d_multiclass_nms', 'box_iou_rotated', 'BOX_NMS_MAX_N']
 
@@ -48,20 +48,17 @@ def _launch(boxes, order, counts, thresh, rotated, xyxyr):
     nbytes = lib.dfm_box_nms_workspace_bytes(n, classes)
     if nbytes == 0:
         _capi.check(-1)
-    with torch.cuda.device(device):
-        ws = _Workspace.get(device, nbytes)
-        tail = (_ptr(order), _ptr(counts), n, classes, float(thresh), _ptr(keep), _ptr(kept), _ptr(ws), nbytes,
-                _stream_ptr(device))
-        if rotated:
-            _capi.check(lib.dfm_box_nms_rotated(_ptr(boxes), boxes.shape[0], int(xyxyr), *tail))
-        else:
-            _capi.check(lib.dfm_box_nms_aligned(_ptr(boxes), boxes.shape[0], *tail))
+    tail = (order, counts, n, classes, float(thresh), keep, kept, WS, STREAM)
+    if rotated:
+        launch('dfm_box_nms_rotated', boxes, boxes.shape[0], int(xyxyr), *tail, ws_bytes=nbytes)
+    else:
+        launch('dfm_box_nms_aligned', boxes, boxes.shape[0], *tail, ws_bytes=nbytes)
     return keep, kept
 
 
 def _single(boxes, scores, thresh, rotated, pre_max_size=None, post_max_size=None):
-    _require_gpu(boxes, 'boxes')
-    _require_gpu(scores, 'scores')
+    require_gpu(boxes, 'boxes')
+    require_gpu(scores, 'scores')
     order = torch.sort(scores, dim=0, descending=True, stable=True)[1]
     if pre_max_size is not None:
         order = order[:pre_max_size]
@@ -106,7 +103,7 @@ def box3d_multiclass_nms(mlvl_bboxes, mlvl_bboxes_for_nms, mlvl_scores, score_th
     ``nms_bev`` / ``nms_normal_bev`` once per class on the boolean-indexed candidates, as the reference does."""
     for name, t in (('mlvl_bboxes', mlvl_bboxes), ('mlvl_bboxes_for_nms', mlvl_bboxes_for_nms),
                     ('mlvl_scores', mlvl_scores)):
-        _require_gpu(t, name)
+        require_gpu(t, name)
     assert mlvl_bboxes_for_nms.shape[1] == 5, 'Input boxes shape should be [N, 5]'
     num_classes = mlvl_scores.shape[1] - 1
     total = 0
@@ -161,8 +158,8 @@ def box_iou_rotated(bboxes1, bboxes2, aligned=False):
     corresponding boxes when ``aligned`` (then M == N).  0 when either area is below 1e-14.  The IoU does not
     depend on whether the angle is counted clockwise or counter-clockwise (mirroring both boxes changes
     nothing)."""
-    _require_gpu(bboxes1, 'bboxes1')
-    _require_gpu(bboxes2, 'bboxes2')
+    require_gpu(bboxes1, 'bboxes1')
+    require_gpu(bboxes2, 'bboxes2')
     assert bboxes1.shape[-1] == 5 and bboxes2.shape[-1] == 5, 'boxes must be (N, 5) = (cx, cy, w, h, angle)'
     n, m = bboxes1.shape[0], bboxes2.shape[0]
     if aligned and n != m:
@@ -172,7 +169,5 @@ def box_iou_rotated(bboxes1, bboxes2, aligned=False):
     if n == 0 or m == 0:
         return out
     b1, b2 = _boxes_f32(bboxes1), _boxes_f32(bboxes2)
-    with torch.cuda.device(device):
-        _capi.check(_capi.lib().dfm_box_iou_rotated(_ptr(b1), n, _ptr(b2), m, int(bool(aligned)), _ptr(out),
-                                                    _stream_ptr(device)))
+    launch('dfm_box_iou_rotated', b1, n, b2, m, int(bool(aligned)), out, STREAM)
     return out

@@ -22,8 +22,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _capi
+from ._launch import STREAM, WS, launch, try_launch
 from .derived import Derived, derived, note_derived_build
-from .plane_sweep import _Workspace, _ptr, _stream_ptr
 
 _WDT = {torch.float32: _capi.DFM_F32, torch.bfloat16: _capi.DFM_BF16}
 
@@ -98,10 +98,8 @@ def pack_conv3d_weights(weight, cin_offset=0, transposed=False):
         w = w.float()
     lib = _capi.lib()
     packed = torch.empty(lib.dfm_conv3d_k3_c32_weight_bytes(), dtype=torch.uint8, device=w.device)
-    with torch.cuda.device(w.device):
-        _capi.check(lib.dfm_conv3d_k3_c32_pack_weights(_ptr(w), _WDT[w.dtype], w.shape[1], cin_offset,
-                                                       1 if transposed else 0, _ptr(packed),
-                                                       _stream_ptr(w.device)))
+    launch('dfm_conv3d_k3_c32_pack_weights', w, _WDT[w.dtype], w.shape[1], cin_offset, 1 if transposed else 0, packed,
+           STREAM)
     return packed
 
 
@@ -131,11 +129,8 @@ def conv3d_k3_c32(x, packed, relu=False, acc_in=None, out_f32=False, depth_chunk
         assert not out_f32 and not relu, 'statistics are taken of the plain bf16 output'
         splits = lib.dfm_conv3d_k3_c32_stats_splits(N, D, H, W, depth_chunk)
         part = torch.empty((N, 32, splits, 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check(lib.dfm_conv3d_k3_c32_fwd_strided(
-            N, D, H, W, _ptr(x), cstride, _ptr(packed), _ptr(acc_in) if acc_in is not None else None,
-            _ptr(out), 1 if out_f32 else 0, 1 if relu else 0, depth_chunk,
-            _ptr(part) if part is not None else None, _stream_ptr(dev)))
+    launch('dfm_conv3d_k3_c32_fwd_strided', N, D, H, W, x, cstride, packed, acc_in, out, 1 if out_f32 else 0,
+           1 if relu else 0, depth_chunk, part, STREAM)
     if out_f32:
         return out
     out = out.permute(0, 4, 1, 2, 3)
@@ -174,13 +169,10 @@ class _MfmaConvFn(torch.autograd.Function):
                 # the k halves written straight into the (N, D, H, W, 32 k) gradient (dfm_conv3d_k3_c32_fwd_slices)
                 N, _, D, H, W = gy.shape
                 buf = torch.empty((N, D, H, W, 32 * k), dtype=torch.bfloat16, device=gy.device)
-                lib = _capi.lib()
-                with torch.cuda.device(gy.device):
-                    for i in range(k):
-                        pk = pack_conv3d_weights(weight, 32 * i, transposed=True)
-                        _capi.check(lib.dfm_conv3d_k3_c32_fwd_slices(
-                            N, D, H, W, _ptr(gy), 32, _ptr(pk), buf.data_ptr() + 64 * i, 32 * k, 0, 0,
-                            _stream_ptr(gy.device)))
+                for i in range(k):
+                    pk = pack_conv3d_weights(weight, 32 * i, transposed=True)
+                    launch('dfm_conv3d_k3_c32_fwd_slices', N, D, H, W, gy, 32, pk, buf[..., 32 * i:], 32 * k, 0, 0,
+                           STREAM)
                 gx = buf.permute(0, 4, 1, 2, 3)
         gw = None
         if ctx.needs_input_grad[1]:  # backward-weight: chunked implicit-im2col GEMM (see above)
@@ -348,15 +340,11 @@ def conv3d_weight_grad(x_in, g_out, stride, padding, out_dtype=torch.float32):
         if nbytes:
             direct = out_dtype in (torch.float32, torch.bfloat16)
             out = torch.empty((A, B, 3, 3, 3), dtype=out_dtype if direct else torch.float32, device=x_in.device)
-            ws = _Workspace.get(x_in.device, nbytes)
-            with torch.cuda.device(x_in.device):
-                rc = lib.dfm_conv3d_wgrad_to(ctypes.byref(d), _ptr(g_out), _ptr(x_in), _ptr(out),
-                                             _capi.DFM_BF16 if out.dtype == torch.bfloat16 else _capi.DFM_F32,
-                                             _ptr(ws), nbytes, _stream_ptr(x_in.device))
-            if rc == 0:
+            # (DFM_ERR_UNSUPPORTED: a tile that does not fit the LDS falls through to the GEMM)
+            if try_launch('dfm_conv3d_wgrad_to', d, g_out, x_in, out,
+                          _capi.DFM_BF16 if out.dtype == torch.bfloat16 else _capi.DFM_F32, WS, STREAM,
+                          ws_bytes=nbytes):
                 return out if direct else out.to(out_dtype)
-            if rc != _capi.DFM_ERR_UNSUPPORTED:  # a tile that does not fit the LDS falls through to the GEMM
-                _capi.check(rc)
     if x_in.is_cuda and _POLICY['mode'] == 'raise':
         raise MfmaPathError(f'weight gradient of a {B}->{A} convolution outside the MFMA kernel\'s coverage '
                             '(channels not multiples of 32, layout, or a tile that does not fit the LDS)')
@@ -477,16 +465,13 @@ def conv3d_to1_norm(y, partials, gamma, beta, eps, weight, relu=True, depth_chun
     w = weight.detach().contiguous()
     if w.dtype not in _WDT:
         w = w.float()
-    lib = _capi.lib()
     dev = y.device
     coef = torch.empty((N, 32, 2), dtype=torch.float32, device=dev)
     out = torch.empty((N, 1, D, H, W), dtype=torch.bfloat16, device=dev)
-    with torch.cuda.device(dev):
-        st = _stream_ptr(dev)
-        _capi.check(lib.dfm_group_norm_coefficients(N, 32, 32, float(eps), _ptr(partials), partials.shape[2],
-                                                    _ptr(gamma), _ptr(beta), _ptr(coef), st))
-        _capi.check(lib.dfm_conv3d_to1_norm_fwd(N, D, H, W, _ptr(y), _ptr(coef), _ptr(w), _WDT[w.dtype],
-                                                1 if relu else 0, 0, _ptr(out), int(depth_chunk), st))
+    launch('dfm_group_norm_coefficients', N, 32, 32, float(eps), partials, partials.shape[2], gamma, beta, coef,
+           STREAM)
+    launch('dfm_conv3d_to1_norm_fwd', N, D, H, W, y, coef, w, _WDT[w.dtype], 1 if relu else 0, 0, out,
+           int(depth_chunk), STREAM)
     return out
 
 
@@ -506,9 +491,7 @@ def conv3d_to1(x, weight, depth_chunk=0):
     coef = _identity_coef.get((x.device, N), (), lambda: torch.tensor(
         [1.0, 0.0], dtype=torch.float32, device=x.device).repeat(N * 32).view(N, 32, 2).contiguous())
     out = torch.empty((N, 1, D, H, W), dtype=torch.bfloat16, device=x.device)
-    with torch.cuda.device(x.device):
-        _capi.check(_capi.lib().dfm_conv3d_to1_norm_fwd(N, D, H, W, _ptr(x), _ptr(coef), _ptr(w), _WDT[w.dtype], 0, 0,
-                                                        _ptr(out), int(depth_chunk), _stream_ptr(x.device)))
+    launch('dfm_conv3d_to1_norm_fwd', N, D, H, W, x, coef, w, _WDT[w.dtype], 0, 0, out, int(depth_chunk), STREAM)
     return out
 
 
@@ -523,9 +506,7 @@ class _MfmaConvTo1Fn(torch.autograd.Function):
             return conv3d_to1(x, weight)
         N, _, D, H, W = x.shape
         out = torch.empty((N, 1, D, H, W), dtype=torch.bfloat16, device=x.device)
-        with torch.cuda.device(x.device):
-            _capi.check(_capi.lib().dfm_conv3d_k3_c32_to1_fwd(N, D, H, W, _ptr(x), _ptr(packed), _ptr(out), 0, 0,
-                                                              _stream_ptr(x.device)))
+        launch('dfm_conv3d_k3_c32_to1_fwd', N, D, H, W, x, packed, out, 0, 0, STREAM)
         return out
 
     @staticmethod
@@ -534,25 +515,20 @@ class _MfmaConvTo1Fn(torch.autograd.Function):
         gx = gw = None
         gy = gy.contiguous()
         N, _, D, H, W = gy.shape
-        lib = _capi.lib()
         direct = (gy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and _is_ndhwc(x) and
                   _ndhwc_channel_stride(x) == 32 and weight.dtype in _WDT)
         if direct:
             # round 6 (csrc/conv3d_to1_bwd.hip): both gradients as matrix products over the 27 taps -- no gradient padded
             # to 32 channels (a 118 MB fill + copy), no 32 -> 32 convolution / weight gradient for one useful row
             wc = weight.detach().contiguous()
-            with torch.cuda.device(gy.device):
-                if ctx.needs_input_grad[0]:
-                    gxb = torch.empty((N, D, H, W, 32), dtype=torch.bfloat16, device=gy.device)
-                    _capi.check(lib.dfm_conv3d_to1_bwd_data(N, D, H, W, _ptr(gy), _ptr(wc), _WDT[wc.dtype], _ptr(gxb),
-                                                            _stream_ptr(gy.device)))
-                    gx = gxb.permute(0, 4, 1, 2, 3)
-                if ctx.needs_input_grad[1]:
-                    gw = torch.empty((1, 32, 3, 3, 3), dtype=weight.dtype, device=gy.device)
-                    nbytes = lib.dfm_conv3d_to1_wgrad_workspace_bytes()
-                    ws = _Workspace.get(gy.device, nbytes)
-                    _capi.check(lib.dfm_conv3d_to1_wgrad(N, D, H, W, _ptr(x), _ptr(gy), _ptr(gw), _WDT[gw.dtype],
-                                                         _ptr(ws), nbytes, _stream_ptr(gy.device)))
+            if ctx.needs_input_grad[0]:
+                gxb = torch.empty((N, D, H, W, 32), dtype=torch.bfloat16, device=gy.device)
+                launch('dfm_conv3d_to1_bwd_data', N, D, H, W, gy, wc, _WDT[wc.dtype], gxb, STREAM)
+                gx = gxb.permute(0, 4, 1, 2, 3)
+            if ctx.needs_input_grad[1]:
+                gw = torch.empty((1, 32, 3, 3, 3), dtype=weight.dtype, device=gy.device)
+                launch('dfm_conv3d_to1_wgrad', N, D, H, W, x, gy, gw, _WDT[gw.dtype], WS, STREAM,
+                       ws_bytes=_capi.lib().dfm_conv3d_to1_wgrad_workspace_bytes())
             return gx, gw, None
         g32 = None
         if ctx.needs_input_grad[0]:
@@ -642,10 +618,8 @@ def pack_conv3d_g_weights(weight, cin, cout, swap=False, flip=0):
         w = w.float()
     lib = _capi.lib()
     packed = torch.empty(lib.dfm_conv3d_g_weight_bytes(cin, cout), dtype=torch.uint8, device=w.device)
-    entry = lib.dfm_conv3d_g_pack_weights_2d if two_d else lib.dfm_conv3d_g_pack_weights
-    with torch.cuda.device(w.device):
-        _capi.check(entry(_ptr(w), _WDT[w.dtype], cin, cout, 1 if swap else 0, int(flip), _ptr(packed),
-                          _stream_ptr(w.device)))
+    launch('dfm_conv3d_g_pack_weights_2d' if two_d else 'dfm_conv3d_g_pack_weights', w, _WDT[w.dtype], cin, cout,
+           1 if swap else 0, int(flip), packed, STREAM)
     return packed
 
 
@@ -743,11 +717,7 @@ def conv3d_g(x, packed, cout, stride=1, padding=1, transposed=False, relu=False,
     if residual is not None:
         assert residual.dtype == torch.bfloat16 and tuple(residual.shape) == (N, cout, *out_size) and \
             _is_ndhwc(residual)
-    with torch.cuda.device(x.device):
-        _capi.check(_capi.lib().dfm_conv3d_g_fwd(
-            ctypes.byref(d), _ptr(x), _ptr(packed), _ptr(scale) if scale is not None else None,
-            _ptr(shift) if shift is not None else None, _ptr(residual) if residual is not None else None,
-            _ptr(out), _stream_ptr(x.device)))
+    launch('dfm_conv3d_g_fwd', d, x, packed, scale, shift, residual, out, STREAM)
     return out.permute(0, 4, 1, 2, 3)
 
 
@@ -767,10 +737,7 @@ def conv3d_g_f32(x, packed, cout, stride=1, padding=1, transposed=False, kernel1
     else:
         out = torch.empty((N, *out_size, cout), dtype=torch.float32, device=x.device)
     d = _conv_desc(N, cin, cout, in_size, out_size, stride, padding, transposed, False, cstride, kernel1)
-    with torch.cuda.device(x.device):
-        _capi.check(_capi.lib().dfm_conv3d_g_fwd_f32(ctypes.byref(d), _ptr(x), _ptr(packed),
-                                                     _ptr(acc) if acc is not None else None, _ptr(out),
-                                                     _stream_ptr(x.device)))
+    launch('dfm_conv3d_g_fwd_f32', d, x, packed, acc, out, STREAM)
     return out
 
 

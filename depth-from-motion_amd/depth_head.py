@@ -1,28 +1,22 @@
 """Host-side mirror of ``DepthHead.forward`` with ``with_convs=False``
 (mmdet3d/models/dense_heads/depth_head.py:190-212): one HIP launch
 (``dfm_depth_head_fwd``) instead of Upsample + softmax + weighted sum."""
-import ctypes
-
 import torch
 
 from . import _capi
-from .plane_sweep import _DTYPES, _ptr, _require_gpu, _stream_ptr
+from ._launch import DTYPES, STREAM, launch, require_gpu
 
 
 class _DepthHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ds, s):
-        lib = _capi.lib()
         device = x.device
         B, _, D, H, W = x.shape
         vol = torch.empty((B, 1, s * D, s * H, s * W), dtype=x.dtype, device=device)
         soft = torch.empty_like(vol)
         pred = torch.empty((B, 1, s * H, s * W), dtype=x.dtype, device=device)
-        with torch.cuda.device(device):
-            _capi.check(
-                lib.dfm_depth_head_fwd(B, D, H, W, s, _DTYPES[x.dtype], _ptr(x), _ptr(ds), _ptr(vol),
-                                       _ptr(soft), _ptr(pred), _stream_ptr(device)))
+        launch('dfm_depth_head_fwd', B, D, H, W, s, DTYPES[x.dtype], x, ds, vol, soft, pred, STREAM)
         ctx.save_for_backward(x, ds)
         ctx.s = s
         return vol, soft, pred
@@ -30,24 +24,19 @@ class _DepthHeadFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_vol, g_soft, g_pred):
         x, ds = ctx.saved_tensors
-        lib = _capi.lib()
         device = x.device
         B, _, D, H, W = x.shape
         gs = [None if g is None else g.contiguous().to(x.dtype) for g in (g_vol, g_soft, g_pred)]
         gx = torch.zeros(x.shape, dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            _capi.check(
-                lib.dfm_depth_head_bwd(B, D, H, W, ctx.s, _DTYPES[x.dtype], _ptr(x), _ptr(ds),
-                                       *(None if g is None else _ptr(g) for g in gs), _ptr(gx),
-                                       _stream_ptr(device)))
+        launch('dfm_depth_head_bwd', B, D, H, W, ctx.s, DTYPES[x.dtype], x, ds, *gs, gx, STREAM)
         return gx.to(x.dtype), None, None
 
 
 def depth_head_forward(stereo_features, depth_samples, downsample_factor=4):
     """(B, 1, D, H, W) -> depth_volumes, depth_volumes_softmax (B, 1, sD, sH, sW),
     depth_preds (B, 1, sH, sW).  Differentiable w.r.t. stereo_features."""
-    _require_gpu(stereo_features, 'stereo_features')
-    if stereo_features.dtype not in _DTYPES:
+    require_gpu(stereo_features, 'stereo_features')
+    if stereo_features.dtype not in DTYPES:
         raise TypeError('stereo_features must be float32 or bfloat16')
     assert stereo_features.dim() == 5 and stereo_features.shape[1] == 1, \
         'with_convs=False expects a single-channel cost volume'
@@ -95,8 +84,8 @@ def depth_head_statistics(stereo_features, depth_samples, downsample_factor=4, n
     pass (depth_preds is None): the detector's inference path does not read it.
     ``keep_graph=True`` (training): the distribution remembers ``stereo_features`` as it sits in the
     autograd graph, for ``DepthHead.loss`` (depth_preds itself carries no gradient here)."""
-    _require_gpu(stereo_features, 'stereo_features')
-    if stereo_features.dtype not in _DTYPES:
+    require_gpu(stereo_features, 'stereo_features')
+    if stereo_features.dtype not in DTYPES:
         raise TypeError('stereo_features must be float32 or bfloat16')
     assert stereo_features.dim() == 5 and stereo_features.shape[1] == 1
     x = stereo_features.detach().contiguous()
@@ -107,11 +96,7 @@ def depth_head_statistics(stereo_features, depth_samples, downsample_factor=4, n
     cmax = torch.empty((B, s * H, s * W), dtype=torch.float32, device=x.device)
     csum = torch.empty_like(cmax)
     pred = torch.empty((B, 1, s * H, s * W), dtype=x.dtype, device=x.device) if need_preds else None
-    with torch.cuda.device(x.device):
-        _capi.check(_capi.lib().dfm_depth_head_stats_fwd(B, D, H, W, s, _DTYPES[x.dtype], _ptr(x), _ptr(ds),
-                                                         _ptr(cmax), _ptr(csum),
-                                                         _ptr(pred) if need_preds else None,
-                                                         _stream_ptr(x.device)))
+    launch('dfm_depth_head_stats_fwd', B, D, H, W, s, DTYPES[x.dtype], x, ds, cmax, csum, pred, STREAM)
     return LazyDepthDistribution(x, cmax, csum, ds, s, cost_with_grad=stereo_features if keep_graph else None), pred
 
 
@@ -123,14 +108,11 @@ class _DepthLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, volumes, depth_img, ds, desc):
-        lib = _capi.lib()
         device = volumes.device
         B, D, H, W = volumes.shape
         loss = torch.empty((B, H, W), dtype=torch.float32, device=device)
         valid = torch.empty((B, H, W), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_depth_loss_fwd(ctypes.byref(desc), _ptr(volumes), _ptr(depth_img),
-                                               _ptr(ds), _ptr(loss), _ptr(valid), _stream_ptr(device)))
+        launch('dfm_depth_loss_fwd', desc, volumes, depth_img, ds, loss, valid, STREAM)
         ctx.save_for_backward(volumes, depth_img, ds)
         ctx.desc = desc
         ctx.mark_non_differentiable(valid)
@@ -139,13 +121,9 @@ class _DepthLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_valid):
         volumes, depth_img, ds = ctx.saved_tensors
-        lib = _capi.lib()
-        device = volumes.device
         g = g_loss.contiguous().float()
         gv = torch.empty_like(volumes)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_depth_loss_bwd(ctypes.byref(ctx.desc), _ptr(volumes), _ptr(depth_img),
-                                               _ptr(ds), _ptr(g), _ptr(gv), _stream_ptr(device)))
+        launch('dfm_depth_loss_bwd', ctx.desc, volumes, depth_img, ds, g, gv, STREAM)
         return gv, None, None, None
 
 
@@ -170,7 +148,7 @@ def _loss_desc(B, D, H, W, dtype, depth_samples, loss_type, min_depth, max_depth
     # the host copy of two scalars, not a device sync on the hot tensor
     two = depth_samples[:2].detach().to('cpu', torch.float32)
     d.interval = float(two[1] - two[0])
-    d.dtype = _DTYPES[dtype]
+    d.dtype = DTYPES[dtype]
     return d
 
 
@@ -186,8 +164,8 @@ def depth_distribution_loss(depth_volumes, depth_img, depth_samples, loss_type, 
     if isinstance(depth_volumes, LazyDepthDistribution):
         return fused_depth_distribution_loss(depth_volumes, depth_img, depth_samples, loss_type, min_depth,
                                              max_depth, alpha, gamma)
-    _require_gpu(depth_volumes, 'depth_volumes')
-    if depth_volumes.dtype not in _DTYPES:
+    require_gpu(depth_volumes, 'depth_volumes')
+    if depth_volumes.dtype not in DTYPES:
         raise TypeError('depth_volumes must be float32 or bfloat16')
     vol = depth_volumes.contiguous()
     B, D, H, W = vol.shape
@@ -207,15 +185,12 @@ class _FusedDepthLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cost, depth_img, ds, desc, scale):
-        lib = _capi.lib()
         device = cost.device
         x = cost.contiguous()
         B, H, W = desc.batch, desc.h, desc.w
         loss = torch.empty((B, H, W), dtype=torch.float32, device=device)
         valid = torch.empty((B, H, W), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_depth_loss_fused_fwd(ctypes.byref(desc), _ptr(x), scale, _ptr(depth_img), _ptr(ds),
-                                                     _ptr(loss), _ptr(valid), _stream_ptr(device)))
+        launch('dfm_depth_loss_fused_fwd', desc, x, scale, depth_img, ds, loss, valid, STREAM)
         ctx.save_for_backward(x, depth_img, ds)
         ctx.desc, ctx.scale = desc, scale
         ctx.mark_non_differentiable(valid)
@@ -224,13 +199,10 @@ class _FusedDepthLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_valid):
         x, depth_img, ds = ctx.saved_tensors
-        lib = _capi.lib()
         device = x.device
         g = g_loss.contiguous().float()
         gx = torch.zeros(x.shape, dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_depth_loss_fused_bwd(ctypes.byref(ctx.desc), _ptr(x), ctx.scale, _ptr(depth_img),
-                                                     _ptr(ds), _ptr(g), _ptr(gx), _stream_ptr(device)))
+        launch('dfm_depth_loss_fused_bwd', ctx.desc, x, ctx.scale, depth_img, ds, g, gx, STREAM)
         return gx.to(x.dtype), None, None, None, None
 
 
@@ -240,7 +212,7 @@ def fused_depth_distribution_loss(dist, depth_img, depth_samples, loss_type, min
     bit-identical to the loss on the materialised ``depth_volumes``; differentiable w.r.t.
     ``dist.cost_with_grad``."""
     cost = dist.cost_with_grad if dist.cost_with_grad is not None else dist.cost
-    _require_gpu(cost, 'cost')
+    require_gpu(cost, 'cost')
     B, _, sD, sH, sW = dist.shape
     img = depth_img.to(device=cost.device, dtype=torch.float32).contiguous()
     assert img.shape == (B, sH, sW), (img.shape, dist.shape)

@@ -9,10 +9,10 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._launch import DTYPES, STREAM, WS, launch, require_gpu, try_launch, upload
 from .derived import Derived
 from .depth_head import LazyDepthDistribution
 from .geometry import stack_meta
-from .plane_sweep import _DTYPES, _Workspace, _ptr, _require_gpu, _stream_ptr, _upload
 
 
 class _F2vFn(torch.autograd.Function):
@@ -20,17 +20,9 @@ class _F2vFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, stereo, sem, soft, coords, cam4, desc):
         lib = _capi.lib()
-        device = stereo.device
         out = _alloc_out(desc, stereo)
         nbytes = lib.dfm_frustum_to_voxel_workspace_bytes(ctypes.byref(desc))
-        ws = _Workspace.get(device, nbytes)
-        with torch.cuda.device(device):
-            _capi.check(
-                lib.dfm_frustum_to_voxel_fwd(ctypes.byref(desc), _ptr(stereo),
-                                             _ptr(soft) if soft is not None else None,
-                                             _ptr(sem) if sem is not None else None, _ptr(coords),
-                                             _ptr(cam4), _ptr(out), _ptr(ws), nbytes,
-                                             _stream_ptr(device)))
+        launch('dfm_frustum_to_voxel_fwd', desc, stereo, soft, sem, coords, cam4, out, WS, STREAM, ws_bytes=nbytes)
         ctx.desc = desc
         ctx.has_sem = sem is not None
         ctx.shapes = (stereo.shape, None if sem is None else sem.shape, stereo.dtype)
@@ -52,14 +44,7 @@ class _F2vFn(torch.autograd.Function):
             return g_st.to(dtype), (g_sem.to(dtype) if g_sem is not None else None), None, None, None, None
         g_st = torch.zeros(st_shape, dtype=torch.float32, device=device)
         nbytes = lib.dfm_frustum_to_voxel_bwd_workspace_bytes(ctypes.byref(desc))
-        ws = _Workspace.get(device, nbytes)
-        with torch.cuda.device(device):
-            _capi.check(
-                lib.dfm_frustum_to_voxel_bwd(ctypes.byref(desc), _ptr(go),
-                                             _ptr(soft) if soft is not None else None, _ptr(coords),
-                                             _ptr(cam4), _ptr(g_st),
-                                             _ptr(g_sem) if g_sem is not None else None, _ptr(ws),
-                                             nbytes, _stream_ptr(device)))
+        launch('dfm_frustum_to_voxel_bwd', desc, go, soft, coords, cam4, g_st, g_sem, WS, STREAM, ws_bytes=nbytes)
         return g_st.to(dtype), (g_sem.to(dtype) if g_sem is not None else None), None, None, None, None
 
 
@@ -72,15 +57,10 @@ class _F2vFusedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, stereo, sem, cost, col_max, col_sum, scale, coords, cam4, desc):
         lib = _capi.lib()
-        device = stereo.device
         out = _alloc_out(desc, stereo)
         nbytes = lib.dfm_frustum_to_voxel_workspace_bytes(ctypes.byref(desc))
-        ws = _Workspace.get(device, nbytes)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_frustum_to_voxel_fused_fwd(
-                ctypes.byref(desc), _ptr(stereo), _ptr(cost), _ptr(col_max), _ptr(col_sum), scale,
-                _ptr(sem) if sem is not None else None, _ptr(coords), _ptr(cam4), _ptr(out), _ptr(ws), nbytes,
-                _stream_ptr(device)))
+        launch('dfm_frustum_to_voxel_fused_fwd', desc, stereo, cost, col_max, col_sum, scale, sem, coords, cam4, out,
+               WS, STREAM, ws_bytes=nbytes)
         ctx.desc, ctx.scale = desc, scale
         ctx.has_sem = sem is not None
         ctx.shapes = (stereo.shape, None if sem is None else sem.shape, stereo.dtype)
@@ -104,12 +84,8 @@ class _F2vFusedFn(torch.autograd.Function):
                     None, None)
         g_st = torch.zeros(st_shape, dtype=torch.float32, device=device)
         nbytes = lib.dfm_frustum_to_voxel_bwd_workspace_bytes(ctypes.byref(bdesc))
-        ws = _Workspace.get(device, nbytes)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_frustum_to_voxel_fused_bwd(
-                ctypes.byref(bdesc), _ptr(go), _ptr(cost), _ptr(col_max), _ptr(col_sum), ctx.scale, _ptr(coords),
-                _ptr(cam4), _ptr(g_st), _ptr(g_sem) if g_sem is not None else None, _ptr(ws), nbytes,
-                _stream_ptr(device)))
+        launch('dfm_frustum_to_voxel_fused_bwd', bdesc, go, cost, col_max, col_sum, ctx.scale, coords, cam4, g_st,
+               g_sem, WS, STREAM, ws_bytes=nbytes)
         return (g_st.to(dtype), (g_sem.to(dtype) if g_sem is not None else None), None, None, None, None, None,
                 None, None)
 
@@ -179,27 +155,20 @@ def _try_gather_backward(desc, go, soft, fused, scale, coords, cam4, st_shape, d
     grid = _regular_grid(coords, desc)
     if grid is None:
         return None
-    lib = _capi.lib()
-    nbytes = lib.dfm_frustum_to_voxel_bwd_gather_workspace_bytes(ctypes.byref(desc))
-    ws = _Workspace.get(device, nbytes)
+    nbytes = _capi.lib().dfm_frustum_to_voxel_bwd_gather_workspace_bytes(ctypes.byref(desc))
     g6 = (ctypes.c_float * 6)(*grid)
     cost, cmax, csum = fused if fused is not None else (None, None, None)
     native = bool(desc.stereo_channels_last) and _BWD_GATHER['native']
     if native:
         B, C, D, H, W = st_shape
         g_st = torch.empty((B, D, H, W, C), dtype=dtype, device=device).permute(0, 4, 1, 2, 3)
-        entry = lib.dfm_frustum_to_voxel_bwd_gather_cl
+        entry = 'dfm_frustum_to_voxel_bwd_gather_cl'
     else:
         g_st = torch.empty(st_shape, dtype=torch.float32, device=device)
-        entry = lib.dfm_frustum_to_voxel_bwd_gather
-    with torch.cuda.device(device):
-        rc = entry(ctypes.byref(desc), _ptr(go), _ptr(soft) if soft is not None else None,
-                   _ptr(cost) if cost is not None else None, _ptr(cmax) if cmax is not None else None,
-                   _ptr(csum) if csum is not None else None, int(scale), _ptr(coords), g6, _ptr(cam4), _ptr(g_st),
-                   _ptr(g_sem) if g_sem is not None else None, _ptr(ws), nbytes, _stream_ptr(device))
-    if rc == _capi.DFM_ERR_UNSUPPORTED:
+        entry = 'dfm_frustum_to_voxel_bwd_gather'
+    if not try_launch(entry, desc, go, soft, cost, cmax, csum, int(scale), coords, g6, cam4, g_st, g_sem, WS, STREAM,
+                      ws_bytes=nbytes):
         return None
-    _capi.check(rc)
     _BWD_GATHER['calls'] = _BWD_GATHER.get('calls', 0) + 1   # (tests read it: which form took the call)
     return g_st
 
@@ -241,10 +210,10 @@ def frustum_to_voxel_sample(stereo_feat, stereo_feat_softmax, img_metas, cur_sem
     Returns:
         (B, C + Cs, Nz, Ny, Nx), same dtype as stereo_feat
     """
-    _require_gpu(stereo_feat, 'stereo_feat')
+    require_gpu(stereo_feat, 'stereo_feat')
     lib = _capi.lib()
     device = stereo_feat.device
-    if stereo_feat.dtype not in _DTYPES:
+    if stereo_feat.dtype not in DTYPES:
         raise TypeError('stereo_feat must be float32 or bfloat16')
     # a channels_last_3d cost volume (NDHWC conv stack) is sampled where it lies: it IS the
     # pixel-major layout the kernel stages an NCDHW volume into
@@ -290,12 +259,12 @@ def frustum_to_voxel_sample(stereo_feat, stereo_feat_softmax, img_metas, cur_sem
     desc.pad_h, desc.pad_w = float(pad_shape[0]), float(pad_shape[1])
     desc.depth_min = float(depth_cfg['depth_min'])
     desc.depth_span = float(depth_cfg['depth_max'] - depth_cfg['depth_min'])
-    desc.dtype = _DTYPES[stereo.dtype]
+    desc.dtype = DTYPES[stereo.dtype]
     cam = stack_meta(img_metas, 'cam2img')  # (staged on the device by stage_geometry: padded where it lies)
     cam4 = torch.eye(4, device=cam.device).repeat(B, 1, 1)
     cam4[:, :cam.shape[1], :cam.shape[2]] = cam
     cam4 = cam4.reshape(B, 16).contiguous() if cam.is_cuda and cam.device == device else \
-        _upload(cam4.cpu().reshape(B, 16), device)
+        upload(cam4.cpu().reshape(B, 16), device)
     if lazy is not None and torch.is_grad_enabled() and (stereo.requires_grad or
                                                          (sem is not None and sem.requires_grad)):
         # training with the depth head fused (the backward ignores the input layouts, like _F2vFn's)
@@ -305,11 +274,7 @@ def frustum_to_voxel_sample(stereo_feat, stereo_feat_softmax, img_metas, cur_sem
         lib = _capi.lib()
         out = _alloc_out(desc, stereo)
         nbytes = lib.dfm_frustum_to_voxel_workspace_bytes(ctypes.byref(desc))
-        ws = _Workspace.get(device, nbytes)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_frustum_to_voxel_fused_fwd(
-                ctypes.byref(desc), _ptr(stereo.detach()), _ptr(lazy.cost), _ptr(lazy.col_max),
-                _ptr(lazy.col_sum), lazy.scale, _ptr(sem.detach()) if sem is not None else None, _ptr(coords), _ptr(cam4), _ptr(out),
-                _ptr(ws), nbytes, _stream_ptr(device)))
+        launch('dfm_frustum_to_voxel_fused_fwd', desc, stereo, lazy.cost, lazy.col_max, lazy.col_sum, lazy.scale, sem,
+               coords, cam4, out, WS, STREAM, ws_bytes=nbytes)
         return out
     return _F2vFn.apply(stereo, sem, soft, coords, cam4, desc)

@@ -6,14 +6,12 @@ GroupNorm kernel followed by a separate ReLU.
 ``state_dict`` keys), so it drops into ``ConvModule`` / ``hourglass`` without
 touching checkpoints.
 """
-import ctypes
-
 import torch
 from torch import nn
 
 from . import _capi
 from .derived import Derived
-from .plane_sweep import _DTYPES, _Workspace, _ptr, _stream_ptr
+from ._launch import DTYPES, STREAM, WS, launch, nonempty
 
 
 _f32_cache = Derived(capacity=1024)
@@ -52,28 +50,22 @@ class _GroupNormFn(torch.autograd.Function):
         rstd = torch.empty_like(mean)
         w32, b32 = _f32_params(weight, bias)
         nbytes = lib.dfm_group_norm_workspace_bytes(n, c, spatial, groups)
-        ws = _Workspace.get(device, nbytes)
-        fn = lib.dfm_group_norm_fwd_channels_last if cl else lib.dfm_group_norm_fwd
         fused_res = residual is not None and cl and residual.dtype == x.dtype and \
             residual.shape == x.shape and residual.stride() == x.stride()
-        rp = _ptr(residual) if fused_res else None
-        with torch.cuda.device(device):
-            if partials is not None:
-                # statistics came from the producer (MFMA conv epilogue): normalisation pass only
-                assert cl and partials.shape[:2] == (n, groups) and partials.is_contiguous()
-                _capi.check(lib.dfm_group_norm_apply_channels_last_res(
-                    n, c, spatial, groups, eps, _DTYPES[x.dtype], int(relu and (fused_res or residual is None)),
-                    _ptr(x), _ptr(w32), _ptr(b32), rp, _ptr(y), _ptr(mean), _ptr(rstd), _ptr(partials),
-                    partials.shape[2], _ptr(ws), nbytes, _stream_ptr(device)))
-            elif cl:
-                _capi.check(lib.dfm_group_norm_fwd_channels_last_res(
-                    n, c, spatial, groups, eps, _DTYPES[x.dtype], int(relu and (fused_res or residual is None)),
-                    _ptr(x), _ptr(w32), _ptr(b32), rp, _ptr(y), _ptr(mean), _ptr(rstd), _ptr(ws), nbytes,
-                    _stream_ptr(device)))
-            else:
-                _capi.check(fn(n, c, spatial, groups, eps, _DTYPES[x.dtype], int(relu and residual is None),
-                               _ptr(x), _ptr(w32), _ptr(b32), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(ws), nbytes,
-                               _stream_ptr(device)))
+        rp = residual if fused_res else None
+        if partials is not None:
+            # statistics came from the producer (MFMA conv epilogue): normalisation pass only
+            assert cl and partials.shape[:2] == (n, groups) and partials.is_contiguous()
+            launch('dfm_group_norm_apply_channels_last_res', n, c, spatial, groups, eps, DTYPES[x.dtype],
+                   int(relu and (fused_res or residual is None)), x, w32, b32, rp, y, mean, rstd, partials,
+                   partials.shape[2], WS, STREAM, ws_bytes=nbytes)
+        elif cl:
+            launch('dfm_group_norm_fwd_channels_last_res', n, c, spatial, groups, eps, DTYPES[x.dtype],
+                   int(relu and (fused_res or residual is None)), x, w32, b32, rp, y, mean, rstd, WS, STREAM,
+                   ws_bytes=nbytes)
+        else:
+            launch('dfm_group_norm_fwd', n, c, spatial, groups, eps, DTYPES[x.dtype], int(relu and residual is None),
+                   x, w32, b32, y, mean, rstd, WS, STREAM, ws_bytes=nbytes)
         if residual is not None and not fused_res:
             # a layout the kernel does not fuse (NCDHW, mismatched strides): plain torch ops
             y = y + residual
@@ -101,7 +93,6 @@ class _GroupNormFn(torch.autograd.Function):
         gw = (torch.empty if cl else torch.zeros)(c, dtype=torch.float32, device=device)
         gb = (torch.empty if cl else torch.zeros)(c, dtype=torch.float32, device=device)
         nbytes = lib.dfm_group_norm_workspace_bytes(n, c, spatial, groups)
-        ws = _Workspace.get(device, nbytes)
         if cl:
             # channels-last kernels: no layout round trip; the masked gradient of a fused residual
             # input is a second output of the same pass
@@ -110,16 +101,11 @@ class _GroupNormFn(torch.autograd.Function):
             gx = torch.empty_like(x)
             gres = torch.empty_like(x) if want_res and relu else None
             if xmask:
-                with torch.cuda.device(device):
-                    _capi.check(lib.dfm_group_norm_bwd_channels_last_xmask(
-                        n, c, spatial, groups, _DTYPES[x.dtype], _ptr(gy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w32),
-                        _ptr(b32), _ptr(gx), _ptr(gw), _ptr(gb), _ptr(ws), nbytes, _stream_ptr(device)))
+                launch('dfm_group_norm_bwd_channels_last_xmask', n, c, spatial, groups, DTYPES[x.dtype], gy, x, mean,
+                       rstd, w32, b32, gx, gw, gb, WS, STREAM, ws_bytes=nbytes)
                 return gx, gw.to(wdt), gb.to(bdt), None, None, None, None, None, None
-            with torch.cuda.device(device):
-                _capi.check(lib.dfm_group_norm_bwd_channels_last(
-                    n, c, spatial, groups, _DTYPES[x.dtype], int(relu), _ptr(gy), _ptr(x), _ptr(y), _ptr(mean),
-                    _ptr(rstd), _ptr(w32), _ptr(gx), _ptr(gres) if gres is not None else None, _ptr(gw),
-                    _ptr(gb), _ptr(ws), nbytes, _stream_ptr(device)))
+            launch('dfm_group_norm_bwd_channels_last', n, c, spatial, groups, DTYPES[x.dtype], int(relu), gy, x, y,
+                   mean, rstd, w32, gx, gres, gw, gb, WS, STREAM, ws_bytes=nbytes)
             if want_res and not relu:
                 gres = gy
             return gx, gw.to(wdt), gb.to(bdt), None, None, None, None, gres, None
@@ -129,11 +115,8 @@ class _GroupNormFn(torch.autograd.Function):
             gres = gy * (y > 0).to(gy.dtype) if relu else gy
         gy = gy.contiguous().to(x.dtype)
         gx = torch.empty_like(x)
-        with torch.cuda.device(device):
-            _capi.check(
-                lib.dfm_group_norm_bwd(n, c, spatial, groups, _DTYPES[x.dtype], int(relu), _ptr(gy),
-                                       _ptr(x), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(w32), _ptr(gx),
-                                       _ptr(gw), _ptr(gb), _ptr(ws), nbytes, _stream_ptr(device)))
+        launch('dfm_group_norm_bwd', n, c, spatial, groups, DTYPES[x.dtype], int(relu), gy, x, y, mean, rstd, w32,
+               gx, gw, gb, WS, STREAM, ws_bytes=nbytes)
         return gx, gw.to(wdt), gb.to(bdt), None, None, None, None, gres, None
 
 
@@ -142,7 +125,7 @@ def group_norm(x, num_groups, weight, bias, eps=1e-5, relu=False, partials=None,
     ``partials`` (N, groups, splits, 3): count / mean / M2 moment partials of ``x`` from its
     producer (``MfmaConv3d.forward_with_stats``); the statistics pass over ``x`` is skipped.
     ``residual``: added after the affine map, before the ReLU (fused into the channels-last pass)."""
-    if not x.is_cuda or x.dtype not in _DTYPES:
+    if not x.is_cuda or x.dtype not in DTYPES:
         raise RuntimeError('fused group_norm needs a float32/bfloat16 GPU tensor '
                            '(depth-from-motion_amd has no CPU path)')
     return _GroupNormFn.apply(x, weight, bias, int(num_groups), float(eps), bool(relu), partials, residual)
@@ -169,7 +152,7 @@ class HipGroupNorm(nn.GroupNorm):
 
     def forward(self, x, relu=False, partials=None, residual=None):
         if x.is_cuda:
-            if x.dtype not in _DTYPES or not self.affine:
+            if x.dtype not in DTYPES or not self.affine:
                 raise RuntimeError(
                     f'HipGroupNorm: unsupported GPU input (dtype {x.dtype}, affine={self.affine}); '
                     'the fused kernels cover float32 / bfloat16 with affine parameters')
@@ -184,7 +167,7 @@ class HipGroupNorm(nn.GroupNorm):
 
 
 def _channels_ok(x):
-    vec = 16 // x.element_size() if x.dtype in _DTYPES else 0
+    vec = 16 // x.element_size() if x.dtype in DTYPES else 0
     c = x.shape[1] if x.dim() >= 2 else 0
     return bool(vec) and 0 < c <= 256 and c % vec == 0 and ((c // vec) & (c // vec - 1)) == 0
 
@@ -221,39 +204,28 @@ def _dense(t, fmt):
     return t
 
 
-def _nullable(t):
-    return _ptr(t) if t is not None and t.numel() else None
-
-
 def bn_stats(x):
     """dfm_batch_norm_stats_channels_last: this rank's payload, fp32 (C, 3) (count, mean, M2) per channel, of a
     channels-last contiguous, 16-byte aligned (N, C, *spatial) tensor (N may be 0)"""
     lib = _capi.lib()
     c, rows = x.shape[1], x.numel() // x.shape[1]
-    nbytes = lib.dfm_batch_norm_workspace_bytes(c, rows)
-    ws = _Workspace.get(x.device, nbytes)
     out = torch.empty(c, 3, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _capi.check(lib.dfm_batch_norm_stats_channels_last(c, rows, _DTYPES[x.dtype], _nullable(x), _ptr(out),
-                                                           _ptr(ws), nbytes, _stream_ptr(x.device)))
+    launch('dfm_batch_norm_stats_channels_last', c, rows, DTYPES[x.dtype], nonempty(x), out, WS, STREAM,
+           ws_bytes=lib.dfm_batch_norm_workspace_bytes(c, rows))
     return out
 
 
 def bn_apply_gathered(x, gathered, w32, b32, eps, relu, residual=None):
     """dfm_batch_norm_apply_gathered_channels_last: gathered (world, C, 3) rank-ordered payloads [device] ->
     (y, mean, rstd, moments); y = relu?(bn(x) + residual), moments (C, 3) the global (count, mean, M2)"""
-    lib = _capi.lib()
     c, rows = x.shape[1], x.numel() // x.shape[1]
     y = torch.empty_like(x)
     mean = torch.empty(c, dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
     moments = torch.empty(c, 3, dtype=torch.float32, device=x.device)
     gathered = gathered.contiguous()
-    with torch.cuda.device(x.device):
-        _capi.check(lib.dfm_batch_norm_apply_gathered_channels_last(
-            c, rows, gathered.shape[0], float(eps), _DTYPES[x.dtype], int(relu), _nullable(x), _ptr(w32), _ptr(b32),
-            _nullable(residual), _ptr(gathered), _nullable(y), _ptr(mean), _ptr(rstd), _ptr(moments),
-            _stream_ptr(x.device)))
+    launch('dfm_batch_norm_apply_gathered_channels_last', c, rows, gathered.shape[0], float(eps), DTYPES[x.dtype],
+           int(relu), nonempty(x), w32, b32, nonempty(residual), gathered, nonempty(y), mean, rstd, moments, STREAM)
     return y, mean, rstd, moments
 
 
@@ -262,13 +234,9 @@ def bn_bwd_reduce(gy, x, y, mean, rstd, w32, b32, relu):
     sum(dy' * xhat) = grad_weight).  relu with y None: the mask is recomputed from x."""
     lib = _capi.lib()
     c, rows = x.shape[1], x.numel() // x.shape[1]
-    nbytes = lib.dfm_batch_norm_workspace_bytes(c, rows)
-    ws = _Workspace.get(x.device, nbytes)
     sums = torch.empty(2, c, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _capi.check(lib.dfm_batch_norm_bwd_reduce_channels_last(
-            c, rows, _DTYPES[x.dtype], int(relu), _nullable(gy), _nullable(x), _nullable(y), _ptr(mean), _ptr(rstd),
-            _ptr(w32), _ptr(b32), _ptr(sums), _ptr(ws), nbytes, _stream_ptr(x.device)))
+    launch('dfm_batch_norm_bwd_reduce_channels_last', c, rows, DTYPES[x.dtype], int(relu), nonempty(gy), nonempty(x),
+           nonempty(y), mean, rstd, w32, b32, sums, WS, STREAM, ws_bytes=lib.dfm_batch_norm_workspace_bytes(c, rows))
     return sums
 
 
@@ -277,15 +245,11 @@ def bn_bwd_apply(gy, x, y, mean, rstd, w32, b32, relu, sums, moments, want_gres=
     the global count moments[0, 0]"""
     lib = _capi.lib()
     c, rows = x.shape[1], x.numel() // x.shape[1]
-    nbytes = lib.dfm_batch_norm_workspace_bytes(c, rows)
-    ws = _Workspace.get(x.device, nbytes)
     gx = torch.empty_like(x)
     gres = torch.empty_like(x) if want_gres else None
-    with torch.cuda.device(x.device):
-        _capi.check(lib.dfm_batch_norm_bwd_apply_channels_last(
-            c, rows, _DTYPES[x.dtype], int(relu), _nullable(gy), _nullable(x), _nullable(y), _ptr(mean), _ptr(rstd),
-            _ptr(w32), _ptr(b32), _ptr(sums.contiguous()), _ptr(moments), _nullable(gx), _nullable(gres), _ptr(ws),
-            nbytes, _stream_ptr(x.device)))
+    launch('dfm_batch_norm_bwd_apply_channels_last', c, rows, DTYPES[x.dtype], int(relu), nonempty(gy), nonempty(x),
+           nonempty(y), mean, rstd, w32, b32, sums.contiguous(), moments, nonempty(gx), nonempty(gres), WS, STREAM,
+           ws_bytes=lib.dfm_batch_norm_workspace_bytes(c, rows))
     return gx, gres
 
 
@@ -388,7 +352,7 @@ def batch_norm_train_channels_last(bn, x, relu=False, residual=None):
             return None   # the same answer on every rank: torch's SyncBatchNorm everywhere
         fmt = _memory_format(x)
         return _SyncBatchNormFn.apply(_dense(x, fmt), bn.weight, bn.bias, residual, bn, bool(relu), group)
-    vec = 16 // x.element_size() if x.dtype in _DTYPES else 0
+    vec = 16 // x.element_size() if x.dtype in DTYPES else 0
     c = x.shape[1]
     fmt = torch.channels_last_3d if x.dim() == 5 else torch.channels_last
     if not (bn.training and x.is_cuda and vec and x.dim() in (4, 5) and bn.affine and bn.track_running_stats and
@@ -432,7 +396,7 @@ class HipBatchNorm3d(nn.BatchNorm3d):
     ``forward(x, relu=False, residual=None)``: y = relu?(bn(x) + residual)."""
 
     def _fusable(self, x):
-        vec = 16 // x.element_size() if x.dtype in _DTYPES else 0
+        vec = 16 // x.element_size() if x.dtype in DTYPES else 0
         c = x.shape[1]
         return (self.training and x.is_cuda and vec and x.dim() == 5 and self.affine and
                 self.track_running_stats and c % vec == 0 and c <= 256 and ((c // vec) & (c // vec - 1)) == 0 and

@@ -23,7 +23,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import _capi
-from .plane_sweep import _DTYPES, _Workspace, _ptr, _require_gpu, _stream_ptr
+from ._launch import DTYPES, STREAM, WS, launch, require_gpu
 
 __all__ = ['NormalizeLayer', 'ImitationLoss', 'imitation_reg_layer_loss', 'imitation_statistics',
            'reduce_imitation_statistics']
@@ -175,7 +175,7 @@ def _desc(pred, target, p_cl, t_cl, points, boxes, mode, center, scale):
     d.num_boxes = 0 if boxes is None else boxes.shape[1]
     d.points_batch = 1 if points is None else points.shape[0]
     d.mode = mode
-    d.pred_dtype, d.target_dtype = _DTYPES[pred.dtype], _DTYPES[target.dtype]
+    d.pred_dtype, d.target_dtype = DTYPES[pred.dtype], DTYPES[target.dtype]
     d.pred_channels_last, d.target_channels_last = p_cl, t_cl
     d.center_len = 0 if center is None else center.numel()
     d.scale_len = 0 if scale is None else scale.numel()
@@ -184,16 +184,11 @@ def _desc(pred, target, p_cl, t_cl, points, boxes, mode, center, scale):
 
 def _launch_fwd(desc, pred, target, points, boxes, center, scale, new_center, mask, stats):
     lib = _capi.lib()
-    device = target.device
     nbytes = lib.dfm_imitation_loss_workspace_bytes(ctypes.byref(desc))
     if nbytes == 0:
         _capi.check(-1)
-    with torch.cuda.device(device):
-        ws = _Workspace.get(device, nbytes)
-        opt = lambda t: None if t is None else _ptr(t)  # noqa: E731
-        _capi.check(lib.dfm_imitation_loss_fwd(ctypes.byref(desc), opt(pred), _ptr(target), opt(points), opt(boxes),
-                                               opt(center), opt(scale), opt(new_center), opt(mask), _ptr(stats),
-                                               _ptr(ws), nbytes, _stream_ptr(device)))
+    launch('dfm_imitation_loss_fwd', desc, pred, target, points, boxes, center, scale, new_center, mask, stats, WS,
+           STREAM, ws_bytes=nbytes)
 
 
 class _ImitationFn(torch.autograd.Function):
@@ -215,14 +210,9 @@ class _ImitationFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_S, _g_mask, _g_stats):
         pred, target, mask, center, scale = ctx.saved_tensors
-        device = pred.device
         coef = g_S.detach().to(torch.float32).reshape(1).contiguous()
         grad = torch.empty_like(pred)  # pred's own layout and dtype
-        opt = lambda t: None if t is None else _ptr(t)  # noqa: E731
-        with torch.cuda.device(device):
-            _capi.check(_capi.lib().dfm_imitation_loss_bwd(ctypes.byref(ctx.desc), _ptr(pred), _ptr(target),
-                                                           _ptr(mask), opt(center), opt(scale), _ptr(coef),
-                                                           _ptr(grad), _stream_ptr(device)))
+        launch('dfm_imitation_loss_bwd', ctx.desc, pred, target, mask, center, scale, coef, grad, STREAM)
         return grad, None, None, None, None, None, None
 
 
@@ -240,9 +230,9 @@ def _pad_boxes(gt_boxes, device):
 
 
 def _prepare(features_preds, features_targets, mode, gt_boxes, points, norm_layer):
-    _require_gpu(features_preds, 'features_preds')
-    _require_gpu(features_targets, 'features_targets')
-    if features_preds.dtype not in _DTYPES or features_targets.dtype not in _DTYPES:
+    require_gpu(features_preds, 'features_preds')
+    require_gpu(features_targets, 'features_targets')
+    if features_preds.dtype not in DTYPES or features_targets.dtype not in DTYPES:
         raise TypeError('features must be float32 or bfloat16')
     if features_preds.shape != features_targets.shape or features_preds.dim() not in (4, 5):
         raise ValueError(f'features must share one (B, C, [Nz,] Ny, Nx) shape, got {tuple(features_preds.shape)} '

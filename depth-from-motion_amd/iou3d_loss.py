@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from .plane_sweep import _ptr, _require_gpu, _stream_ptr
+from ._launch import STREAM, launch, require_gpu
 from .registry import register_module
 
 __all__ = ['diff_iou_rotated_3d', 'diff_iou_rotated_2d', 'iou3d_loss', 'IOU3DLoss', 'iou3d_loss_from_deltas']
@@ -46,10 +46,7 @@ class _DiffIoUFn(torch.autograd.Function):
         g1 = torch.empty_like(b1) if want else None
         g2 = torch.empty_like(b2) if want else None
         if n:
-            with torch.cuda.device(device):
-                _capi.check(_capi.lib().dfm_diff_iou_rotated(
-                    _ptr(b1), _ptr(b2), n, width, _ptr(iou), _ptr(g1) if want else None,
-                    _ptr(g2) if want else None, _stream_ptr(device)))
+            launch('dfm_diff_iou_rotated', b1, b2, n, width, iou, g1 if want else None, g2 if want else None, STREAM)
         if want:
             ctx.save_for_backward(g1, g2)
         ctx.shapes = (box1.shape, box1.dtype, box2.shape, box2.dtype)
@@ -66,8 +63,8 @@ class _DiffIoUFn(torch.autograd.Function):
 
 
 def _diff_iou(box1, box2, width, name):
-    _require_gpu(box1, 'box1')
-    _require_gpu(box2, 'box2')
+    require_gpu(box1, 'box1')
+    require_gpu(box2, 'box2')
     if box1.shape != box2.shape or box1.dim() != 3 or box1.shape[-1] != width:
         raise ValueError(f'{name} takes two (B, N, {width}) tensors, got {tuple(box1.shape)} and '
                          f'{tuple(box2.shape)}')
@@ -115,8 +112,8 @@ def iou3d_loss(pred, target, weight=None, reduction='mean', avg_factor=None):
     has shape ``(1, N)`` as the reference's has; with ``N == 0`` it is ``(pred - target).sum(1) * 0.`` -- the
     branch the reference wrote for that case but cannot reach behind its ``assert target.numel() > 0``, while
     ``loss_single`` calls it for an image without positives all the same."""
-    _require_gpu(pred, 'pred')
-    _require_gpu(target, 'target')
+    require_gpu(pred, 'pred')
+    require_gpu(target, 'target')
     target = torch.where(torch.isnan(target), pred, target)
     if pred.size(0) > 0:
         loss = 1 - diff_iou_rotated_3d(pred.unsqueeze(0), target.unsqueeze(0))
@@ -156,10 +153,8 @@ class _FromDeltasFn(torch.autograd.Function):
         want = ctx.needs_input_grad[0]
         jac = torch.empty((num_pos, 7), dtype=torch.float32, device=device) if want else None
         if num_pos:
-            with torch.cuda.device(device):
-                _capi.check(_capi.lib().dfm_iou3d_loss_from_deltas(
-                    _ptr(a), _ptr(p), _ptr(t), _ptr(pos_inds), rows, size, num_pos, _ptr(loss),
-                    _ptr(jac) if want else None, _stream_ptr(device)))
+            launch('dfm_iou3d_loss_from_deltas', a, p, t, pos_inds, rows, size, num_pos, loss,
+                   jac, STREAM)
         if want:
             ctx.save_for_backward(jac, pos_inds)
         ctx.meta = (bbox_pred.shape, bbox_pred.dtype)
@@ -187,7 +182,7 @@ def iou3d_loss_from_deltas(anchors, bbox_pred, bbox_targets, pos_inds, bbox_weig
     per-row weights multiplied in.  Rows of ``bbox_pred`` outside ``pos_inds`` get exactly zero gradient."""
     for name, t in (('anchors', anchors), ('bbox_pred', bbox_pred), ('bbox_targets', bbox_targets),
                     ('pos_inds', pos_inds)):
-        _require_gpu(t, name)
+        require_gpu(t, name)
     if not (anchors.dim() == 2 and anchors.shape == bbox_pred.shape == bbox_targets.shape and anchors.shape[1] >= 7):
         raise ValueError(f'anchors, bbox_pred and bbox_targets share one (R, S >= 7) shape, got '
                          f'{tuple(anchors.shape)}, {tuple(bbox_pred.shape)}, {tuple(bbox_targets.shape)}')

@@ -36,7 +36,8 @@ from .frustum_to_voxel import frustum_to_voxel_sample
 from .geometry import stack_meta
 from .group_norm import HipBatchNorm3d, HipGroupNorm, _f32_params, batch_norm_train_channels_last
 from . import _capi
-from .plane_sweep import _DTYPES, _Workspace, _ptr, _stream_ptr, build_dfm_cost
+from ._launch import DTYPES, STREAM, WS, launch, pointers
+from .plane_sweep import build_dfm_cost
 from .sweep_conv import pack_sweep_conv_weights, sweep_conv_supported, sweep_dres0
 from .registry import register_module
 
@@ -196,9 +197,7 @@ class _DepthPoolFn(torch.autograd.Function):
         N, C, D, H, W = x.shape
         ctx.k, ctx.shape = k, tuple(x.shape)
         y = torch.empty((N, D // k, H, W, C), dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            _capi.check(_capi.lib().dfm_depth_pool_fwd(N * (D // k), k, H * W * C, _DTYPES[x.dtype], _ptr(x), _ptr(y),
-                                                       _stream_ptr(x.device)))
+        launch('dfm_depth_pool_fwd', N * (D // k), k, H * W * C, DTYPES[x.dtype], x, y, STREAM)
         return y.permute(0, 4, 1, 2, 3)
 
     @staticmethod
@@ -207,9 +206,7 @@ class _DepthPoolFn(torch.autograd.Function):
         k = ctx.k
         gy = gy.contiguous(memory_format=torch.channels_last_3d)
         gx = torch.empty((N, D, H, W, C), dtype=gy.dtype, device=gy.device)
-        with torch.cuda.device(gy.device):
-            _capi.check(_capi.lib().dfm_depth_pool_bwd(N * (D // k), k, H * W * C, _DTYPES[gy.dtype], _ptr(gy), _ptr(gx),
-                                                       _stream_ptr(gy.device)))
+        launch('dfm_depth_pool_bwd', N * (D // k), k, H * W * C, DTYPES[gy.dtype], gy, gx, STREAM)
         return gx.permute(0, 4, 1, 2, 3), None
 
 
@@ -222,7 +219,7 @@ def _depth_pool4(pool, x):
     if (x.is_cuda and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last_3d) and
             k[1:] == (1, 1) and tuple(pool.stride) == tuple(k) and x.shape[2] % k[0] == 0):
         B, C, D, H, W = x.shape
-        if x.dtype in _DTYPES and (H * W * C * x.element_size()) % 16 == 0 and x.data_ptr() % 16 == 0:
+        if x.dtype in DTYPES and (H * W * C * x.element_size()) % 16 == 0 and x.data_ptr() % 16 == 0:
             return _DepthPoolFn.apply(x, k[0])
         v = x.permute(0, 2, 3, 4, 1).reshape(B, D // k[0], k[0], H, W, C)
         return v.float().mean(dim=2).to(x.dtype).permute(0, 4, 1, 2, 3)
@@ -363,7 +360,7 @@ class DfMBackbone(nn.Module):
     # full-resolution convolutions that leave a quarter of the CUs idle in their second round of workgroups,
     # hourglass levels of 250 workgroups (half a chip), GroupNorm passes -- and the other stack's kernels fill
     # what one leaves free.  The side stream waits for what the main stream has produced so far, the main stream
-    # joins it before the prediction heads; scratch is per (device, stream) (plane_sweep._Workspace) and the
+    # joins it before the prediction heads; scratch is per (device, stream) (_launch.Workspace) and the
     # side stream's results are handed to the main stream with record_stream.  two_streams = False pins one stream.
     two_streams = True
     # With autograd recording: every backward node runs on the stream its forward ran on (the engine inserts the
@@ -556,8 +553,8 @@ class DfMBackbone(nn.Module):
         """cat + Conv2d(2D -> D, 1x1) + sigmoid + blend (dfm_backbone.py:136-141) as one launch
         (csrc/cost_gate.hip): inference, both costs (B, 1, D, H, W) contiguous on the GPU; None otherwise."""
         w = self.aggregate_cost.weight
-        if not (self.fused_gate and s_cost.is_cuda and not torch.is_grad_enabled() and s_cost.dtype in _DTYPES
-                and w.dtype in _DTYPES and m_cost.dtype == s_cost.dtype and m_cost.shape == s_cost.shape
+        if not (self.fused_gate and s_cost.is_cuda and not torch.is_grad_enabled() and s_cost.dtype in DTYPES
+                and w.dtype in DTYPES and m_cost.dtype == s_cost.dtype and m_cost.shape == s_cost.shape
                 and s_cost.dim() == 5 and s_cost.shape[1] == 1 and s_cost.shape[2] <= 96
                 and s_cost.is_contiguous() and m_cost.is_contiguous() and w.is_contiguous()
                 and w.shape[0] == s_cost.shape[2] and w.shape[1] == 2 * s_cost.shape[2]):
@@ -572,17 +569,14 @@ class DfMBackbone(nn.Module):
         def make():
             nb = lib.dfm_cost_gate_mfma_weight_bytes(D) if mfma else lib.dfm_cost_gate_weight_bytes(D)
             packed = torch.empty(nb, dtype=torch.uint8, device=w.device)
-            pack = lib.dfm_cost_gate_mfma_pack_weights if mfma else lib.dfm_cost_gate_pack_weights
-            _capi.check(pack(_ptr(w.detach()), _DTYPES[w.dtype], D, _ptr(packed), _stream_ptr(s_cost.device)))
+            launch('dfm_cost_gate_mfma_pack_weights' if mfma else 'dfm_cost_gate_pack_weights', w, DTYPES[w.dtype], D,
+                   packed, STREAM)
             return packed
-        with torch.cuda.device(s_cost.device):
-            packed = derived(self).get('gate_pack', (w,), make, (w.dtype, mfma, D))  # packed once per weight version
-            if mfma:
-                _capi.check(lib.dfm_cost_gate_mfma_fwd(B, D, H * W, _ptr(s_cost), _ptr(m_cost), _ptr(packed),
-                                                       _ptr(out), _stream_ptr(s_cost.device)))
-            else:
-                _capi.check(lib.dfm_cost_gate_fwd(B, D, H * W, _DTYPES[s_cost.dtype], _ptr(s_cost), _ptr(m_cost),
-                                                  _ptr(packed), _ptr(out), _stream_ptr(s_cost.device)))
+        packed = derived(self).get('gate_pack', (w,), make, (w.dtype, mfma, D))  # packed once per weight version
+        if mfma:
+            launch('dfm_cost_gate_mfma_fwd', B, D, H * W, s_cost, m_cost, packed, out, STREAM)
+        else:
+            launch('dfm_cost_gate_fwd', B, D, H * W, DTYPES[s_cost.dtype], s_cost, m_cost, packed, out, STREAM)
         return out
 
     def _predict(self, stereo, s_cost, mono, m_cost):
@@ -983,11 +977,9 @@ class _BilinearResizeFn(torch.autograd.Function):
             ci, cw, kw = _interp_table(w_in, w_out, ac, scale, gy.device)
             if kh * kw <= 64 and gy.data_ptr() % 16 == 0:
                 gx = torch.empty((B, h_in, w_in, C), dtype=gy.dtype, device=gy.device)
-                with torch.cuda.device(gy.device):
-                    _capi.check(_capi.lib().dfm_bilinear_resize_bwd_nhwc(
-                        B, C, h_in, w_in, h_out, w_out, _capi.DFM_BF16 if gy.dtype == torch.bfloat16 else _capi.DFM_F32,
-                        gy.data_ptr(), ri.data_ptr(), rw.data_ptr(), kh, ci.data_ptr(), cw.data_ptr(), kw,
-                        gx.data_ptr(), torch.cuda.current_stream(gy.device).cuda_stream))
+                launch('dfm_bilinear_resize_bwd_nhwc', B, C, h_in, w_in, h_out, w_out,
+                       _capi.DFM_BF16 if gy.dtype == torch.bfloat16 else _capi.DFM_F32, gy, ri, rw, kh, ci, cw, kw, gx,
+                       STREAM)
                 return gx.permute(0, 3, 1, 2), None, None, None
         if gy.stride(1) == 1 and C > 1 and gy.is_contiguous(memory_format=torch.channels_last):
             # an NHWC gradient (the 2-D necks train channels-last): the same two products on the memory as it lies --
@@ -1245,17 +1237,9 @@ class SPPUNetNeck(nn.Module):
             d.pooled_h[i], d.pooled_w[i] = p.shape[1], p.shape[2]
         ctot = sum(t.shape[1] for t in srcs) + len(cms) * self.spp_channel
         out = torch.empty((B, H, W, ctot), dtype=x.dtype, device=x.device)
-        lib = _capi.lib()
-        nbytes = lib.dfm_spp_tail_workspace_bytes(ctypes.byref(d))
-        ws = _Workspace.get(x.device, nbytes)
-
-        def arr(ts):
-            return (ctypes.c_void_p * 4)(*[t.data_ptr() for t in ts], *([None] * (4 - len(ts))))
-        with torch.cuda.device(x.device):
-            _capi.check(lib.dfm_spp_tail_fwd(
-                ctypes.byref(d), arr(pooled), arr([p[0] for p in params]), arr([p[1] for p in params]),
-                arr([p[2] for p in params]), arr(list(srcs)), out.data_ptr(), ws.data_ptr(), nbytes,
-                torch.cuda.current_stream(x.device).cuda_stream))
+        launch('dfm_spp_tail_fwd', d, pointers(pooled, 4), pointers([p[0] for p in params], 4),
+               pointers([p[1] for p in params], 4), pointers([p[2] for p in params], 4), pointers(srcs, 4), out, WS,
+               STREAM, ws_bytes=_capi.lib().dfm_spp_tail_workspace_bytes(ctypes.byref(d)))
         return out.permute(0, 3, 1, 2)
 
     def forward(self, feats):

@@ -17,15 +17,7 @@ import numpy as np
 import torch
 
 from . import _capi
-
-_DTYPES = {torch.float32: _capi.DFM_F32, torch.bfloat16: _capi.DFM_BF16}
-
-
-def _require_gpu(t, name):
-    if not t.is_cuda:
-        raise RuntimeError(
-            f'{name} must live on the GPU: depth-from-motion_amd has no CPU path '
-            '(the HIP kernels are the product; the CPU oracle is test-only)')
+from ._launch import DTYPES, STREAM, WS, launch, require_gpu, try_launch, upload
 
 
 def _pad4x4_batch(m, batch_size):
@@ -60,13 +52,10 @@ def camera_matrices(cam2imgs, cur2prevs, batch_size, device, cam2img_inv=None):
     cam2imgs, cur2prevs = as_f32(cam2imgs), as_f32(cur2prevs)
     if cam2imgs.device == device and device.type == 'cuda':
         # device-resident: one small kernel pads + inverts, nothing touches the host
-        lib = _capi.lib()
         k = cam2imgs[:batch_size].contiguous()
         P = torch.empty((batch_size, 16), dtype=torch.float32, device=device)
         Pinv = torch.empty_like(P)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_camera_prepare(_ptr(k), k.shape[-2], k.shape[-1], batch_size, _ptr(P),
-                                               _ptr(Pinv), _stream_ptr(device)))
+        launch('dfm_camera_prepare', k, k.shape[-2], k.shape[-1], batch_size, P, Pinv, STREAM)
         if cam2img_inv is not None:
             Pinv = as_f32(cam2img_inv)[:batch_size].to(device).reshape(batch_size, 16).contiguous()
         T = cur2prevs[:batch_size].to(device).reshape(batch_size, 16).contiguous()
@@ -79,10 +68,10 @@ def camera_matrices(cam2imgs, cur2prevs, batch_size, device, cam2img_inv=None):
     if cur2prevs.device.type == 'cuda':
         # the detector moves cur2prevs to the device (dfm.py:288-293) while the intrinsics stay
         # img_meta lists: no device -> host round trip for the poses, one pinned upload for P / Pinv
-        pack = _upload(torch.stack([P, Pinv]).reshape(2, batch_size, 16), device)
+        pack = upload(torch.stack([P, Pinv]).reshape(2, batch_size, 16), device)
         return pack[0], pack[1], cur2prevs[:batch_size].to(device).reshape(batch_size, 16).contiguous()
     T = cur2prevs[:batch_size]
-    pack = _upload(torch.stack([P, Pinv, T]).reshape(3, batch_size, 16), device)
+    pack = upload(torch.stack([P, Pinv, T]).reshape(3, batch_size, 16), device)
     return pack[0], pack[1], pack[2]
 
 
@@ -102,41 +91,8 @@ def _make_desc(cur_feats, num_depths, feat_sample_factor, cost_sample_factor, im
     desc.crop_y = float(img_crop_offset[1])
     desc.org_w = float(img_shape[1])
     desc.flip = 1 if flip else 0
-    desc.dtype = _DTYPES[cur_feats.dtype]
+    desc.dtype = DTYPES[cur_feats.dtype]
     return desc
-
-
-def _upload(t, device):
-    """small host tensor -> device without blocking the host on the stream: a pageable H2D copy
-    waits for everything queued before it, which serialises the Python launch loop of the next
-    step with the GPU work of the previous one (profiles/archive/r02_c26_*: 2x on the multi-view path)"""
-    if t.device.type != 'cpu':
-        return t.to(device)
-    return t.contiguous().pin_memory().to(device, non_blocking=True)
-
-
-def _stream_ptr(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-class _Workspace:
-    """Scratch (blocked feature copies, GroupNorm partials, pixel-major staging), grown on
-    demand and kept so that the steady state allocates nothing.  One buffer per (device,
-    stream): two ops issued on different streams never share scratch."""
-    _bufs = {}
-
-    @classmethod
-    def get(cls, device, nbytes):
-        key = (device, torch.cuda.current_stream(device).cuda_stream)
-        buf = cls._bufs.get(key)
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            cls._bufs[key] = buf
-        return buf
 
 
 # ---------------------------------------------------------------------------
@@ -236,13 +192,8 @@ def plane_sweep_forward(desc, cur_feats, prev_feats, depths, P, Pinv, T, out=Non
             out = torch.empty((desc.batch, desc.num_depths, desc.h_out, desc.w_out, 2 * desc.channels),
                               dtype=cur_feats.dtype, device=device).permute(0, 4, 1, 2, 3)
         assert out.is_contiguous(memory_format=torch.channels_last_3d)
-        nbytes = 256 + 4 * desc.channels
-        ws = _Workspace.get(device, nbytes)
-        with torch.cuda.device(device):
-            _capi.check(
-                lib.dfm_plane_sweep_fwd_nhwc(
-                    ctypes.byref(desc), _ptr(cur_feats), _ptr(prev_feats), _ptr(depths), _ptr(P),
-                    _ptr(Pinv), _ptr(T), _ptr(out), _ptr(ws), nbytes, _stream_ptr(device)))
+        launch('dfm_plane_sweep_fwd_nhwc', desc, cur_feats, prev_feats, depths, P, Pinv, T, out, WS, STREAM,
+               ws_bytes=256 + 4 * desc.channels)
         return out
     if (not channels_last and _nhwc(cur_feats) and _nhwc(prev_feats) and _current_opts(schedule) is None and
             (desc.h_out * desc.w_out) % (16 // cur_feats.element_size()) == 0):
@@ -250,42 +201,23 @@ def plane_sweep_forward(desc, cur_feats, prev_feats, depths, P, Pinv, T, out=Non
         if out is None:
             out = torch.empty((desc.batch, 2 * desc.channels, desc.num_depths, desc.h_out, desc.w_out),
                               dtype=cur_feats.dtype, device=device)
-        nbytes = 256 + 4 * desc.channels
-        ws = _Workspace.get(device, nbytes)
-        with torch.cuda.device(device):
-            rc = lib.dfm_plane_sweep_fwd_from_nhwc(
-                ctypes.byref(desc), _ptr(cur_feats), _ptr(prev_feats), _ptr(depths), _ptr(P), _ptr(Pinv),
-                _ptr(T), _ptr(out), _ptr(ws), nbytes, _stream_ptr(device))
-        if rc == 0:
+        if try_launch('dfm_plane_sweep_fwd_from_nhwc', desc, cur_feats, prev_feats, depths, P, Pinv, T, out, WS,
+                      STREAM, ws_bytes=256 + 4 * desc.channels):
             return out
-        if rc != _capi.DFM_ERR_UNSUPPORTED:
-            _capi.check(rc)
     cur_feats, prev_feats = cur_feats.contiguous(), prev_feats.contiguous()
     if channels_last:
         if out is None:
             out = torch.empty((desc.batch, desc.num_depths, desc.h_out, desc.w_out, 2 * desc.channels),
                               dtype=cur_feats.dtype, device=device).permute(0, 4, 1, 2, 3)
         assert out.is_contiguous(memory_format=torch.channels_last_3d)
-        nbytes = lib.dfm_plane_sweep_cl_workspace_bytes(ctypes.byref(desc))
-        ws = _Workspace.get(device, nbytes)
-        with torch.cuda.device(device):
-            _capi.check(
-                lib.dfm_plane_sweep_fwd_channels_last(
-                    ctypes.byref(desc), _ptr(cur_feats), _ptr(prev_feats), _ptr(depths), _ptr(P),
-                    _ptr(Pinv), _ptr(T), _ptr(out), _ptr(ws), nbytes, _stream_ptr(device)))
+        launch('dfm_plane_sweep_fwd_channels_last', desc, cur_feats, prev_feats, depths, P, Pinv, T, out, WS,
+               STREAM, ws_bytes=lib.dfm_plane_sweep_cl_workspace_bytes(ctypes.byref(desc)))
         return out
     if out is None:
         out = torch.empty((desc.batch, 2 * desc.channels, desc.num_depths, desc.h_out, desc.w_out),
                           dtype=cur_feats.dtype, device=device)
-    nbytes = lib.dfm_plane_sweep_workspace_bytes(ctypes.byref(desc))
-    ws = _Workspace.get(device, nbytes)
-    opts = _current_opts(schedule)
-    with torch.cuda.device(device):
-        _capi.check(
-            lib.dfm_plane_sweep_fwd_opts(ctypes.byref(desc), _ptr(cur_feats), _ptr(prev_feats),
-                                         _ptr(depths), _ptr(P), _ptr(Pinv), _ptr(T), _ptr(out),
-                                         _ptr(ws), nbytes, _stream_ptr(device),
-                                         ctypes.byref(opts) if opts is not None else None))
+    launch('dfm_plane_sweep_fwd_opts', desc, cur_feats, prev_feats, depths, P, Pinv, T, out, WS, STREAM,
+           _current_opts(schedule), ws_bytes=lib.dfm_plane_sweep_workspace_bytes(ctypes.byref(desc)))
     return out
 
 
@@ -295,16 +227,9 @@ def plane_sweep_autotune(desc, cur_feats, prev_feats, depths, P, Pinv, T, out):
     (``dfm_plane_sweep_autotune``; synchronous; ``out`` holds valid results afterwards).
     Returns the choice as a dict.  ``dfm_plane_sweep_fwd`` does this by itself on the first
     launch of a volume >= 1 GB."""
-    lib = _capi.lib()
-    device = cur_feats.device
-    nbytes = lib.dfm_plane_sweep_workspace_bytes(ctypes.byref(desc))
-    ws = _Workspace.get(device, nbytes)
     chosen = _capi.SweepOpts()
-    with torch.cuda.device(device):
-        _capi.check(
-            lib.dfm_plane_sweep_autotune(ctypes.byref(desc), _ptr(cur_feats), _ptr(prev_feats),
-                                         _ptr(depths), _ptr(P), _ptr(Pinv), _ptr(T), _ptr(out), _ptr(ws),
-                                         nbytes, _stream_ptr(device), ctypes.byref(chosen)))
+    launch('dfm_plane_sweep_autotune', desc, cur_feats, prev_feats, depths, P, Pinv, T, out, WS, STREAM, chosen,
+           ws_bytes=_capi.lib().dfm_plane_sweep_workspace_bytes(ctypes.byref(desc)))
     return chosen.as_dict()
 
 
@@ -343,7 +268,7 @@ def plane_sweep_backward(desc, grad_out, depths, P, Pinv, T):
     gradients take them from here."""
     lib = _capi.lib()
     device = grad_out.device
-    _require_gpu(grad_out, 'grad_out')
+    require_gpu(grad_out, 'grad_out')
     shape = (desc.batch, desc.channels, desc.h_in, desc.w_in)
     opts = _current_opts()
     if _bwd_kernel is not None:
@@ -355,39 +280,24 @@ def plane_sweep_backward(desc, grad_out, depths, P, Pinv, T):
         # up to 2 GB: re-laid by the library's LDS-tile transpose (copy speed) into a scratch of the
         # volume's size; larger volumes are read in place (no extra memory)
         if (_PREV_GATHER['on'] and desc.cost_sample_factor >= 1.5 and desc.channels % 32 == 0 and
-                _DTYPES.get(grad_out.dtype) == desc.dtype):
+                DTYPES.get(grad_out.dtype) == desc.dtype):
             # strided sweeps (config K): both maps by the gather kernel, the volume read where it lies -- a hit is
             # one contiguous run of 32 channels -- and the map gradients written pixel-major (returned as
             # channels_last (B, C, H, W) tensors: the layout the NHWC necks' backward wants).  No re-layout
             # pass, no scratch of the volume's size, no atomics, no zero-filled maps.
             nb = lib.dfm_plane_sweep_bwd_prev_gather_workspace_bytes(ctypes.byref(desc))
-            gws = _Workspace.get(device, nb)
             maps = [torch.empty((desc.batch, desc.h_in, desc.w_in, desc.channels), dtype=torch.float32,
                                 device=device) for _ in range(2)]
-            rc = 0
-            with torch.cuda.device(device):
-                for half in (0, 1):
-                    if rc == 0:
-                        rc = lib.dfm_plane_sweep_bwd_gather(ctypes.byref(desc), half, _ptr(grad_out), 1, _ptr(depths),
-                                                            _ptr(P), _ptr(Pinv), _ptr(T), _ptr(maps[half]), 1,
-                                                            _ptr(gws), nb, _stream_ptr(device))
-            if rc == 0:
+            if all(try_launch('dfm_plane_sweep_bwd_gather', desc, half, grad_out, 1, depths, P, Pinv, T, maps[half],
+                              1, WS, STREAM, ws_bytes=nb) for half in (0, 1)):
                 return maps[0].permute(0, 3, 1, 2), maps[1].permute(0, 3, 1, 2)
-            if rc != _capi.DFM_ERR_UNSUPPORTED:
-                _capi.check(rc)
         nbytes = grad_out.numel() * grad_out.element_size()
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes <= (2 << 30) else None
         g_cur = torch.zeros(shape, dtype=torch.float32, device=device)
         g_prev = torch.zeros(shape, dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            rc = lib.dfm_plane_sweep_bwd_channels_last(ctypes.byref(desc), _ptr(grad_out), _ptr(depths), _ptr(P),
-                                                       _ptr(Pinv), _ptr(T), _ptr(g_cur), _ptr(g_prev),
-                                                       _ptr(ws) if ws is not None else None,
-                                                       nbytes if ws is not None else 0, _stream_ptr(device))
-        if rc == 0:
+        if try_launch('dfm_plane_sweep_bwd_channels_last', desc, grad_out, depths, P, Pinv, T, g_cur, g_prev, ws,
+                      nbytes if ws is not None else 0, STREAM):
             return g_cur, g_prev
-        if rc != _capi.DFM_ERR_UNSUPPORTED:
-            _capi.check(rc)
     grad_out = grad_out.contiguous()
     if (opts is None and desc.cost_sample_factor >= 1.5 and grad_out.dtype == torch.float32 and
             desc.channels % 32 == 0 and (desc.h_out * desc.w_out) % 16 == 0):
@@ -398,38 +308,21 @@ def plane_sweep_backward(desc, grad_out, depths, P, Pinv, T):
         g_cur = torch.zeros((desc.batch, desc.h_in, desc.w_in, desc.channels), dtype=torch.float32,
                             device=device).permute(0, 3, 1, 2)
         g_prev = torch.empty(shape, dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            # the prev map: a lane per map pixel gathers its contributions plane by plane through the planes'
-            # inverse homographies and STORES the sums -- no zero-filled map (csrc/plane_sweep_bwd_gather.hip;
-            # round 5) -- the LDS-atomic tile kernel (kernel 8, prev map only) where that form does not apply
-            rc = _capi.DFM_ERR_UNSUPPORTED
-            if _PREV_GATHER['on']:
-                nb = lib.dfm_plane_sweep_bwd_prev_gather_workspace_bytes(ctypes.byref(desc))
-                gws = _Workspace.get(device, nb)
-                rc = lib.dfm_plane_sweep_bwd_prev_gather(ctypes.byref(desc), _ptr(grad_out), _ptr(depths), _ptr(P),
-                                                         _ptr(Pinv), _ptr(T), _ptr(g_prev), _ptr(gws), nb,
-                                                         _stream_ptr(device))
-            if rc == _capi.DFM_ERR_UNSUPPORTED:
-                g_prev.zero_()
-                prev_only = make_opts(kernel=8)
-                rc = lib.dfm_plane_sweep_bwd_opts(ctypes.byref(desc), _ptr(grad_out), _ptr(depths), _ptr(P),
-                                                  _ptr(Pinv), _ptr(T), _ptr(g_prev), _ptr(g_prev), _stream_ptr(device),
-                                                  ctypes.byref(prev_only))
-            if rc == 0:
-                rc = lib.dfm_plane_sweep_bwd_cur_nhwc(ctypes.byref(desc), _ptr(grad_out), _ptr(depths), _ptr(P),
-                                                      _ptr(Pinv), _ptr(T), _ptr(g_cur), _stream_ptr(device))
-        if rc == 0:
+        # the prev map: a lane per map pixel gathers its contributions plane by plane through the planes'
+        # inverse homographies and STORES the sums -- no zero-filled map (csrc/plane_sweep_bwd_gather.hip;
+        # round 5) -- the LDS-atomic tile kernel (kernel 8, prev map only) where that form does not apply
+        done = _PREV_GATHER['on'] and try_launch(
+            'dfm_plane_sweep_bwd_prev_gather', desc, grad_out, depths, P, Pinv, T, g_prev, WS, STREAM,
+            ws_bytes=lib.dfm_plane_sweep_bwd_prev_gather_workspace_bytes(ctypes.byref(desc)))
+        if not done:
+            g_prev.zero_()
+            done = try_launch('dfm_plane_sweep_bwd_opts', desc, grad_out, depths, P, Pinv, T, g_prev, g_prev, STREAM,
+                              make_opts(kernel=8))
+        if done and try_launch('dfm_plane_sweep_bwd_cur_nhwc', desc, grad_out, depths, P, Pinv, T, g_cur, STREAM):
             return g_cur, g_prev
-        if rc != _capi.DFM_ERR_UNSUPPORTED:
-            _capi.check(rc)
     g_cur = torch.zeros(shape, dtype=torch.float32, device=device)
     g_prev = torch.zeros(shape, dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _capi.check(
-            lib.dfm_plane_sweep_bwd_opts(ctypes.byref(desc), _ptr(grad_out), _ptr(depths),
-                                         _ptr(P), _ptr(Pinv), _ptr(T), _ptr(g_cur), _ptr(g_prev),
-                                         _stream_ptr(device),
-                                         ctypes.byref(opts) if opts is not None else None))
+    launch('dfm_plane_sweep_bwd_opts', desc, grad_out, depths, P, Pinv, T, g_cur, g_prev, STREAM, opts)
     return g_cur, g_prev
 
 
@@ -467,9 +360,9 @@ def build_dfm_cost(cur_feats,
     Returns:
         cost_volume: [B, 2C, D, H_out, W_out], same dtype as the inputs
     """
-    _require_gpu(cur_feats, 'cur_feats')
-    _require_gpu(prev_feats, 'prev_feats')
-    if cur_feats.dtype not in _DTYPES or prev_feats.dtype != cur_feats.dtype:
+    require_gpu(cur_feats, 'cur_feats')
+    require_gpu(prev_feats, 'prev_feats')
+    if cur_feats.dtype not in DTYPES or prev_feats.dtype != cur_feats.dtype:
         raise TypeError('cur_feats/prev_feats must both be float32 or bfloat16')
     assert cur_feats.dim() == 4 and cur_feats.shape == prev_feats.shape
     device = cur_feats.device
@@ -491,8 +384,7 @@ def plane_sweep_grid(cur_feats, depths, feat_sample_factor, cost_sample_factor, 
                      img_shape, flip=False, img_crop_offset=(0, 0), img_scale_factor=1.0, sample=0):
     """Parity aid: the normalised (cur_grid, prev_grid), each (D*H_out*W_out, 2),
     that the reference feeds to F.grid_sample (dfm_backbone.py:291-294)."""
-    _require_gpu(cur_feats, 'cur_feats')
-    lib = _capi.lib()
+    require_gpu(cur_feats, 'cur_feats')
     device = cur_feats.device
     depths = depths.reshape(-1).to(device=device, dtype=torch.float32).contiguous()
     desc = _make_desc(cur_feats, depths.numel(), feat_sample_factor, cost_sample_factor, img_shape,
@@ -501,8 +393,5 @@ def plane_sweep_grid(cur_feats, depths, feat_sample_factor, cost_sample_factor, 
     n = desc.num_depths * desc.h_out * desc.w_out
     cur_grid = torch.empty((n, 2), dtype=torch.float32, device=device)
     prev_grid = torch.empty((n, 2), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _capi.check(
-            lib.dfm_plane_sweep_grid(ctypes.byref(desc), sample, _ptr(depths), _ptr(P), _ptr(Pinv),
-                                     _ptr(T), _ptr(cur_grid), _ptr(prev_grid), _stream_ptr(device)))
+    launch('dfm_plane_sweep_grid', desc, sample, depths, P, Pinv, T, cur_grid, prev_grid, STREAM)
     return cur_grid, prev_grid

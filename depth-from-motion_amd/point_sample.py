@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from .plane_sweep import _DTYPES, _Workspace, _ptr, _require_gpu, _stream_ptr, _upload
+from ._launch import DTYPES, STREAM, WS, launch, require_gpu, try_launch, upload
 
 
 def voxel_centers(voxel_range, n_voxels):
@@ -91,7 +91,7 @@ def _make_desc(feats, npoints, nxyz, num_views, num_frames, scale, crop, flip, p
     desc.mode = 1 if aligned else 0
     desc.aggregate = 1 if aggregate == 'concat' else 0
     desc.valid_sample = 1 if valid_sample else 0
-    desc.dtype = _DTYPES[feats.dtype]
+    desc.dtype = DTYPES[feats.dtype]
     return desc
 
 
@@ -155,26 +155,15 @@ class _MvFn(torch.autograd.Function):
             out = torch.empty((B, points.shape[-2], c_out), dtype=feats.dtype, device=device)
         valid = torch.empty((B, points.shape[-2]), dtype=torch.uint8, device=device) if want_valid else None
         nbytes = lib.dfm_point_sample_mv_workspace_bytes(ctypes.byref(d0))
-        ws = _Workspace.get(device, nbytes)
-        with torch.cuda.device(device):
-            # the whole batch in one launch when the lanes-per-voxel kernel covers the call (channels-last
-            # views and volume, nearest sampling); DFM_ERR_UNSUPPORTED: one launch per sample below
-            rc = _capi.DFM_ERR_UNSUPPORTED
-            if d0.feats_channels_last and d0.mode == 0 and d0.valid_sample and \
-                    (nxyz is None or channels_last) and proj.is_contiguous() and ori_w.is_contiguous():
-                arr = (_capi.MvDesc * B)(*descs)
-                rc = lib.dfm_point_sample_mv_fwd_batched(
-                    arr, B, _ptr(feats), _ptr(points), 1 if points.dim() == 3 else 0, _ptr(proj), _ptr(ori_w),
-                    _ptr(out), _ptr(valid) if want_valid else None, _stream_ptr(device))
-                if rc not in (0, _capi.DFM_ERR_UNSUPPORTED):
-                    _capi.check(rc)
-            for b in range(B if rc != 0 else 0):
-                _capi.check(
-                    lib.dfm_point_sample_mv_fwd(ctypes.byref(descs[b]), _ptr(feats[b]),
-                                                _ptr(points[b] if points.dim() == 3 else points),
-                                                _ptr(proj[b]), _ptr(ori_w[b]), _ptr(out[b]),
-                                                _ptr(valid[b]) if want_valid else None, _ptr(ws),
-                                                nbytes, _stream_ptr(device)))
+        # the whole batch in one launch when the lanes-per-voxel kernel covers the call (channels-last
+        # views and volume, nearest sampling); DFM_ERR_UNSUPPORTED: one launch per sample below
+        batched = d0.feats_channels_last and d0.mode == 0 and d0.valid_sample and \
+            (nxyz is None or channels_last) and proj.is_contiguous() and ori_w.is_contiguous() and \
+            try_launch('dfm_point_sample_mv_fwd_batched', (_capi.MvDesc * B)(*descs), B, feats, points,
+                       1 if points.dim() == 3 else 0, proj, ori_w, out, valid, STREAM)
+        for b in range(0 if batched else B):
+            launch('dfm_point_sample_mv_fwd', descs[b], feats[b], points[b] if points.dim() == 3 else points,
+                   proj[b], ori_w[b], out[b], valid[b] if want_valid else None, WS, STREAM, ws_bytes=nbytes)
         ctx.descs = descs  # (the backward reads a (C, N) gradient: grad_out.contiguous() below)
         ctx.meta = (feats.shape, feats.dtype)
         ctx.save_for_backward(points, proj, ori_w)
@@ -191,14 +180,9 @@ class _MvFn(torch.autograd.Function):
         go = grad_out.contiguous().to(dtype)
         gf = torch.zeros(shape, dtype=torch.float32, device=device)
         nbytes = lib.dfm_point_sample_mv_bwd_workspace_bytes(ctypes.byref(ctx.descs[0]))
-        ws = _Workspace.get(device, nbytes)
-        with torch.cuda.device(device):
-            for b in range(shape[0]):
-                _capi.check(
-                    lib.dfm_point_sample_mv_bwd(ctypes.byref(ctx.descs[b]), _ptr(go[b]),
-                                                _ptr(points[b] if points.dim() == 3 else points),
-                                                _ptr(proj[b]), _ptr(ori_w[b]), _ptr(gf[b]), _ptr(ws),
-                                                nbytes, _stream_ptr(device)))
+        for b in range(shape[0]):
+            launch('dfm_point_sample_mv_bwd', ctx.descs[b], go[b], points[b] if points.dim() == 3 else points,
+                   proj[b], ori_w[b], gf[b], WS, STREAM, ws_bytes=nbytes)
         return gf.to(dtype), None, None, None, None, None, None, None
 
 
@@ -220,7 +204,7 @@ def point_sample(img_meta,
     [+ (N,) bool validity when ``valid_flag``]."""
     if padding_mode != 'zeros' or not align_corners:
         raise NotImplementedError('only padding_mode="zeros", align_corners=True (what DfM uses)')
-    _require_gpu(img_features, 'img_features')
+    require_gpu(img_features, 'img_features')
     assert img_features.dim() == 4 and img_features.shape[0] == 1
     device = img_features.device
     feats = img_features.contiguous()
@@ -243,7 +227,7 @@ def mv_feature_transformation(batch_feats, img_metas, num_views, num_frames, vox
     the tensor the reference hands to ``neck_3d`` (multiview_dfm.py:206-209).
     ``memory_format=torch.channels_last_3d`` (extension): the same tensor stored (B, Nx, Ny, Nz, C),
     what the NDHWC / MFMA neck convolutions read -- written directly, no conversion copy."""
-    _require_gpu(batch_feats, 'batch_feats')
+    require_gpu(batch_feats, 'batch_feats')
     device = batch_feats.device
     if points is None:
         points = _device_voxel_centers(voxel_range, n_voxels, device)
@@ -276,9 +260,9 @@ def mv_feature_transformation(batch_feats, img_metas, num_views, num_frames, vox
     if all(torch.is_tensor(p_) for p_ in proj):
         proj = torch.stack([p_.to(device) for p_ in proj]).contiguous()   # device tensors: no host round trip
     else:
-        proj = _upload(torch.from_numpy(np.stack([p_.detach().cpu().numpy() if torch.is_tensor(p_) else p_
+        proj = upload(torch.from_numpy(np.stack([p_.detach().cpu().numpy() if torch.is_tensor(p_) else p_
                                                   for p_ in proj])), device)
-    ori_w = _upload(torch.tensor(ori_w, dtype=torch.float32), device)
+    ori_w = upload(torch.tensor(ori_w, dtype=torch.float32), device)
     if any(m.get('transformation_3d_flow') for m in img_metas):
         # point_sample undoes each sample's own 3-D augmentation first (point_fusion.py:57-58)
         points = torch.stack([_reverse_3d_flow(points, 'LIDAR', m) for m in img_metas]).contiguous()
@@ -311,9 +295,8 @@ def voxel_sample(voxel_features,
     between CPU models, so bit-exact replays of a fixture pass the stored inverse."""
     if padding_mode != 'zeros' or not align_corners:
         raise NotImplementedError('only padding_mode="zeros", align_corners=True')
-    _require_gpu(voxel_features, 'voxel_features')
+    require_gpu(voxel_features, 'voxel_features')
     assert voxel_features.dim() == 5 and voxel_features.shape[0] == 1
-    lib = _capi.lib()
     device = voxel_features.device
     vox = voxel_features.contiguous()
     depths = torch.as_tensor(depth_samples, dtype=torch.float32)[::downsample_factor]
@@ -336,7 +319,7 @@ def voxel_sample(voxel_features,
     for i, v in enumerate(inv.reshape(16).tolist()):
         desc.proj_inv[i] = v
     desc.mode = 1 if aligned else 0
-    desc.dtype = _DTYPES[vox.dtype]
+    desc.dtype = DTYPES[vox.dtype]
     return _VoxelSampleFn.apply(vox, depths, desc)
 
 
@@ -345,13 +328,10 @@ class _VoxelSampleFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vox, depths, desc):
-        lib = _capi.lib()
         device = vox.device
         out = torch.empty((1, desc.channels, desc.num_depths, desc.h_out, desc.w_out), dtype=vox.dtype,
                           device=device)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_voxel_sample_fwd(ctypes.byref(desc), _ptr(vox), _ptr(depths), _ptr(out),
-                                                 _stream_ptr(device)))
+        launch('dfm_voxel_sample_fwd', desc, vox, depths, out, STREAM)
         ctx.desc, ctx.meta = desc, (vox.shape, vox.dtype)
         ctx.save_for_backward(depths)
         return out
@@ -360,13 +340,10 @@ class _VoxelSampleFn(torch.autograd.Function):
     def backward(ctx, gout):
         (depths,) = ctx.saved_tensors
         shape, dtype = ctx.meta
-        lib = _capi.lib()
         device = gout.device
         go = gout.contiguous().to(dtype)
         gv = torch.zeros(shape, dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_voxel_sample_bwd(ctypes.byref(ctx.desc), _ptr(go), _ptr(depths), _ptr(gv),
-                                                 _stream_ptr(device)))
+        launch('dfm_voxel_sample_bwd', ctx.desc, go, depths, gv, STREAM)
         return gv.to(dtype), None, None
 
 
@@ -417,11 +394,10 @@ def voxel_sample_mv(volume,
     ``img_shapes[b][v]``: (h, w, ...) of the view before padding.
     ``memory_format=torch.channels_last_3d``: the result stored (B * Nv, D, h_out, w_out, C), what
     ``MfmaConv3dTo1`` reads."""
-    _require_gpu(volume, 'volume')
+    require_gpu(volume, 'volume')
     assert volume.dim() == 5
-    if volume.dtype not in _DTYPES:
+    if volume.dtype not in DTYPES:
         raise TypeError(f'volume must be float32 or bfloat16, got {volume.dtype}')
-    lib = _capi.lib()
     device = volume.device
     B, C = volume.shape[:2]
     num_views = int(num_views)
@@ -440,7 +416,7 @@ def voxel_sample_mv(volume,
     else:
         vox, vcl = volume.contiguous(), 0
     downsample_factor = int(downsample_factor)
-    depths = _upload(torch.as_tensor(depth_samples, dtype=torch.float32).detach()[::downsample_factor], device)
+    depths = upload(torch.as_tensor(depth_samples, dtype=torch.float32).detach()[::downsample_factor], device)
     depths = depths.contiguous()
     scales = [_scale_xy(s) for s in img_scale_factors]
     crops = [_crop_xy(c) for c in img_crop_offsets]
@@ -452,9 +428,8 @@ def voxel_sample_mv(volume,
         mats = mats[:, :num_views].to(device=device, dtype=torch.float32).reshape(P, 4, 4).contiguous()
         pad4, inv = torch.empty((P, 16), dtype=torch.float32, device=device), \
             torch.empty((P, 16), dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_camera_prepare(_ptr(mats), 4, 4, P, _ptr(pad4), _ptr(inv), _stream_ptr(device)))
-        pairs = _upload(torch.from_numpy(_pair_rows(None, scales, crops, img_flips, img_shapes, num_views)), device)
+        launch('dfm_camera_prepare', mats, 4, 4, P, pad4, inv, STREAM)
+        pairs = upload(torch.from_numpy(_pair_rows(None, scales, crops, img_flips, img_shapes, num_views)), device)
         pairs[:, :16] = inv
     else:
         def host(m):
@@ -464,7 +439,7 @@ def voxel_sample_mv(volume,
         else:
             inv = torch.stack([torch.inverse(host(proj_mats[b][v]))   # utils.py:241, one matrix at a time
                                for b in range(B) for v in range(num_views)])
-        pairs = _upload(torch.from_numpy(_pair_rows(inv.reshape(P, 16).numpy(), scales, crops, img_flips,
+        pairs = upload(torch.from_numpy(_pair_rows(inv.reshape(P, 16).numpy(), scales, crops, img_flips,
                                                     img_shapes, num_views)), device)
     desc = _capi.VsMvDesc()
     desc.batch, desc.num_views, desc.channels = B, num_views, C
@@ -476,7 +451,7 @@ def voxel_sample_mv(volume,
         desc.voxel_range[i] = float(v)
     for i, v in enumerate(np.asarray(voxel_size, dtype=np.float32).reshape(3)):
         desc.voxel_size[i] = float(v)
-    desc.dtype = _DTYPES[vox.dtype]
+    desc.dtype = DTYPES[vox.dtype]
     desc.volume_channels_last = vcl
     desc.out_channels_last = 1 if memory_format == torch.channels_last_3d else 0
     return _VoxelSampleMvFn.apply(vox, depths, pairs, desc)
@@ -487,7 +462,6 @@ class _VoxelSampleMvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vox, depths, pairs, desc):
-        lib = _capi.lib()
         device = vox.device
         P, C = desc.batch * desc.num_views, desc.channels
         lattice = (desc.num_depths, desc.h_out, desc.w_out)
@@ -495,9 +469,7 @@ class _VoxelSampleMvFn(torch.autograd.Function):
             out = torch.empty((P,) + lattice + (C,), dtype=vox.dtype, device=device).permute(0, 4, 1, 2, 3)
         else:
             out = torch.empty((P, C) + lattice, dtype=vox.dtype, device=device)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_voxel_sample_mv_fwd(ctypes.byref(desc), _ptr(pairs), _ptr(vox), _ptr(depths),
-                                                    _ptr(out), _stream_ptr(device)))
+        launch('dfm_voxel_sample_mv_fwd', desc, pairs, vox, depths, out, STREAM)
         ctx.desc, ctx.meta = desc, (vox.shape, vox.dtype)
         ctx.save_for_backward(depths, pairs)
         return out
@@ -507,7 +479,6 @@ class _VoxelSampleMvFn(torch.autograd.Function):
         depths, pairs = ctx.saved_tensors
         (B, C, nx, ny, nz), dtype = ctx.meta
         desc = ctx.desc
-        lib = _capi.lib()
         device = gout.device
         go = gout.to(dtype)
         if desc.out_channels_last:
@@ -518,7 +489,5 @@ class _VoxelSampleMvFn(torch.autograd.Function):
             gv = torch.zeros((B, nx, ny, nz, C), dtype=torch.float32, device=device).permute(0, 4, 1, 2, 3)
         else:
             gv = torch.zeros((B, C, nx, ny, nz), dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            _capi.check(lib.dfm_voxel_sample_mv_bwd(ctypes.byref(desc), _ptr(pairs), _ptr(go), _ptr(depths),
-                                                    _ptr(gv), _stream_ptr(device)))
+        launch('dfm_voxel_sample_mv_bwd', desc, pairs, go, depths, gv, STREAM)
         return gv.to(dtype), None, None, None

@@ -10,7 +10,8 @@ import ctypes
 import torch
 
 from . import _capi
-from .plane_sweep import _make_desc, _nhwc, _ptr, _require_gpu, _stream_ptr, camera_matrices
+from ._launch import STREAM, launch, require_gpu
+from .plane_sweep import _make_desc, _nhwc, camera_matrices
 
 
 def pack_sweep_conv_weights(w_stereo, w_mono):
@@ -20,11 +21,9 @@ def pack_sweep_conv_weights(w_stereo, w_mono):
     ws, wm = w_stereo.detach().contiguous(), w_mono.detach().contiguous()
     if ws.dtype not in (torch.float32, torch.bfloat16) or wm.dtype != ws.dtype:
         ws, wm = ws.float(), wm.float()
-    lib = _capi.lib()
-    packed = torch.empty(lib.dfm_sweep_conv_weight_bytes(), dtype=torch.uint8, device=ws.device)
-    with torch.cuda.device(ws.device):
-        _capi.check(lib.dfm_sweep_conv_pack_weights(_ptr(ws), _ptr(wm), _capi.DFM_F32 if ws.dtype == torch.float32
-                                                    else _capi.DFM_BF16, _ptr(packed), _stream_ptr(ws.device)))
+    packed = torch.empty(_capi.lib().dfm_sweep_conv_weight_bytes(), dtype=torch.uint8, device=ws.device)
+    launch('dfm_sweep_conv_pack_weights', ws, wm, _capi.DFM_F32 if ws.dtype == torch.float32 else _capi.DFM_BF16,
+           packed, STREAM)
     return packed
 
 
@@ -40,8 +39,8 @@ def sweep_dres0(cur_feats, prev_feats, depths, feat_sample_factor, cost_sample_f
     ``dres0_mono.conv(cost_raw[:, :32])`` as (B, 32, D, H, W) bf16 channels_last_3d tensors BEFORE
     GroupNorm / ReLU, and their per-channel moment partials (B, 32, splits, 3) for
     ``group_norm(..., partials=...)``."""
-    _require_gpu(cur_feats, 'cur_feats')
-    _require_gpu(prev_feats, 'prev_feats')
+    require_gpu(cur_feats, 'cur_feats')
+    require_gpu(prev_feats, 'prev_feats')
     if not sweep_conv_supported(cur_feats) or prev_feats.dtype != cur_feats.dtype or prev_feats.shape != cur_feats.shape:
         raise TypeError('sweep_dres0 takes two (B, 32, H, W) bfloat16 feature maps')
     device = cur_feats.device
@@ -64,8 +63,6 @@ def sweep_dres0(cur_feats, prev_feats, depths, feat_sample_factor, cost_sample_f
     ym = torch.empty(shape, dtype=torch.bfloat16, device=device)
     ps = torch.empty((B, 32, splits, 3), dtype=torch.float32, device=device)
     pm = torch.empty((B, 32, splits, 3), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _capi.check(lib.dfm_sweep_conv_fwd(ctypes.byref(desc), _ptr(cur_feats), _ptr(prev_feats), _ptr(depths), _ptr(P),
-                                           _ptr(Pinv), _ptr(T), _ptr(packed), _ptr(ys), _ptr(ym), _ptr(ps), _ptr(pm),
-                                           depth_chunk, _stream_ptr(device)))
+    launch('dfm_sweep_conv_fwd', desc, cur_feats, prev_feats, depths, P, Pinv, T, packed, ys, ym, ps, pm, depth_chunk,
+           STREAM)
     return ys.permute(0, 4, 1, 2, 3), ps, ym.permute(0, 4, 1, 2, 3), pm

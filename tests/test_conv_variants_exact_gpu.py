@@ -44,6 +44,14 @@ def _vp(addr):
     return ctypes.c_void_p(addr)
 
 
+def _ptr(t):
+    return _vp(t.data_ptr())
+
+
+def _stream_ptr(device):
+    return importlib.import_module('depth-from-motion_amd._launch').stream_ptr(device)
+
+
 def _guarded_input(x_ndhwc, cstride):
     """x (N, D, H, W, C) bf16 -> (buffer, address of x's first element): x's pixels cstride elements apart, the
     other channels of each pixel and PRE / POST elements either side filled with BIG"""
@@ -95,7 +103,7 @@ def test_conv3d_g_every_body_exact_with_guards(cv, c):
     ref = _ref64(c, x, w, swap).permute(0, 2, 3, 4, 1).contiguous()          # (N, D', H', W', cout) float64
     xbuf, xaddr = _guarded_input(x.bfloat16().permute(0, 2, 3, 4, 1), c.cstride)
     pk = cv.pack_conv3d_g_weights(w.to(DEV), c.cin, c.cout, swap=swap)
-    st = cv._stream_ptr(DEV)
+    st = _stream_ptr(DEV)
     numel = ref.numel()
     oshape = ref.shape
 
@@ -108,9 +116,9 @@ def test_conv3d_g_every_body_exact_with_guards(cv, c):
                                   (True, True, True), (False, False, True)):
         raw, out, oaddr = _guarded_output(numel, torch.bfloat16)
         d = _desc(cv, c, relu)
-        rc = lib.dfm_conv3d_g_fwd(ctypes.byref(d), _vp(xaddr), cv._ptr(pk),
-                                  cv._ptr(scale) if use_ss else None, cv._ptr(shift) if use_ss else None,
-                                  cv._ptr(res) if use_res else None, _vp(oaddr), st)
+        rc = lib.dfm_conv3d_g_fwd(ctypes.byref(d), _vp(xaddr), _ptr(pk),
+                                  _ptr(scale) if use_ss else None, _ptr(shift) if use_ss else None,
+                                  _ptr(res) if use_res else None, _vp(oaddr), st)
         assert rc == 0, lib.dfm_last_error()
         torch.cuda.synchronize()
         e = ref
@@ -130,14 +138,14 @@ def test_conv3d_g_every_body_exact_with_guards(cv, c):
     # fp32 form: into a guarded buffer, then accumulating in place (acc_in == out)
     raw, out, oaddr = _guarded_output(numel, torch.float32)
     d = _desc(cv, c)
-    assert lib.dfm_conv3d_g_fwd_f32(ctypes.byref(d), _vp(xaddr), cv._ptr(pk), None, _vp(oaddr), st) == 0
+    assert lib.dfm_conv3d_g_fwd_f32(ctypes.byref(d), _vp(xaddr), _ptr(pk), None, _vp(oaddr), st) == 0
     torch.cuda.synchronize()
     assert torch.equal(out.view(oshape), ref.float()), f'{c.name} fp32: max |diff| ' \
         f'{(out.view(oshape).double() - ref).abs().max().item()}'
     assert _guards_intact(raw, numel)
     acc = _ints(tuple(oshape), seed=12, lo=-1000, hi=1000)
     out.copy_(acc.view(-1))
-    assert lib.dfm_conv3d_g_fwd_f32(ctypes.byref(d), _vp(xaddr), cv._ptr(pk), _vp(oaddr), _vp(oaddr), st) == 0
+    assert lib.dfm_conv3d_g_fwd_f32(ctypes.byref(d), _vp(xaddr), _ptr(pk), _vp(oaddr), _vp(oaddr), st) == 0
     torch.cuda.synchronize()
     assert torch.equal(out.view(oshape), (ref + acc.to(DEV, torch.float64)).float()), f'{c.name} fp32 acc_in == out'
     assert _guards_intact(raw, numel)
@@ -203,15 +211,15 @@ def test_conv3d_k3_c32_forward_forms_exact(cv, depth_chunk):
     pk = cv.pack_conv3d_weights(wt.to(DEV), 0)
     acc = _ints(tuple(ref.shape), seed=5, lo=-500, hi=500).to(DEV)
     numel = ref.numel()
-    st = cv._stream_ptr(DEV)
+    st = _stream_ptr(DEV)
     splits = lib.dfm_conv3d_k3_c32_stats_splits(n, d, h, w, depth_chunk)
     for out_f32, use_acc, stats, relu in ((1, True, False, 0), (1, False, False, 0), (0, True, True, 0),
                                           (0, False, True, 0), (0, True, False, 1), (0, False, False, 0)):
         raw, out, oaddr = _guarded_output(numel, torch.float32 if out_f32 else torch.bfloat16)
         part = torch.empty((n, 32, splits, 3), dtype=torch.float32, device=DEV) if stats else None
-        rc = lib.dfm_conv3d_k3_c32_fwd_strided(n, d, h, w, _vp(xaddr), 32, cv._ptr(pk),
-                                               cv._ptr(acc) if use_acc else None, _vp(oaddr), out_f32, relu,
-                                               depth_chunk, cv._ptr(part) if stats else None, st)
+        rc = lib.dfm_conv3d_k3_c32_fwd_strided(n, d, h, w, _vp(xaddr), 32, _ptr(pk),
+                                               _ptr(acc) if use_acc else None, _vp(oaddr), out_f32, relu,
+                                               depth_chunk, _ptr(part) if stats else None, st)
         assert rc == 0, lib.dfm_last_error()
         torch.cuda.synchronize()
         e = ref + acc.double() if use_acc else ref
@@ -228,20 +236,20 @@ def test_conv3d_k3_c32_to1_and_slices_exact(cv):
     n, d, h, w = 1, 5, 17, 33
     x, wt, ref = _c32_io(n, d, h, w, seed=21)
     xd = x.bfloat16().to(DEV).contiguous(memory_format=torch.channels_last_3d)
-    st = cv._stream_ptr(DEV)
+    st = _stream_ptr(DEV)
     # 32 -> 1: the weight in row 0 of a zero-padded (32, 32) pack, channel 0 stored
     w1 = torch.zeros_like(wt)
     w1[0] = wt[0]
     pk1 = cv.pack_conv3d_weights(w1.to(DEV), 0)
     raw, out, oaddr = _guarded_output(n * d * h * w, torch.bfloat16)
-    assert lib.dfm_conv3d_k3_c32_to1_fwd(n, d, h, w, cv._ptr(xd), cv._ptr(pk1), _vp(oaddr), 0, 0, st) == 0
+    assert lib.dfm_conv3d_k3_c32_to1_fwd(n, d, h, w, _ptr(xd), _ptr(pk1), _vp(oaddr), 0, 0, st) == 0
     torch.cuda.synchronize()
     assert torch.equal(out.view(n, d, h, w), ref[..., 0].float().bfloat16()) and _guards_intact(raw, n * d * h * w)
     # _fwd_slices: 32 channels written into a 64- and a 96-channel tensor, the others untouched
     pk = cv.pack_conv3d_weights(wt.to(DEV), 0)
     for C, lo in ((64, 32), (96, 32), (96, 64)):
         raw, out, base = _guarded_output(n * d * h * w * C, torch.bfloat16)
-        assert lib.dfm_conv3d_k3_c32_fwd_slices(n, d, h, w, cv._ptr(xd), 32, cv._ptr(pk), _vp(base + 2 * lo), C, 0,
+        assert lib.dfm_conv3d_k3_c32_fwd_slices(n, d, h, w, _ptr(xd), 32, _ptr(pk), _vp(base + 2 * lo), C, 0,
                                                 0, st) == 0
         torch.cuda.synchronize()
         o = out.view(n, d, h, w, C)

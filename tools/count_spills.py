@@ -7,6 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 pkg = importlib.import_module('depth-from-motion_amd')
 sweep = importlib.import_module('depth-from-motion_amd.plane_sweep')
+launch = importlib.import_module('depth-from-motion_amd._launch')
 lib = pkg._capi.lib()
 w = bench.WORKLOADS['nstar']; dev = torch.device('cuda:0'); B = w['B']
 cur = torch.randn(B, w['C'], w['H'], w['W']).to(dev).bfloat16(); prev = torch.randn_like(cur)
@@ -19,7 +20,7 @@ for kib in (36, 52, 64, 78, 100, 150):
         sweep.plane_sweep_forward(desc, cur, prev, depths, P, Pinv, T, out=out)
     torch.cuda.synchronize()
     nbytes = lib.dfm_plane_sweep_workspace_bytes(ctypes.byref(desc))
-    ws = sweep._Workspace.get(dev, nbytes)
+    ws = launch.Workspace.get(dev.index, launch.stream_ptr(dev).value, nbytes)
     blocked = ((B * 32 * w['H'] * w['W'] * 16 + 255) // 256) * 256
     count = int(ws[2 * blocked: 2 * blocked + 4].view(torch.int32).item())
     print(f'lds {kib:3d} KiB: {count} tiles queued for the second-chance pass')
