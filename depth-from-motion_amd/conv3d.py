@@ -9,23 +9,28 @@ mmdet3d/models/utils/conv_modules.py:27-43 (every full-resolution convolution of
 ``MfmaConv3d`` is an ``nn.Conv3d`` (same parameters, same ``state_dict`` keys).  Its forward runs
 the MFMA kernel when the input is a bfloat16 ``channels_last_3d`` GPU tensor (what a backbone
 converted with ``.to(torch.bfloat16, memory_format=torch.channels_last_3d)`` produces, fed by the
-channels-last cost volume); any other dtype / layout takes torch's convolution (MIOpen) exactly as
-before -- that is the module's other documented path, not a fallback of a failed launch.
+channels-last cost volume); an fp32 GPU input runs the general kernel in split precision; any other dtype /
+layout takes torch's convolution (MIOpen) exactly as before -- that is the module's other documented path, not a
+fallback of a failed launch.
 Backward: the input gradient runs in the same MFMA kernel (transposed, mirrored weight
-fragments); the weight gradient is torch's convolution backward (MIOpen).
+fragments); the weight gradient is the hand-written MFMA kernel of csrc/conv3d_wgrad.hip
+(``conv3d_weight_grad``).
+
+The general kernel (csrc/conv3d_g.hip) serves every other 3x3x3 / 3x3 convolution of the path.  ``ConvGeom``
+describes one of its convolutions -- forward launch, both backward launches, planner descriptor -- and
+``_ConvGFn`` is its one autograd function, in bf16 or in split precision.
 """
 import ctypes
 import warnings
+from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import _capi
-from ._launch import STREAM, WS, launch, try_launch
+from ._launch import DTYPES, STREAM, WS, launch, try_launch
 from .derived import Derived, derived, note_derived_build
-
-_WDT = {torch.float32: _capi.DFM_F32, torch.bfloat16: _capi.DFM_BF16}
 
 # ---------------------------------------------------------------------------------------------
 # What an ``Mfma*`` module does with a GPU input its kernel does not take (fp32, NCDHW, a shape no
@@ -76,7 +81,7 @@ def _torch_path(module, x, why):
     key = (type(module).__name__, why)
     if key not in _WARNED:
         _WARNED.add(key)
-        warnings.warn(msg, RuntimeWarning, stacklevel=3)
+        warnings.warn(msg, RuntimeWarning, stacklevel=5)  # past _torch_forward, _forward and forward
 
 
 def _why_not_bf16_cl(x, dims):
@@ -87,6 +92,60 @@ def _why_not_bf16_cl(x, dims):
     return None
 
 
+class _MfmaModule:
+    """What the ``Mfma*`` modules share; each names this class before its torch parent.  A module says in
+    ``_covered()`` whether its configuration is one its kernel takes (``UNCOVERED``: the reason when it is not), in
+    ``why_not(x)`` why its bf16 kernel does not take ``x``, and runs ``x`` in an arithmetic of the general kernel
+    (``_BF16`` | ``_SPLIT``) in ``_run(x, arith)``."""
+    UNCOVERED = None
+    _DIMS = 5                  # of the input
+    _SPLIT_IN_REASON = False   # does the warning also say why split precision did not apply?
+
+    def config_why_not(self):
+        """None when the module's configuration is one its kernel covers, else the reason: the part of ``why_not``
+        that does not depend on the input.  The fp32 dispatch asks this, not the text of a reason."""
+        return None if self._covered() else self.UNCOVERED
+
+    def _why_not_config(self, x):
+        return 'CPU tensor' if not x.is_cuda else self.config_why_not()
+
+    def eligible(self, x):
+        return self.why_not(x) is None
+
+    def _geom(self):
+        return ConvGeom.of(self)
+
+    def split_why_not(self, x):
+        """why an fp32 CUDA input does NOT take the split-precision MFMA path (None: it does)"""
+        if _FP32_MODE['mode'] == 'torch':
+            return 'set_fp32_mode("torch")'
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == self._DIMS and
+                x.shape[1] == self.in_channels):
+            return 'not an fp32 GPU call of this module'
+        g = self._geom()
+        size = tuple(x.shape[2:]) if self._DIMS == 5 else (1, x.shape[2], x.shape[3])
+        if not all(t or k1 or s + 2 * p >= 3 for s, p, t, k1 in zip(size, g.padding, g.transposed, g.kernel1)):
+            return 'input smaller than the kernel'
+        return None if g.plannable(x.shape[0], size) else 'no tiling of the general kernel fits this shape'
+
+    def _forward(self, x, why):
+        """the forward every module shares: its bf16 kernel when ``why`` (not) is None; split precision for an
+        fp32 GPU input of a covered configuration; else torch's convolution, announced"""
+        if why is None:
+            return self._run(x, _BF16)
+        if x.is_cuda and x.dtype == torch.float32 and self.config_why_not() is None:
+            why32 = self.split_why_not(x)
+            if why32 is None:  # an fp32 model: the general kernel in split precision
+                return self._run(x, _SPLIT)
+            if self._SPLIT_IN_REASON:
+                why = f'{why}; split precision: {why32}'
+        return self._torch_forward(x, why)
+
+    def _torch_forward(self, x, why, *args):
+        _torch_path(self, x, why)
+        return super().forward(x, *args)
+
+
 def pack_conv3d_weights(weight, cin_offset=0, transposed=False):
     """(32, C_in >= 32, 3, 3, 3) fp32/bf16 GPU weight -> MFMA A-operand fragments (+ zero page) for
     the 32 input channels starting at ``cin_offset``.  ``transposed``: fragments of the
@@ -94,11 +153,11 @@ def pack_conv3d_weights(weight, cin_offset=0, transposed=False):
     note_derived_build()
     assert weight.is_cuda and weight.dim() == 5 and weight.shape[0] == 32 and tuple(weight.shape[2:]) == (3, 3, 3)
     w = weight.detach().contiguous()
-    if w.dtype not in _WDT:
+    if w.dtype not in DTYPES:
         w = w.float()
     lib = _capi.lib()
     packed = torch.empty(lib.dfm_conv3d_k3_c32_weight_bytes(), dtype=torch.uint8, device=w.device)
-    launch('dfm_conv3d_k3_c32_pack_weights', w, _WDT[w.dtype], w.shape[1], cin_offset, 1 if transposed else 0, packed,
+    launch('dfm_conv3d_k3_c32_pack_weights', w, DTYPES[w.dtype], w.shape[1], cin_offset, 1 if transposed else 0, packed,
            STREAM)
     return packed
 
@@ -180,43 +239,37 @@ class _MfmaConvFn(torch.autograd.Function):
         return gx, gw, None, None
 
 
-class MfmaConv3d(nn.Conv3d):
+class MfmaConv3d(_MfmaModule, nn.Conv3d):
     """nn.Conv3d(C_in in {32, 64, ...}, 32, 3, stride=1, padding=1, bias=False) whose bf16 / NDHWC
     forward is the hand-written MFMA kernel.  Packed weight fragments are cached and rebuilt when
     the parameter changes (derived.Derived)."""
+    UNCOVERED = 'convolution configuration outside the 32-channel kernel\'s coverage'
+    _SPLIT_IN_REASON = True
+
+    def _covered(self):
+        return (self.out_channels == 32 and self.in_channels % 32 == 0 and self.kernel_size == (3, 3, 3) and
+                self.stride == (1, 1, 1) and self.padding == (1, 1, 1) and self.dilation == (1, 1, 1) and
+                self.groups == 1 and self.bias is None)
 
     def why_not(self, x):
         """None when the MFMA kernel takes ``x``, else the reason it does not"""
-        if not x.is_cuda:
-            return 'CPU tensor'
-        if not (self.out_channels == 32 and self.in_channels % 32 == 0 and self.kernel_size == (3, 3, 3) and
-                self.stride == (1, 1, 1) and self.padding == (1, 1, 1) and self.dilation == (1, 1, 1) and
-                self.groups == 1 and self.bias is None):
-            return 'convolution configuration outside the 32-channel kernel\'s coverage'
-        why = _why_not_bf16_cl(x, 5)
+        why = self._why_not_config(x) or _why_not_bf16_cl(x, 5)
         if why is None and not _ndhwc_channel_stride(x):
             why = 'input is not channels_last_3d (nor a channel slice of an NDHWC tensor)'
         return why
-
-    def eligible(self, x):
-        return self.why_not(x) is None
 
     def _packed(self):
         return derived(self).get('packs', (self.weight,), lambda: [
             pack_conv3d_weights(self.weight, 32 * i) for i in range(self.in_channels // 32)])
 
-    def forward(self, x):
-        why = self.why_not(x)
-        if why is None:
+    def _run(self, x, arith):
+        if arith is _BF16:
             return _MfmaConvFn.apply(x, self.weight, self._packed())
-        if x.is_cuda and x.dtype == torch.float32 and 'coverage' not in why:
-            why32 = _split_why_not(self, x, 'conv')
-            if why32 is None:  # an fp32 model: the general kernel in split precision
-                return _ConvGSplitFn.apply(x, self.weight, _split_packs(self, self.in_channels, 32, False), 'conv',
-                                           self.stride, self.padding)
-            why = f'{why}; split precision: {why32}'
-        _torch_path(self, x, why)
-        return super().forward(x)
+        g = self._geom()
+        return _ConvGFn.apply(x, self.weight, None, g, arith, _split_packs(self, g))
+
+    def forward(self, x):
+        return self._forward(x, self.why_not(x))
 
     def forward_with_stats(self, x):
         """(y, moment partials): the convolution plus the per-channel GroupNorm statistics of y
@@ -227,10 +280,11 @@ class MfmaConv3d(nn.Conv3d):
 # ---------------------------------------------------------------------------------------------
 # backward-weight: MIOpen's untuned bf16 NDHWC kernels for these shapes are 84 ms .. 1.26 s PER
 # CONVOLUTION (naive fallbacks; profiles/archive/r02_c31_train_step_kernel_stats.txt: 2.1 s per training
-# step of DfMBackbone).  Until the MFMA weight-gradient kernel exists, the gradient is a chunked
-# implicit-im2col GEMM: a strided view of the padded input gives the (rows, 27 C_in) patch matrix of
-# a depth chunk, one library GEMM (hipBLASLt, fp32 accumulation over the chunk) contracts it with
-# the output gradient, chunks are summed in fp32.
+# step of DfMBackbone).  ``conv3d_weight_grad`` runs the hand-written MFMA kernel (csrc/conv3d_wgrad.hip)
+# when the channel counts are multiples of 32.  Other channel counts take a chunked implicit-im2col GEMM:
+# a strided view of the padded input gives the (rows, 27 C_in) patch matrix of a depth chunk, one library
+# GEMM (hipBLASLt, fp32 accumulation over the chunk) contracts it with the output gradient, chunks are
+# summed in fp32.
 # ---------------------------------------------------------------------------------------------
 _OUT_DTYPE_OK = {}  # (op name, device type) -> does op(..., out_dtype=torch.float32) work on this build / backend?
 
@@ -463,14 +517,14 @@ def conv3d_to1_norm(y, partials, gamma, beta, eps, weight, relu=True, depth_chun
     N, _, D, H, W = y.shape
     assert partials.shape[:2] == (N, 32) and partials.is_contiguous() and partials.dtype == torch.float32
     w = weight.detach().contiguous()
-    if w.dtype not in _WDT:
+    if w.dtype not in DTYPES:
         w = w.float()
     dev = y.device
     coef = torch.empty((N, 32, 2), dtype=torch.float32, device=dev)
     out = torch.empty((N, 1, D, H, W), dtype=torch.bfloat16, device=dev)
     launch('dfm_group_norm_coefficients', N, 32, 32, float(eps), partials, partials.shape[2], gamma, beta, coef,
            STREAM)
-    launch('dfm_conv3d_to1_norm_fwd', N, D, H, W, y, coef, w, _WDT[w.dtype], 1 if relu else 0, 0, out,
+    launch('dfm_conv3d_to1_norm_fwd', N, D, H, W, y, coef, w, DTYPES[w.dtype], 1 if relu else 0, 0, out,
            int(depth_chunk), STREAM)
     return out
 
@@ -486,23 +540,25 @@ def conv3d_to1(x, weight, depth_chunk=0):
     assert x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == 32 and _is_ndhwc(x)
     N, _, D, H, W = x.shape
     w = weight.detach().contiguous()
-    if w.dtype not in _WDT:
+    if w.dtype not in DTYPES:
         w = w.float()
     coef = _identity_coef.get((x.device, N), (), lambda: torch.tensor(
         [1.0, 0.0], dtype=torch.float32, device=x.device).repeat(N * 32).view(N, 32, 2).contiguous())
     out = torch.empty((N, 1, D, H, W), dtype=torch.bfloat16, device=x.device)
-    launch('dfm_conv3d_to1_norm_fwd', N, D, H, W, x, coef, w, _WDT[w.dtype], 0, 0, out, int(depth_chunk), STREAM)
+    launch('dfm_conv3d_to1_norm_fwd', N, D, H, W, x, coef, w, DTYPES[w.dtype], 0, 0, out, int(depth_chunk), STREAM)
     return out
 
 
 class _MfmaConvTo1Fn(torch.autograd.Function):
-    """Conv3d(32, 1, 3, 1, 1) through the MFMA kernel (weight rows 1..31 zero, channel 0 stored);
-    backward is torch's convolution backward (MIOpen) -- the op is memory-bound either way."""
+    """Conv3d(32, 1, 3, 1, 1): the lean 32 -> 1 kernel (``packed`` None), or the 32 -> 32 kernel on the weight
+    zero-padded to 32 output channels, channel 0 stored (other pixel strides).  Backward: both gradients as
+    matrix products over the 27 taps (csrc/conv3d_to1_bwd.hip) for bf16 NDHWC operands, else the one gradient
+    channel zero-padded to 32 through the 32 -> 32 kernel and ``conv3d_weight_grad``."""
 
     @staticmethod
     def forward(ctx, x, weight, packed):
         ctx.save_for_backward(x, weight)
-        if packed is None:   # the lean 32 -> 1 kernel (round 6)
+        if packed is None:   # the lean 32 -> 1 kernel
             return conv3d_to1(x, weight)
         N, _, D, H, W = x.shape
         out = torch.empty((N, 1, D, H, W), dtype=torch.bfloat16, device=x.device)
@@ -516,18 +572,18 @@ class _MfmaConvTo1Fn(torch.autograd.Function):
         gy = gy.contiguous()
         N, _, D, H, W = gy.shape
         direct = (gy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and _is_ndhwc(x) and
-                  _ndhwc_channel_stride(x) == 32 and weight.dtype in _WDT)
+                  _ndhwc_channel_stride(x) == 32 and weight.dtype in DTYPES)
         if direct:
             # round 6 (csrc/conv3d_to1_bwd.hip): both gradients as matrix products over the 27 taps -- no gradient padded
             # to 32 channels (a 118 MB fill + copy), no 32 -> 32 convolution / weight gradient for one useful row
             wc = weight.detach().contiguous()
             if ctx.needs_input_grad[0]:
                 gxb = torch.empty((N, D, H, W, 32), dtype=torch.bfloat16, device=gy.device)
-                launch('dfm_conv3d_to1_bwd_data', N, D, H, W, gy, wc, _WDT[wc.dtype], gxb, STREAM)
+                launch('dfm_conv3d_to1_bwd_data', N, D, H, W, gy, wc, DTYPES[wc.dtype], gxb, STREAM)
                 gx = gxb.permute(0, 4, 1, 2, 3)
             if ctx.needs_input_grad[1]:
                 gw = torch.empty((1, 32, 3, 3, 3), dtype=weight.dtype, device=gy.device)
-                launch('dfm_conv3d_to1_wgrad', N, D, H, W, x, gy, gw, _WDT[gw.dtype], WS, STREAM,
+                launch('dfm_conv3d_to1_wgrad', N, D, H, W, x, gy, gw, DTYPES[gw.dtype], WS, STREAM,
                        ws_bytes=_capi.lib().dfm_conv3d_to1_wgrad_workspace_bytes())
             return gx, gw, None
         g32 = None
@@ -548,26 +604,26 @@ class _MfmaConvTo1Fn(torch.autograd.Function):
         return gx, gw, None
 
 
-class MfmaConv3dTo1(nn.Conv3d):
+class MfmaConv3dTo1(_MfmaModule, nn.Conv3d):
     """nn.Conv3d(32, 1, 3, 1, 1, bias=False): the prediction convolutions of DfMBackbone
-    (dfm_backbone.py:120-127).  bf16 / NDHWC input: the 32 -> 32 MFMA kernel with a zero-padded
-    weight, storing channel 0 only (MIOpen's untuned kernel for this shape takes 3.4 ms at config K,
-    this one 0.12 ms)."""
+    (dfm_backbone.py:120-127).  bf16 / NDHWC input: the lean 32 -> 1 MFMA kernel (``conv3d_to1``: ~50 us at
+    config K; MIOpen's untuned kernel for this shape takes 3.4 ms); an NDHWC input with another pixel stride runs
+    the 32 -> 32 kernel on the weight zero-padded to 32 output channels, storing channel 0 only (0.12 ms)."""
+    UNCOVERED = 'convolution configuration outside the 32 -> 1 kernel\'s coverage'
+
+    def _covered(self):
+        return (self.in_channels == 32 and self.out_channels == 1 and self.kernel_size == (3, 3, 3) and
+                self.stride == (1, 1, 1) and self.padding == (1, 1, 1) and self.dilation == (1, 1, 1) and
+                self.groups == 1 and self.bias is None)
 
     def why_not(self, x):
-        if not x.is_cuda:
-            return 'CPU tensor'
-        if not (self.in_channels == 32 and self.out_channels == 1 and self.kernel_size == (3, 3, 3) and
-                self.stride == (1, 1, 1) and self.padding == (1, 1, 1) and self.dilation == (1, 1, 1) and
-                self.groups == 1 and self.bias is None):
-            return 'convolution configuration outside the 32 -> 1 kernel\'s coverage'
-        why = _why_not_bf16_cl(x, 5)
+        why = self._why_not_config(x) or _why_not_bf16_cl(x, 5)
         if why is None and not _is_ndhwc(x):
             why = 'input is not channels_last_3d'
         return why
 
-    def eligible(self, x):
-        return self.why_not(x) is None
+    def _geom(self):
+        return ConvGeom(32, 32, (1, 1, 1), (1, 1, 1))   # split precision: the weight zero-padded to 32 outputs
 
     def _packed(self):
         def make():
@@ -576,21 +632,18 @@ class MfmaConv3dTo1(nn.Conv3d):
             return pack_conv3d_weights(w)
         return derived(self).get('pack', (self.weight,), make)
 
-    def forward(self, x):
-        why = self.why_not(x)
-        if why is None:
+    def _run(self, x, arith):
+        if arith is _BF16:
             # (other pixel strides: the 32 -> 32 kernel on the zero-padded weight)
             lean = _ndhwc_channel_stride(x) == 32
             return _MfmaConvTo1Fn.apply(x, self.weight, None if lean else self._packed())
-        if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and 'coverage' not in why and
-                _FP32_MODE['mode'] != 'torch' and x.shape[1] == 32 and
-                conv3d_g_plannable(x.shape[0], 32, 32, tuple(x.shape[2:]), 1, 1)):
-            # an fp32 model: the general kernel in split precision on the weight zero-padded to 32 output
-            # channels (MIOpen's naive kernel takes 1.4 s for this convolution at config K)
-            w32 = torch.cat([self.weight, self.weight.new_zeros((31, 32, 3, 3, 3))], 0)
-            return _ConvGSplitFn.apply(x, w32, None, 'conv', (1, 1, 1), (1, 1, 1))[:, :1].contiguous()
-        _torch_path(self, x, why)
-        return super().forward(x)
+        # an fp32 model: the general kernel in split precision on the weight zero-padded to 32 output
+        # channels (MIOpen's naive kernel takes 1.4 s for this convolution at config K)
+        w32 = torch.cat([self.weight, self.weight.new_zeros((31, 32, 3, 3, 3))], 0)
+        return _ConvGFn.apply(x, w32, None, self._geom(), arith, None)[:, :1].contiguous()
+
+    def forward(self, x):
+        return self._forward(x, self.why_not(x))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -614,11 +667,11 @@ def pack_conv3d_g_weights(weight, cin, cout, swap=False, flip=0):
     assert weight.is_cuda and weight.dim() in (4, 5) and tuple(weight.shape[2:]) == ((3, 3) if two_d else (3, 3, 3))
     assert tuple(weight.shape[:2]) == ((cin, cout) if swap else (cout, cin))
     w = weight.detach().contiguous()
-    if w.dtype not in _WDT:
+    if w.dtype not in DTYPES:
         w = w.float()
     lib = _capi.lib()
     packed = torch.empty(lib.dfm_conv3d_g_weight_bytes(cin, cout), dtype=torch.uint8, device=w.device)
-    launch('dfm_conv3d_g_pack_weights_2d' if two_d else 'dfm_conv3d_g_pack_weights', w, _WDT[w.dtype], cin, cout,
+    launch('dfm_conv3d_g_pack_weights_2d' if two_d else 'dfm_conv3d_g_pack_weights', w, DTYPES[w.dtype], cin, cout,
            1 if swap else 0, int(flip), packed, STREAM)
     return packed
 
@@ -662,38 +715,115 @@ def conv3d_g_out_size(in_size, stride, padding, transposed, kernel1=(False, Fals
                  for s, st, p, t, k1 in zip(in_size, stride, padding, transposed, kernel1))
 
 
+_F3, _K1D = (False, False, False), (True, False, False)
+_PLAN_OK = {}
+# which operand of ``conv3d_weight_grad`` the convolution's input and its output gradient are ('input' |
+# 'grad_output'), and the stride / padding of that launch
+WeightGrad = namedtuple('WeightGrad', 'x_in g_out stride padding')
+
+
+class ConvGeom(namedtuple('ConvGeom', 'cin cout stride padding transposed kernel1 swap flip',
+                          defaults=(_F3, _F3, False, 0))):
+    """One convolution as the general kernel runs it: channel counts, per-axis (d, h, w) ``stride``, ``padding``,
+    ``transposed`` (the x2 transposed convolution: kernel 3, stride 2, padding 1, output_padding 1) and ``kernel1``
+    (kernel extent 1, padding 0), and the layout its weight packs with (``swap`` / ``flip`` of
+    ``pack_conv3d_g_weights``).  A 2-D convolution is a depth-1 volume with kernel extent 1 along depth.  The
+    forward launch, both backward launches and the planner's descriptor all derive from this one value; nothing
+    here touches a tensor."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, m):
+        """the forward launch of an nn.Conv3d / nn.Conv2d (kernel 3) or an nn.ConvTranspose3d / nn.ConvTranspose2d
+        (kernel 3, stride 2, padding 1, output_padding 1); a narrow input (the 3-channel image) counts as one
+        32-channel chunk"""
+        two_d = len(m.kernel_size) == 2
+        k1 = _K1D if two_d else _F3
+        if m.transposed:
+            return cls(m.in_channels, m.out_channels, (1, 1, 1), (0, 1, 1) if two_d else (1, 1, 1),
+                       tuple(not k for k in k1), k1, True)
+        return cls(max(m.in_channels, 32), m.out_channels, (1, *m.stride) if two_d else tuple(m.stride),
+                   (0, *m.padding) if two_d else tuple(m.padding), _F3, k1)
+
+    def out_size(self, in_size):
+        return conv3d_g_out_size(in_size, self.stride, self.padding, self.transposed, self.kernel1)
+
+    def desc(self, n, in_size, relu=False, cstride=0):
+        """the C ABI's descriptor of this convolution on ``n`` inputs of ``in_size`` whose pixels are ``cstride``
+        elements apart (0: dense)"""
+        return _conv_desc(n, self.cin, self.cout, in_size, self.out_size(in_size), self.stride, self.padding,
+                          self.transposed, relu, cstride, self.kernel1)
+
+    def plannable(self, n, in_size, cstride=0):
+        """does ``dfm_conv3d_g_plan`` find a tiling for this problem (sample < 2^31 bytes, a block that
+        fits the LDS, a grid within the launch limits)?  Cached per problem; the Mfma* modules ask before
+        they take the MFMA path, so a shape the kernel rejects runs torch's convolution (with the
+        fallback policy's warning) instead of raising DfmHipError from inside the launch."""
+        key = (n, self.cin, self.cout, tuple(in_size), self.stride, self.padding, self.transposed, self.kernel1,
+               cstride)
+        ok = _PLAN_OK.get(key)
+        if ok is None:
+            plan = (ctypes.c_int64 * 8)()
+            ok = all(o > 0 for o in self.out_size(in_size)) and \
+                _capi.lib().dfm_conv3d_g_plan(ctypes.byref(self.desc(n, in_size, False, cstride)), plan) == 0
+            if len(_PLAN_OK) > 4096:
+                _PLAN_OK.clear()
+            _PLAN_OK[key] = ok
+        return ok
+
+    def torch_padding(self):
+        """padding of the 27-tap convolution that torch and ``conv3d_weight_grad`` see: an extent-1 axis is the
+        centre tap of a padded 3-tap axis"""
+        return tuple(1 if k1 else p for p, k1 in zip(self.padding, self.kernel1))
+
+    def backward_data(self, in_size):
+        """the launch that turns the output gradient into the gradient of an input of ``in_size``: the same kernel
+        on the channel-swapped weights.  Of a correlation it mirrors the stride-1 axes, and a stride-2 axis comes
+        back as a transposed axis when its padding is 1 and its extent even -- None when one is not (the caller
+        takes aten's convolution_backward); of a transposed convolution it is the stride-2 correlation."""
+        if any(self.transposed):
+            return ConvGeom(self.cout, self.cin, tuple(2 if t else 1 for t in self.transposed), self.padding, _F3,
+                            self.kernel1, False, 0)
+        if not all(st == 1 or (st == 2 and p == 1 and s % 2 == 0 and not k1)
+                   for s, st, p, k1 in zip(in_size, self.stride, self.padding, self.kernel1)):
+            return None
+        return ConvGeom(self.cout, self.cin, (1, 1, 1),
+                        tuple(0 if k1 else 2 - p for p, k1 in zip(self.padding, self.kernel1)),
+                        tuple(st == 2 for st in self.stride), self.kernel1, True,
+                        sum(b for b, st in zip((4, 2, 1), self.stride) if st == 1))
+
+    def backward_weight(self):
+        """the ``conv3d_weight_grad`` launch whose result has the module's weight layout: a correlation contracts
+        its input against the output gradient; a transposed convolution is the stride-2 correlation the other way
+        round, so the operands swap"""
+        if any(self.transposed):
+            return WeightGrad('grad_output', 'input', tuple(2 if t else 1 for t in self.transposed), (1, 1, 1))
+        return WeightGrad('input', 'grad_output', self.stride, self.torch_padding())
+
+
 def conv3d_g_plan(n, cin, cout, in_size, stride=1, padding=1, transposed=False):
     """The tiling the kernel picks: dict(pfw, cw, tile, block_px, lds, workgroups)."""
-    stride, padding = _triple(stride), _triple(padding)
-    transposed = _triple(transposed)
-    out_size = conv3d_g_out_size(in_size, stride, padding, transposed)
-    d = _conv_desc(n, cin, cout, in_size, out_size, stride, padding, transposed, False)
+    d = ConvGeom(cin, cout, _triple(stride), _triple(padding), _triple(transposed)).desc(n, in_size)
     plan = (ctypes.c_int64 * 8)()
     _capi.check(_capi.lib().dfm_conv3d_g_plan(ctypes.byref(d), plan))
     return dict(pfw=plan[0], cw=plan[1], tile=(plan[2], plan[3], plan[4]), block_px=plan[5], lds=plan[6],
                 workgroups=plan[7])
 
 
-_PLAN_OK = {}
-
-
 def conv3d_g_plannable(n, cin, cout, in_size, stride, padding, transposed=False, kernel1=False, in_channel_stride=0):
-    """does ``dfm_conv3d_g_plan`` find a tiling for this problem (sample < 2^31 bytes, a block that
-    fits the LDS, a grid within the launch limits)?  Cached per problem; the Mfma* modules ask before
-    they take the MFMA path, so a shape the kernel rejects runs torch's convolution (with the
-    fallback policy's warning) instead of raising DfmHipError from inside the launch."""
-    stride, padding, transposed, kernel1 = _triple(stride), _triple(padding), _triple(transposed), _triple(kernel1)
-    key = (n, cin, cout, tuple(in_size), stride, padding, transposed, kernel1, in_channel_stride)
-    ok = _PLAN_OK.get(key)
-    if ok is None:
-        out_size = conv3d_g_out_size(in_size, stride, padding, transposed, kernel1)
-        d = _conv_desc(n, cin, cout, in_size, out_size, stride, padding, transposed, False, in_channel_stride, kernel1)
-        plan = (ctypes.c_int64 * 8)()
-        ok = all(o > 0 for o in out_size) and _capi.lib().dfm_conv3d_g_plan(ctypes.byref(d), plan) == 0
-        if len(_PLAN_OK) > 4096:
-            _PLAN_OK.clear()
-        _PLAN_OK[key] = ok
-    return ok
+    """``ConvGeom.plannable`` of a problem given by its numbers"""
+    return ConvGeom(cin, cout, _triple(stride), _triple(padding), _triple(transposed),
+                    _triple(kernel1)).plannable(n, in_size, in_channel_stride)
+
+
+def _g_problem(x, cout, stride, padding, transposed, kernel1, relu=False):
+    """what ``conv3d_g`` and ``conv3d_g_f32`` share: the checked input's descriptor and the NDHWC shape of the
+    output"""
+    cstride = _ndhwc_channel_stride(x)
+    assert x.is_cuda and x.dtype == torch.bfloat16 and cstride, 'bf16 channels_last_3d (or a channel slice of it)'
+    g = ConvGeom(x.shape[1], cout, _triple(stride), _triple(padding), _triple(transposed), _triple(kernel1))
+    d = g.desc(x.shape[0], tuple(x.shape[2:]), relu, cstride)
+    return d, (x.shape[0], *d.out_size, cout)
 
 
 def conv3d_g(x, packed, cout, stride=1, padding=1, transposed=False, relu=False, scale=None, shift=None,
@@ -702,21 +832,14 @@ def conv3d_g(x, packed, cout, stride=1, padding=1, transposed=False, relu=False,
     channels_last_3d = relu?(conv(x) * scale + shift + residual).  ``transposed``: per-axis flags of
     the x2 transposed convolution (kernel 3, stride 2, padding 1, output_padding 1); ``kernel1``:
     per-axis flags of kernel extent 1 (padding 0; the packed 27-tap weights' centre index is used)."""
-    cstride = _ndhwc_channel_stride(x)
-    assert x.is_cuda and x.dtype == torch.bfloat16 and cstride, 'bf16 channels_last_3d (or a channel slice of it)'
-    stride, padding, transposed = _triple(stride), _triple(padding), _triple(transposed)
-    kernel1 = _triple(kernel1)
-    N, cin = x.shape[:2]
-    in_size = tuple(x.shape[2:])
-    out_size = conv3d_g_out_size(in_size, stride, padding, transposed, kernel1)
-    out = torch.empty((N, *out_size, cout), dtype=torch.bfloat16, device=x.device)
-    d = _conv_desc(N, cin, cout, in_size, out_size, stride, padding, transposed, relu, cstride, kernel1)
+    d, shape = _g_problem(x, cout, stride, padding, transposed, kernel1, relu)
+    out = torch.empty(shape, dtype=torch.bfloat16, device=x.device)
     if scale is not None:
         scale, shift = scale.float().contiguous(), shift.float().contiguous()
         assert scale.numel() == cout and shift.numel() == cout
     if residual is not None:
-        assert residual.dtype == torch.bfloat16 and tuple(residual.shape) == (N, cout, *out_size) and \
-            _is_ndhwc(residual)
+        assert residual.dtype == torch.bfloat16 and _is_ndhwc(residual) and \
+            tuple(residual.shape) == (shape[0], cout, *shape[1:4])
     launch('dfm_conv3d_g_fwd', d, x, packed, scale, shift, residual, out, STREAM)
     return out.permute(0, 4, 1, 2, 3)
 
@@ -725,18 +848,12 @@ def conv3d_g_f32(x, packed, cout, stride=1, padding=1, transposed=False, kernel1
     """The general kernel with its fp32 accumulators stored as they are (``dfm_conv3d_g_fwd_f32``):
     x (N, C_in, D, H, W) bf16 channels_last_3d -> fp32 (N, D', H', W', cout), plus ``acc`` (same shape;
     accumulated in place when given)."""
-    cstride = _ndhwc_channel_stride(x)
-    assert x.is_cuda and x.dtype == torch.bfloat16 and cstride, 'bf16 channels_last_3d (or a channel slice of it)'
-    stride, padding, transposed, kernel1 = _triple(stride), _triple(padding), _triple(transposed), _triple(kernel1)
-    N, cin = x.shape[:2]
-    in_size = tuple(x.shape[2:])
-    out_size = conv3d_g_out_size(in_size, stride, padding, transposed, kernel1)
+    d, shape = _g_problem(x, cout, stride, padding, transposed, kernel1)
     if acc is not None:
-        assert acc.dtype == torch.float32 and tuple(acc.shape) == (N, *out_size, cout) and acc.is_contiguous()
+        assert acc.dtype == torch.float32 and tuple(acc.shape) == shape and acc.is_contiguous()
         out = acc
     else:
-        out = torch.empty((N, *out_size, cout), dtype=torch.float32, device=x.device)
-    d = _conv_desc(N, cin, cout, in_size, out_size, stride, padding, transposed, False, cstride, kernel1)
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
     launch('dfm_conv3d_g_fwd_f32', d, x, packed, acc, out, STREAM)
     return out
 
@@ -815,94 +932,213 @@ def conv3d_weight_grad_split(x_in, g_out, stride, padding):
     return out
 
 
-class _ConvGSplitFn(torch.autograd.Function):
-    """nn.Conv3d / nn.ConvTranspose3d (k3 s2 p1 op1) of an fp32 model through the MFMA kernels in split
-    precision; input and output keep the caller's layout (NCDHW for the reference's pipeline).
-    ``two_d``: x is a depth-1 view of an NCHW / NHWC tensor and weight a 2-D kernel embedded in the centre
-    depth slice (``_embed2d``): kernel extent 1 along depth, stride / transposition on (h, w) only."""
+def _split_packs(module, g):
+    """fragment buffers of the bf16 pieces of the module's fp32 weight, cached per weight version"""
+    return derived(module).get('split_packs', (module.weight,), lambda: [
+        pack_conv3d_g_weights(w, g.cin, g.cout, swap=g.swap) for w in split_pieces(module.weight.detach().float())],
+        (_FP32_MODE['mode'], g.swap))
+
+
+def _embed2d(w):
+    """(a, b, 3, 3) -> (a, b, 3, 3, 3) with the 2-D kernel in the centre depth slice"""
+    w3 = w.new_zeros((*w.shape[:2], 3, 3, 3))
+    w3[:, :, 1] = w
+    return w3
+
+
+def _pad_to_chunk(t, ndhwc=False):
+    """``t`` with zero channels (dim 1) up to one 32-channel chunk: the 3-channel image of upconv_module's last skip
+    (spp_unet_neck.py:51-56) and the weight that reads it.  ``ndhwc``: the copy has its channels innermost, whatever
+    the layout of ``t`` (one small copy, 26 MB at 320 x 1280); else it is dense."""
+    if t.shape[1] >= 32:
+        return t
+    if not ndhwc:
+        return torch.cat([t, t.new_zeros((t.shape[0], 32 - t.shape[1], *t.shape[2:]))], 1)
+    p = t.new_zeros((t.shape[0], *t.shape[2:], 32))
+    p[..., :t.shape[1]] = t.movedim(1, -1)
+    return p.movedim(-1, 1)
+
+
+# ---------------------------------------------------------------------------------------------
+# The two arithmetics of a general-kernel convolution under autograd.  ``conv(x, weight, geom, packs, shift)``
+# is one product (forward or backward-data) -> (N, geom.cout, D', H', W') channels-last; ``wgrad(x_in, g_out,
+# stride, padding, dtype)`` the weight gradient; ``ndhwc``: the operands must be NDHWC tensors already (split
+# precision makes channels-last copies of its own while it cuts them into pieces).
+#   bf16:  one ``conv3d_g`` launch per product (a bias rides in the epilogue), ``conv3d_weight_grad``
+#   split: ``conv3d_g_split`` and ``conv3d_weight_grad_split`` over ``_split_pairs``
+# ---------------------------------------------------------------------------------------------
+def _conv_bf16(x, weight, g, packed=None, shift=None):
+    if packed is None:
+        packed = pack_conv3d_g_weights(weight, g.cin, g.cout, swap=g.swap, flip=g.flip)
+    return conv3d_g(x, packed, g.cout, g.stride, g.padding, g.transposed, kernel1=g.kernel1,
+                    scale=None if shift is None else torch.ones_like(shift), shift=shift)
+
+
+def _conv_split(x, weight, g, packs=None, shift=None):
+    if weight.dim() == 4:
+        weight = _embed2d(weight)
+    y = conv3d_g_split(x, weight, g.cin, g.cout, swap=g.swap, flip=g.flip, stride=g.stride, padding=g.padding,
+                       transposed=g.transposed, kernel1=g.kernel1, packs=packs)
+    return y if shift is None else y + shift.view(1, -1, 1, 1, 1)
+
+
+def _wgrad_bf16(x_in, g_out, stride, padding, dtype):
+    return conv3d_weight_grad(x_in, g_out, stride, padding, out_dtype=dtype)
+
+
+def _wgrad_split(x_in, g_out, stride, padding, dtype):
+    return conv3d_weight_grad_split(x_in, g_out, stride, padding).to(dtype)
+
+
+_Arithmetic = namedtuple('_Arithmetic', 'conv wgrad ndhwc')
+_BF16 = _Arithmetic(_conv_bf16, _wgrad_bf16, True)
+_SPLIT = _Arithmetic(_conv_split, _wgrad_split, False)
+
+
+class _ConvGFn(torch.autograd.Function):
+    """A convolution of geometry ``geom`` (ConvGeom) in arithmetic ``arith`` (_BF16 | _SPLIT) through the general
+    MFMA kernel: forward, backward-data (``geom.backward_data``; aten's convolution_backward where that is None)
+    and backward-weight (``geom.backward_weight``, csrc/conv3d_wgrad.hip).  ``x`` and ``weight`` are the module's
+    own: a 2-D call (spp_unet_neck.py:93-119, bev_hourglass.py:36-137, conv_modules.py:152-214) enters as a
+    depth-1 view and leaves through ``squeeze(2)``, a narrow input and its weight are zero-padded to one chunk
+    and their gradients sliced back, a bias is added (its gradient: the sum of the output gradient), and output
+    and input gradient keep the caller's layout -- channels-last when the input was (or was read in place as a
+    channel slice of an NDHWC tensor), else dense, so the torch ops either side are untouched."""
 
     @staticmethod
-    def forward(ctx, x, weight, packs, kind, stride, padding, two_d=False):
+    def forward(ctx, x, weight, bias, geom, arith, packs):
         cl = torch.channels_last_3d
-        keep_cl = x.is_contiguous(memory_format=cl) and not x.is_contiguous()
-        xd = x.detach()
-        k1 = (True, False, False) if two_d else False
-        if kind == 'conv':
-            cout, cin = weight.shape[:2]
-            y = conv3d_g_split(xd, weight, cin, cout, stride=stride, padding=padding, kernel1=k1, packs=packs)
-        else:
-            cin, cout = weight.shape[:2]
-            y = conv3d_g_split(xd, weight, cin, cout, swap=True, stride=1, padding=(0, 1, 1) if two_d else 1,
-                               transposed=(False, True, True) if two_d else True, kernel1=k1, packs=packs)
-        ctx.save_for_backward(x, weight)
-        ctx.cfg = (kind, stride, padding, keep_cl, two_d)
+        two_d = x.dim() == 4
+        x5 = x.unsqueeze(2) if two_d else x
+        keep_cl = (x5.is_contiguous(memory_format=cl) and not x5.is_contiguous()) or \
+            bool(arith.ndhwc and _ndhwc_channel_stride(x5))
+        cin, w = x.shape[1], weight.detach()
+        if cin < geom.cin:
+            x5, w = _pad_to_chunk(x5, ndhwc=True), _pad_to_chunk(w)
+        elif arith.ndhwc and not keep_cl:
+            x5 = x5.contiguous(memory_format=cl)
+        y = arith.conv(x5, w, geom, packs, None if bias is None else bias.detach().float())
+        ctx.save_for_backward(x5, weight)
+        ctx.cfg = (geom, arith, cin, keep_cl, two_d, bias is not None)
+        if two_d:
+            y = y.squeeze(2)
         return y if keep_cl else y.contiguous()
 
     @staticmethod
     def backward(ctx, gy):
-        x, weight = ctx.saved_tensors
-        kind, stride, padding, keep_cl, two_d = ctx.cfg
-        gx = gw = None
-        in_size = tuple(x.shape[2:])
-        w = weight.detach().float()
-        k1 = (True, False, False) if two_d else False
-        wpad = (1, 1, 1) if two_d else None   # weight gradient of a depth-1 volume: the 27-tap kernel, depth padded
-        if kind == 'conv':
-            cout, cin = weight.shape[:2]
-            stride, padding = _triple(stride), _triple(padding)
-            if ctx.needs_input_grad[0]:
-                if _bwd_data_supported(in_size, stride, (1, 1, 1) if two_d else padding):
-                    up = tuple(st == 2 for st in stride)
-                    flip = sum(b for b, st in zip((4, 2, 1), stride) if st == 1)
-                    bpad = (0, 1, 1) if two_d else tuple(2 - p for p in padding)
-                    gx = conv3d_g_split(gy, w, cout, cin, swap=True, flip=flip, stride=1, padding=bpad,
-                                        transposed=up, kernel1=k1)
-                else:
-                    gx = torch.ops.aten.convolution_backward(
-                        gy, x, w, None, list(stride), list((1, 1, 1) if two_d else padding), [1, 1, 1], False,
-                        [0, 0, 0], 1, [True, False, False])[0]
-            if ctx.needs_input_grad[1]:
-                gw = conv3d_weight_grad_split(x, gy, stride, wpad or padding).to(weight.dtype)
-        else:
-            cin, cout = weight.shape[:2]
-            if ctx.needs_input_grad[0]:
-                gx = conv3d_g_split(gy, w, cout, cin, swap=False, flip=0, stride=(1, 2, 2) if two_d else 2,
-                                    padding=(0, 1, 1) if two_d else 1, kernel1=k1)
-            if ctx.needs_input_grad[1]:
-                gw = conv3d_weight_grad_split(gy, x, (1, 2, 2) if two_d else 2, wpad or 1).to(weight.dtype)
-        if gx is not None and not keep_cl:
-            gx = gx.contiguous()
-        return gx, gw, None, None, None, None, None
+        x5, weight = ctx.saved_tensors
+        geom, arith, cin, keep_cl, two_d, has_bias = ctx.cfg
+        g5 = gy.unsqueeze(2) if two_d else gy
+        if arith.ndhwc:
+            g5 = g5.contiguous(memory_format=torch.channels_last_3d)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            w = _pad_to_chunk(weight.detach()) if cin < geom.cin else weight.detach()
+            back = geom.backward_data(tuple(x5.shape[2:]))
+            if back is not None:
+                gx = arith.conv(g5, w, back)
+            else:
+                w5 = _embed2d(w) if two_d else w
+                gx = torch.ops.aten.convolution_backward(
+                    g5, x5, w5.to(x5.dtype), None, list(geom.stride), list(geom.torch_padding()), [1, 1, 1], False,
+                    [0, 0, 0], 1, [True, False, False])[0]
+            if cin < geom.cin:
+                gx = gx[:, :cin]
+            if two_d:
+                gx = gx.squeeze(2)
+            if not keep_cl:
+                gx = gx.contiguous()
+        if ctx.needs_input_grad[1]:
+            wg = geom.backward_weight()
+            ops = {'input': x5, 'grad_output': g5}
+            gw = arith.wgrad(ops[wg.x_in], ops[wg.g_out], wg.stride, wg.padding, weight.dtype)
+            if cin < geom.cin:
+                gw = gw[:, :cin]
+            if two_d:
+                gw = gw[:, :, 1]
+        if has_bias and ctx.needs_input_grad[2]:
+            gb = g5.float().sum((0, 2, 3, 4)).to(weight.dtype)
+        return gx, gw, gb, None, None, None
 
 
-def _split_why_not(module, x, kind):
-    """why an fp32 CUDA input does NOT take the split-precision MFMA path (None: it does)"""
-    if _FP32_MODE['mode'] == 'torch':
-        return 'set_fp32_mode("torch")'
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and x.shape[1] == module.in_channels):
-        return 'not an fp32 GPU call of this module'
-    n, size = x.shape[0], tuple(x.shape[2:])
-    if kind == 'conv':
-        if not all(s + 2 * p >= 3 for s, p in zip(size, module.padding)):
+class MfmaConv3dG(_MfmaModule, nn.Conv3d):
+    """nn.Conv3d(32 j, 32 k, 3, stride in {1, 2}, padding in {0, 1, 2}, bias=False) whose bf16 /
+    NDHWC forward is the general MFMA kernel; an fp32 GPU input runs the same kernel in split precision; any
+    other input takes torch's convolution (MIOpen), the module's other documented path.  ``forward_fused`` folds a
+    per-channel scale / shift (an eval-mode BatchNorm3d), a residual and the ReLU into the epilogue (inference)."""
+    UNCOVERED = 'convolution configuration outside the general kernel\'s coverage'
+    _SPLIT_IN_REASON = True
+
+    def _covered(self):
+        return (self.in_channels % 32 == 0 and self.out_channels % 32 == 0 and self.kernel_size == (3, 3, 3) and
+                all(s in (1, 2) for s in self.stride) and all(0 <= p <= 2 for p in self.padding) and
+                self.dilation == (1, 1, 1) and self.groups == 1 and self.bias is None and
+                self.padding_mode == 'zeros')
+
+    def why_not(self, x):
+        why = self._why_not_config(x) or _why_not_bf16_cl(x, 5)
+        if why is not None:
+            return why
+        cs = _ndhwc_channel_stride(x)
+        if not cs:
+            return 'input is not channels_last_3d (nor a channel slice of an NDHWC tensor)'
+        if not all(s + 2 * p >= 3 for s, p in zip(x.shape[2:], self.padding)):
             return 'input smaller than the kernel'
-        ok = conv3d_g_plannable(n, module.in_channels, module.out_channels, size, module.stride, module.padding)
-    else:
-        ok = conv3d_g_plannable(n, module.in_channels, module.out_channels, size, 1, 1, transposed=True)
-    return None if ok else 'no tiling of the general kernel fits this shape'
+        if not self._geom().plannable(x.shape[0], tuple(x.shape[2:]), 0 if cs == self.in_channels else cs):
+            return 'no tiling of the general kernel fits this shape'
+        return None
+
+    def _packed(self):
+        return derived(self).get('pack', (self.weight,), lambda: pack_conv3d_g_weights(
+            self.weight, self.in_channels, self.out_channels, swap=self.transposed))
+
+    def _run(self, x, arith):
+        g = self._geom()
+        return _ConvGFn.apply(x, self.weight, None, g, arith,
+                              self._packed() if arith is _BF16 else _split_packs(self, g))
+
+    def forward(self, x):
+        return self._forward(x, self.why_not(x))
+
+    def forward_fused(self, x, scale=None, shift=None, residual=None, relu=False):
+        """inference only (no autograd): relu?(conv(x) * scale + shift + residual)"""
+        assert self.eligible(x)
+        return conv3d_g(x, self._packed(), self.out_channels, self.stride, self.padding, relu=relu,
+                        scale=scale, shift=shift, residual=residual)
 
 
-def _split_packs(module, cin, cout, swap):
-    """(hi, lo) fragment buffers of the module's fp32 weight, cached per weight version"""
-    return derived(module).get('split_packs', (module.weight,), lambda: [
-        pack_conv3d_g_weights(w, cin, cout, swap=swap) for w in split_pieces(module.weight.detach().float())],
-        (_FP32_MODE['mode'], swap))
+class MfmaConvTranspose3d(_MfmaModule, nn.ConvTranspose3d):
+    """nn.ConvTranspose3d(32 j, 32 k, 3, stride=2, padding=1, output_padding=1, bias=False) of the
+    hourglass (conv_modules.py:101-117): evaluated per output parity class on the low-resolution
+    input by the general MFMA kernel when the input is bf16 / NDHWC (fp32: in split precision)."""
+    UNCOVERED = 'transposed-convolution configuration outside the general kernel\'s coverage'
+    _SPLIT_IN_REASON = True
+    _packed, _run = MfmaConv3dG._packed, MfmaConv3dG._run
+
+    def _covered(self):
+        return (self.in_channels % 32 == 0 and self.out_channels % 32 == 0 and self.kernel_size == (3, 3, 3) and
+                self.stride == (2, 2, 2) and self.padding == (1, 1, 1) and self.output_padding == (1, 1, 1) and
+                self.dilation == (1, 1, 1) and self.groups == 1 and self.bias is None)
+
+    def why_not(self, x):
+        why = self._why_not_config(x) or _why_not_bf16_cl(x, 5)
+        if why is None and not _is_ndhwc(x):
+            why = 'input is not channels_last_3d'
+        if why is None and not self._geom().plannable(x.shape[0], tuple(x.shape[2:])):
+            why = 'no tiling of the general kernel fits this shape'
+        return why
+
+    def forward(self, x, output_size=None):
+        if output_size is not None:
+            return self._torch_forward(x, 'explicit output_size', output_size)
+        return self._forward(x, self.why_not(x))
 
 
 # ---------------------------------------------------------------------------------------------
 # 2-D 3x3 convolutions through the same kernel: an NHWC (channels_last) tensor is a depth-1 NDHWC
 # volume and the kernel is (1, 3, 3).  The 2-D producers / consumers either side of the path
 # (SURVEY.md 8f rank 3): SPPUNetNeck (necks/spp_unet_neck.py), BEVHourglass / hourglass2d
-# (backbones/bev_hourglass.py, utils/conv_modules.py).  Inference (no autograd through these).
+# (backbones/bev_hourglass.py, utils/conv_modules.py).
 # ---------------------------------------------------------------------------------------------
 def pack_conv2d_g_weights(weight, cin, cout, swap=False):
     """torch 2-D weight (dim0, dim1, 3, 3) -> the 27-tap fragment buffer with the 2-D kernel in its
@@ -913,7 +1149,7 @@ def pack_conv2d_g_weights(weight, cin, cout, swap=False):
 
 def conv2d_g_why_not(x, cin, cout):
     """inference path: a bf16 channels_last input under no_grad (training goes through
-    ``_Conv2dGFn``, which takes any layout: ``MfmaConv2d.train_why_not``)"""
+    ``_ConvGFn``, which takes any layout: ``train_why_not``)"""
     if not x.is_cuda:
         return 'CPU tensor'
     if cin % 32 or cout % 32:
@@ -947,102 +1183,51 @@ def conv2d_g(x, packed, cout, stride=1, transposed=False, relu=False, scale=None
     return y.squeeze(2)
 
 
-def _embed2d(w):
-    """(a, b, 3, 3) -> (a, b, 3, 3, 3) with the 2-D kernel in the centre depth slice"""
-    w3 = w.new_zeros((*w.shape[:2], 3, 3, 3))
-    w3[:, :, 1] = w
-    return w3
+class _Mfma2dModule(_MfmaModule):
+    """the two 2-D modules: without autograd a bf16 channels_last input runs one fused launch on the weight packed
+    once per version; with autograd recording, ``_ConvGFn`` (any layout in, the caller's layout out)"""
+    _DIMS = 4
+
+    def _recording(self, x):
+        return torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad)
+
+    def train_why_not(self, x):
+        """why a call with autograd recording does NOT take the MFMA kernels (None: it does)"""
+        why = self._why_not_config(x)
+        g = self._geom()
+        if why is None and (g.cin % 32 or g.cout % 32):
+            why = self.UNCOVERED
+        if why is not None:
+            return why
+        if x.dim() != 4 or x.shape[1] != self.in_channels or x.dtype != torch.bfloat16 or \
+                self.weight.dtype != torch.bfloat16:
+            return 'not a bf16 call of this module'
+        n, size = x.shape[0], (1, x.shape[2], x.shape[3])
+        back = g.backward_data(size)
+        if back is None:
+            return 'odd extent under stride 2 (backward-data is a transposed convolution)'
+        if not (g.plannable(n, size) and back.plannable(n, g.out_size(size))):
+            return 'no tiling of the general kernel fits this shape'
+        return None
+
+    def _run(self, x, arith):
+        if arith is _BF16 and not self._recording(x):
+            return self.forward_fused(x)
+        return _ConvGFn.apply(x, self.weight, self.bias, self._geom(), arith, None)
 
 
-class _Conv2dGFn(torch.autograd.Function):
-    """Training path of the 2-D 3x3 convolutions of SPPUNetNeck / BEVHourglass (spp_unet_neck.py:93-119,
-    bev_hourglass.py:36-137, conv_modules.py:152-214): forward, backward-data and backward-weight in the
-    hand-written MFMA kernels (csrc/conv3d_g.hip with a (1, 3, 3) kernel, csrc/conv3d_wgrad.hip) on NHWC
-    copies of the operands; input and output keep the CALLER's layout, so the torch ops either side
-    (BatchNorm, bilinear resize, concatenation: NCHW while training) are untouched.
-    kind 'conv': nn.Conv2d k3 p1 stride 1 | 2 (+bias); 'convT': nn.ConvTranspose2d k3 s2 p1 op1."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, kind, stride):
-        cl = torch.channels_last
-        keep_cl = x.is_contiguous(memory_format=cl) and not x.is_contiguous()
-        xcl = x.detach().contiguous(memory_format=cl)
-        cin = weight.shape[1] if kind == 'conv' else weight.shape[0]
-        cout = weight.shape[0] if kind == 'conv' else weight.shape[1]
-        w = weight.detach()
-        if cin < 32:  # the 3-channel image skip: zero channels up to one 32-channel chunk
-            B, C, H, W = xcl.shape
-            xp = xcl.new_zeros((B, H, W, 32))
-            xp[..., :C] = xcl.permute(0, 2, 3, 1)
-            xcl = xp.permute(0, 3, 1, 2)
-            w = torch.cat([w, w.new_zeros(w.shape[0], 32 - cin, 3, 3)], 1)
-        cin_p = max(cin, 32)
-        scale = shift = None
-        if bias is not None:
-            shift = bias.detach().float()
-            scale = torch.ones_like(shift)
-        if kind == 'conv':
-            packed = pack_conv2d_g_weights(w, cin_p, cout)
-            y = conv2d_g(xcl, packed, cout, stride=stride, scale=scale, shift=shift)
-        else:
-            packed = pack_conv2d_g_weights(w, cin_p, cout, swap=True)
-            y = conv2d_g(xcl, packed, cout, transposed=True)
-        ctx.save_for_backward(xcl, weight)
-        ctx.cfg = (kind, stride, cin, cout, bias is not None, keep_cl)
-        return y if keep_cl else y.contiguous()
-
-    @staticmethod
-    def backward(ctx, gy):
-        xcl, weight = ctx.saved_tensors
-        kind, stride, cin, cout, has_bias, keep_cl = ctx.cfg
-        cin_p = max(cin, 32)
-        gcl = gy.contiguous(memory_format=torch.channels_last)
-        g5, x5 = gcl.unsqueeze(2), xcl.unsqueeze(2)
-        k1 = (True, False, False)
-        gx = gw = gb = None
-        w = weight.detach()
-        if kind == 'conv':
-            if cin < 32:
-                w = torch.cat([w, w.new_zeros(w.shape[0], 32 - cin, 3, 3)], 1)
-            if ctx.needs_input_grad[0]:
-                # backward-data = the same kernel on the mirrored, channel-swapped weights; a stride-2 axis
-                # becomes a transposed axis (even extents, padding 1: MfmaConv2d.train_why_not)
-                up = stride == 2
-                pk = pack_conv3d_g_weights(w, cout, cin_p, swap=True, flip=4 if up else 7)
-                gx = conv3d_g(g5, pk, cin_p, stride=1, padding=(0, 1, 1), transposed=(False, up, up),
-                              kernel1=k1).squeeze(2)[:, :cin]
-            if ctx.needs_input_grad[1]:
-                gw = conv3d_weight_grad(x5, g5, (1, stride, stride), (1, 1, 1))[:, :cin, 1].to(weight.dtype)
-            if has_bias and ctx.needs_input_grad[2]:
-                gb = gcl.float().sum((0, 2, 3)).to(weight.dtype)
-        else:
-            if ctx.needs_input_grad[0]:
-                pk = pack_conv3d_g_weights(w, cout, cin, swap=False, flip=0)
-                gx = conv3d_g(g5, pk, cin, stride=(1, 2, 2), padding=(0, 1, 1), kernel1=k1).squeeze(2)
-            if ctx.needs_input_grad[1]:
-                gw = conv3d_weight_grad(g5, x5, (1, 2, 2), (1, 1, 1))[:, :, 1].to(weight.dtype)
-        if gx is not None and not keep_cl:
-            gx = gx.contiguous()
-        return gx, gw, gb, None, None
-
-
-class _Mfma2dMixin:
-    """packs the 2-D weight once per version (inference: the weights do not change between calls)"""
-
-    def _packed2d(self, cin, cout, swap):
-        return derived(self).get('pack2d', (self.weight,),
-                                 lambda: pack_conv2d_g_weights(self.weight, cin, cout, swap=swap))
-
-
-class MfmaConv2d(nn.Conv2d, _Mfma2dMixin):
+class MfmaConv2d(_Mfma2dModule, nn.Conv2d):
     """nn.Conv2d (same parameters / state_dict keys).  kernel 3, padding 1, stride 1 | 2, dilation 1,
-    groups 1, channels = 32 k, bf16 channels_last input under no_grad: the hand-written MFMA kernel
-    (csrc/conv3d_g.hip with a (1, 3, 3) kernel); anything else: torch's convolution, the module's other
-    documented path.  ``forward_fused`` = relu?(conv(x) * scale + shift + residual) in one launch
-    (eval-mode BatchNorm / bias folded into the epilogue)."""
+    groups 1, channels = 32 k (or a narrow input, zero-padded to one chunk): the hand-written MFMA kernel
+    (csrc/conv3d_g.hip with a (1, 3, 3) kernel) for bf16 inputs -- one fused launch without autograd, forward,
+    backward-data and backward-weight with it -- and in split precision for fp32 ones; anything else: torch's
+    convolution, the module's other documented path.  ``forward_fused`` = relu?(conv(x) * scale + shift +
+    residual) in one launch (eval-mode BatchNorm / bias folded into the epilogue)."""
+    UNCOVERED = 'convolution configuration outside the kernel\'s coverage (3x3, padding 1, stride 1 | 2)'
 
     @staticmethod
-    def covers(in_channels, out_channels, kernel_size, stride=1, padding=0):
+    def covers(in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1,
+               padding_mode='zeros'):
         """would an ``MfmaConv2d`` of this configuration ever reach an MFMA / matrix-product path?  (what
         ``modules.ConvModule`` asks before choosing this class over a plain nn.Conv2d: 3x3 / padding 1 /
         stride 1 | 2 with whole 32-channel chunks -- or a narrow input padded to one chunk -- and 1x1 / stride 1 /
@@ -1051,21 +1236,19 @@ class MfmaConv2d(nn.Conv2d, _Mfma2dMixin):
         k, st, pd = pair(kernel_size), pair(stride), pair(padding)
         if k == (1, 1):
             return st == (1, 1) and pd == (0, 0)
-        return (k == (3, 3) and pd == (1, 1) and st in ((1, 1), (2, 2)) and out_channels % 32 == 0 and
+        return (k == (3, 3) and pd == (1, 1) and pair(dilation) == (1, 1) and groups == 1 and
+                st in ((1, 1), (2, 2)) and padding_mode == 'zeros' and out_channels % 32 == 0 and
                 (in_channels % 32 == 0 or in_channels < 32))
 
-    def _cin_padded(self):
-        """input channels as the kernel sees them: a narrow input (the 3-channel image of
-        upconv_module's last skip, spp_unet_neck.py:51-56) is zero-padded to one 32-channel chunk"""
-        return 32 if self.in_channels < 32 else self.in_channels
+    def _covered(self):
+        return self.kernel_size == (3, 3) and self.covers(
+            self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding, self.dilation,
+            self.groups, self.padding_mode)
 
     def why_not(self, x):
-        if not x.is_cuda:
-            return 'CPU tensor'
-        if not (self.kernel_size == (3, 3) and self.padding == (1, 1) and self.dilation == (1, 1) and
-                self.groups == 1 and self.stride in ((1, 1), (2, 2)) and self.padding_mode == 'zeros' and
-                self.out_channels % 32 == 0 and (self.in_channels % 32 == 0 or self.in_channels < 32)):
-            return 'convolution configuration outside the kernel\'s coverage (3x3, padding 1, stride 1 | 2)'
+        why = self._why_not_config(x)
+        if why is not None:
+            return why
         if x.dim() != 4 or x.shape[1] != self.in_channels:
             return 'input shape does not match the module'
         if self.in_channels >= 32:
@@ -1074,45 +1257,14 @@ class MfmaConv2d(nn.Conv2d, _Mfma2dMixin):
             # narrow input: the zero-padded NHWC copy is made here, whatever the caller's layout
             why = _why_not_bf16_cl(x, 4) or \
                 ('autograd is recording (the 2-D MFMA path is inference-only)' if torch.is_grad_enabled() else None)
-        if why is None and not conv3d_g_plannable(x.shape[0], self._cin_padded(), self.out_channels,
-                                                  (1, x.shape[2], x.shape[3]), (1,) + self.stride, (0, 1, 1),
-                                                  kernel1=(True, False, False)):
+        if why is None and not self._geom().plannable(x.shape[0], (1, x.shape[2], x.shape[3])):
             why = 'no tiling of the general kernel fits this shape'
         return why
 
-    def eligible(self, x):
-        return self.why_not(x) is None
-
-    def train_why_not(self, x):
-        """why a call with autograd recording does NOT take the MFMA kernels (None: it does)"""
-        if not x.is_cuda:
-            return 'CPU tensor'
-        if not (self.kernel_size == (3, 3) and self.padding == (1, 1) and self.dilation == (1, 1) and
-                self.groups == 1 and self.stride in ((1, 1), (2, 2)) and self.padding_mode == 'zeros' and
-                self.out_channels % 32 == 0 and (self.in_channels % 32 == 0 or self.in_channels < 32)):
-            return 'convolution configuration outside the kernel\'s coverage (3x3, padding 1, stride 1 | 2)'
-        if x.dim() != 4 or x.shape[1] != self.in_channels or x.dtype != torch.bfloat16 or \
-                self.weight.dtype != torch.bfloat16:
-            return 'not a bf16 call of this module'
-        n, _, h, w = x.shape
-        st = self.stride[0]
-        if st == 2 and (h % 2 or w % 2):
-            return 'odd extent under stride 2 (backward-data is a transposed convolution)'
-        cin, cout = self._cin_padded(), self.out_channels
-        ho, wo = (h - 1) // st + 1, (w - 1) // st + 1
-        if not (conv3d_g_plannable(n, cin, cout, (1, h, w), (1, st, st), (0, 1, 1), kernel1=(True, False, False)) and
-                conv3d_g_plannable(n, cout, cin, (1, ho, wo), (1, 1, 1), (0, 1, 1),
-                                   transposed=(False, st == 2, st == 2), kernel1=(True, False, False))):
-            return 'no tiling of the general kernel fits this shape'
-        return None
-
-    def _packed2d_padded(self):
-        def make():
-            w = self.weight.detach()
-            if self.in_channels < 32:
-                w = torch.cat([w, w.new_zeros(w.shape[0], 32 - self.in_channels, 3, 3)], 1)
-            return pack_conv2d_g_weights(w, self._cin_padded(), self.out_channels)
-        return derived(self).get('pack2d_padded', (self.weight,), make)
+    def _packed(self):
+        g = self._geom()
+        return derived(self).get('pack2d_padded', (self.weight,), lambda: pack_conv2d_g_weights(
+            _pad_to_chunk(self.weight.detach()), g.cin, g.cout))
 
     def forward_fused(self, x, scale=None, shift=None, residual=None, relu=False):
         if self.bias is not None:
@@ -1120,13 +1272,8 @@ class MfmaConv2d(nn.Conv2d, _Mfma2dMixin):
             shift = b if shift is None else shift + b * (scale if scale is not None else 1.0)
             if scale is None:
                 scale = torch.ones_like(b)
-        if self.in_channels < 32:  # NHWC, zero channels up to 32: one small copy (26 MB at 320 x 1280)
-            B, C, H, W = x.shape
-            xp = x.new_zeros((B, H, W, 32))
-            xp[..., :C] = x.permute(0, 2, 3, 1)
-            x = xp.permute(0, 3, 1, 2)
-        return conv2d_g(x, self._packed2d_padded(), self.out_channels, stride=self.stride, relu=relu,
-                        scale=scale, shift=shift, residual=residual)
+        return conv2d_g(_pad_to_chunk(x, ndhwc=True), self._packed(), self.out_channels, stride=self.stride,
+                        relu=relu, scale=scale, shift=shift, residual=residual)
 
     def forward(self, x):
         if (self.kernel_size == (1, 1) and self.stride == (1, 1) and self.padding == (0, 0) and self.groups == 1 and
@@ -1141,248 +1288,35 @@ class MfmaConv2d(nn.Conv2d, _Mfma2dMixin):
             else:
                 y = F.linear(x.permute(0, 2, 3, 1), w2, self.bias)
             return y.permute(0, 3, 1, 2)
-        recording = torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad)
-        if recording:
-            why = self.train_why_not(x)
-            if why is None:
-                return _Conv2dGFn.apply(x, self.weight, self.bias, 'conv', self.stride[0])
-        else:
-            why = self.why_not(x)
-            if why is None:
-                return self.forward_fused(x)
-        if self.kernel_size == (3, 3) and x.is_cuda and x.dtype == torch.float32 and 'coverage' not in why:
-            y = self._forward_fp32_split(x)
-            if y is not None:
-                return y
-        # (the 1x1 convolutions built through convbn() are torch's by design)
-        if self.kernel_size == (3, 3):
-            _torch_path(self, x, why)
-        return super().forward(x)
-
-    def _forward_fp32_split(self, x):
-        """an fp32 model: the depth-1 form of the general kernel in split precision (None: not applicable)"""
-        if _FP32_MODE['mode'] == 'torch' or x.dim() != 4 or x.shape[1] != self.in_channels:
-            return None
-        n, cin, h, w_ = x.shape
-        st, cout, cin_p = self.stride[0], self.out_channels, self._cin_padded()
-        if not conv3d_g_plannable(n, cin_p, cout, (1, h, w_), (1, st, st), (0, 1, 1), kernel1=(True, False, False)):
-            return None
-        w = self.weight
-        if cin < 32:  # the 3-channel image skip: zero channels up to one 32-channel chunk
-            x = torch.cat([x, x.new_zeros((n, 32 - cin, h, w_))], 1)
-            w = torch.cat([w, w.new_zeros((cout, 32 - cin, 3, 3))], 1)
-        keep_cl = x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
-        y = _ConvGSplitFn.apply(x.unsqueeze(2), _embed2d(w), None, 'conv', (1, st, st), (0, 1, 1), True).squeeze(2)
-        if self.bias is not None:
-            y = y + self.bias.view(1, -1, 1, 1)
-        return y if keep_cl else y.contiguous()
+        if self.kernel_size != (3, 3):  # (the 1x1 convolutions built through convbn() are torch's by design)
+            return super().forward(x)
+        return self._forward(x, self.train_why_not(x) if self._recording(x) else self.why_not(x))
 
 
-class MfmaConvTranspose2d(nn.ConvTranspose2d, _Mfma2dMixin):
+class MfmaConvTranspose2d(_Mfma2dModule, nn.ConvTranspose2d):
     """nn.ConvTranspose2d kernel 3, stride 2, padding 1, output_padding 1 (hourglass2d's up-convs,
     conv_modules.py:196-214) through the MFMA kernel under the conditions of ``MfmaConv2d``."""
+    UNCOVERED = 'transposed-convolution configuration outside the kernel\'s coverage'
+
+    def _covered(self):
+        return (self.kernel_size == (3, 3) and self.padding == (1, 1) and self.stride == (2, 2) and
+                self.output_padding == (1, 1) and self.dilation == (1, 1) and self.groups == 1 and
+                self.bias is None)
 
     def why_not(self, x):
-        if not x.is_cuda:
-            return 'CPU tensor'
-        if not (self.kernel_size == (3, 3) and self.padding == (1, 1) and self.stride == (2, 2) and
-                self.output_padding == (1, 1) and self.dilation == (1, 1) and self.groups == 1 and
-                self.bias is None):
-            return 'transposed-convolution configuration outside the kernel\'s coverage'
-        why = conv2d_g_why_not(x, self.in_channels, self.out_channels)
-        if why is None and not conv3d_g_plannable(x.shape[0], self.in_channels, self.out_channels,
-                                                  (1, x.shape[2], x.shape[3]), (1, 1, 1), (0, 1, 1),
-                                                  transposed=(False, True, True), kernel1=(True, False, False)):
+        why = self._why_not_config(x) or conv2d_g_why_not(x, self.in_channels, self.out_channels)
+        if why is None and not self._geom().plannable(x.shape[0], (1, x.shape[2], x.shape[3])):
             why = 'no tiling of the general kernel fits this shape'
         return why
 
-    def eligible(self, x):
-        return self.why_not(x) is None
-
-    def train_why_not(self, x):
-        if not x.is_cuda:
-            return 'CPU tensor'
-        if not (self.kernel_size == (3, 3) and self.padding == (1, 1) and self.stride == (2, 2) and
-                self.output_padding == (1, 1) and self.dilation == (1, 1) and self.groups == 1 and
-                self.bias is None and self.in_channels % 32 == 0 and self.out_channels % 32 == 0):
-            return 'transposed-convolution configuration outside the kernel\'s coverage'
-        if x.dim() != 4 or x.shape[1] != self.in_channels or x.dtype != torch.bfloat16 or \
-                self.weight.dtype != torch.bfloat16:
-            return 'not a bf16 call of this module'
-        n, _, h, w = x.shape
-        k1 = (True, False, False)
-        if not (conv3d_g_plannable(n, self.in_channels, self.out_channels, (1, h, w), (1, 1, 1), (0, 1, 1),
-                                   transposed=(False, True, True), kernel1=k1) and
-                conv3d_g_plannable(n, self.out_channels, self.in_channels, (1, 2 * h, 2 * w), (1, 2, 2), (0, 1, 1),
-                                   kernel1=k1)):
-            return 'no tiling of the general kernel fits this shape'
-        return None
-
-    def forward(self, x, output_size=None):
-        recording = torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad)
-        if output_size is not None:
-            why = 'explicit output_size'
-        elif recording:
-            why = self.train_why_not(x)
-            if why is None:
-                return _Conv2dGFn.apply(x, self.weight, None, 'convT', 2)
-        else:
-            why = self.why_not(x)
-            if why is None:
-                return conv2d_g(x, self._packed2d(self.in_channels, self.out_channels, True), self.out_channels,
-                                transposed=True)
-        if (output_size is None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and
-                'coverage' not in why and _FP32_MODE['mode'] != 'torch' and x.shape[1] == self.in_channels and
-                conv3d_g_plannable(x.shape[0], self.in_channels, self.out_channels, (1, x.shape[2], x.shape[3]),
-                                   (1, 1, 1), (0, 1, 1), transposed=(False, True, True), kernel1=(True, False, False))):
-            keep_cl = x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
-            y = _ConvGSplitFn.apply(x.unsqueeze(2), _embed2d(self.weight), None, 'convT', 2, 1, True).squeeze(2)
-            return y if keep_cl else y.contiguous()
-        _torch_path(self, x, why)
-        return super().forward(x, output_size)
-
-
-def _bwd_data_supported(in_size, stride, padding):
-    """backward-data of an nn.Conv3d runs in the same kernel when every stride-2 axis has padding 1
-    and an even extent (it becomes a transposed axis)"""
-    return all(st == 1 or (st == 2 and p == 1 and s % 2 == 0) for s, st, p in zip(in_size, stride, padding))
-
-
-class _ConvGFn(torch.autograd.Function):
-    """nn.Conv3d (kind 'conv') / nn.ConvTranspose3d k3 s2 p1 op1 (kind 'convT') through the MFMA kernel.
-    Backward-data is another launch of the same kernel; backward-weight is torch's (MIOpen)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, packed, kind, stride, padding):
-        ctx.save_for_backward(x, weight)
-        ctx.cfg = (kind, stride, padding)
-        if kind == 'conv':
-            return conv3d_g(x, packed, weight.shape[0], stride, padding)
-        return conv3d_g(x, packed, weight.shape[1], transposed=True)
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, weight = ctx.saved_tensors
-        kind, stride, padding = ctx.cfg
-        gy = gy.contiguous(memory_format=torch.channels_last_3d)
-        gx = gw = None
-        in_size = tuple(x.shape[2:])
-        if kind == 'conv':
-            cout, cin = weight.shape[:2]
-            if ctx.needs_input_grad[0]:
-                if _bwd_data_supported(in_size, stride, padding):
-                    up = tuple(st == 2 for st in stride)
-                    flip = sum(b for b, st in zip((4, 2, 1), stride) if st == 1)
-                    pk = pack_conv3d_g_weights(weight, cout, cin, swap=True, flip=flip)
-                    gx = conv3d_g(gy, pk, cin, stride=1, padding=tuple(2 - p for p in padding), transposed=up)
-                else:
-                    gx = torch.ops.aten.convolution_backward(
-                        gy, x, weight.to(x.dtype), None, list(stride), list(padding), [1, 1, 1], False,
-                        [0, 0, 0], 1, [True, False, False])[0]
-            if ctx.needs_input_grad[1]:
-                gw = conv3d_weight_grad(x, gy, stride, padding, out_dtype=weight.dtype)
-        else:
-            cin, cout = weight.shape[:2]
-            if ctx.needs_input_grad[0]:
-                pk = pack_conv3d_g_weights(weight, cout, cin, swap=False, flip=0)
-                gx = conv3d_g(gy, pk, cin, stride=2, padding=1)
-            if ctx.needs_input_grad[1]:
-                gw = conv3d_weight_grad(gy, x, 2, 1, out_dtype=weight.dtype)
-        return gx, gw, None, None, None, None
-
-
-class MfmaConv3dG(nn.Conv3d):
-    """nn.Conv3d(32 j, 32 k, 3, stride in {1, 2}, padding in {0, 1, 2}, bias=False) whose bf16 /
-    NDHWC forward is the general MFMA kernel; any other input takes torch's convolution (MIOpen),
-    the module's other documented path.  ``forward_fused`` folds a per-channel scale / shift (an
-    eval-mode BatchNorm3d), a residual and the ReLU into the epilogue (inference)."""
-
-    def why_not(self, x):
-        if not x.is_cuda:
-            return 'CPU tensor'
-        if not (self.in_channels % 32 == 0 and self.out_channels % 32 == 0 and self.kernel_size == (3, 3, 3) and
-                all(s in (1, 2) for s in self.stride) and all(0 <= p <= 2 for p in self.padding) and
-                self.dilation == (1, 1, 1) and self.groups == 1 and self.bias is None and
-                self.padding_mode == 'zeros'):
-            return 'convolution configuration outside the general kernel\'s coverage'
-        why = _why_not_bf16_cl(x, 5)
-        if why is not None:
-            return why
-        cs = _ndhwc_channel_stride(x)
-        if not cs:
-            return 'input is not channels_last_3d (nor a channel slice of an NDHWC tensor)'
-        if not all(s + 2 * p >= 3 for s, p in zip(x.shape[2:], self.padding)):
-            return 'input smaller than the kernel'
-        if not conv3d_g_plannable(x.shape[0], self.in_channels, self.out_channels, tuple(x.shape[2:]), self.stride,
-                                  self.padding, in_channel_stride=0 if cs == self.in_channels else cs):
-            return 'no tiling of the general kernel fits this shape'
-        return None
-
-    def eligible(self, x):
-        return self.why_not(x) is None
-
     def _packed(self):
-        return derived(self).get('pack', (self.weight,), lambda: pack_conv3d_g_weights(
-            self.weight, self.in_channels, self.out_channels))
-
-    def forward(self, x):
-        why = self.why_not(x)
-        if why is None:
-            return _ConvGFn.apply(x, self.weight, self._packed(), 'conv', self.stride, self.padding)
-        if x.is_cuda and x.dtype == torch.float32 and 'coverage' not in why:
-            why32 = _split_why_not(self, x, 'conv')
-            if why32 is None:  # an fp32 model: the same kernel in split precision
-                return _ConvGSplitFn.apply(x, self.weight,
-                                           _split_packs(self, self.in_channels, self.out_channels, False), 'conv',
-                                           self.stride, self.padding)
-            why = f'{why}; split precision: {why32}'
-        _torch_path(self, x, why)
-        return super().forward(x)
-
-    def forward_fused(self, x, scale=None, shift=None, residual=None, relu=False):
-        """inference only (no autograd): relu?(conv(x) * scale + shift + residual)"""
-        assert self.eligible(x)
-        return conv3d_g(x, self._packed(), self.out_channels, self.stride, self.padding, relu=relu,
-                        scale=scale, shift=shift, residual=residual)
-
-
-class MfmaConvTranspose3d(nn.ConvTranspose3d):
-    """nn.ConvTranspose3d(32 j, 32 k, 3, stride=2, padding=1, output_padding=1, bias=False) of the
-    hourglass (conv_modules.py:101-117): evaluated per output parity class on the low-resolution
-    input by the general MFMA kernel when the input is bf16 / NDHWC."""
-
-    def why_not(self, x):
-        if not x.is_cuda:
-            return 'CPU tensor'
-        if not (self.in_channels % 32 == 0 and self.out_channels % 32 == 0 and self.kernel_size == (3, 3, 3) and
-                self.stride == (2, 2, 2) and self.padding == (1, 1, 1) and self.output_padding == (1, 1, 1) and
-                self.dilation == (1, 1, 1) and self.groups == 1 and self.bias is None):
-            return 'transposed-convolution configuration outside the general kernel\'s coverage'
-        why = _why_not_bf16_cl(x, 5)
-        if why is None and not _is_ndhwc(x):
-            why = 'input is not channels_last_3d'
-        if why is None and not conv3d_g_plannable(x.shape[0], self.in_channels, self.out_channels,
-                                                  tuple(x.shape[2:]), 1, 1, transposed=True):
-            why = 'no tiling of the general kernel fits this shape'
-        return why
-
-    def eligible(self, x):
-        return self.why_not(x) is None
-
-    def _packed(self):
-        return derived(self).get('pack', (self.weight,), lambda: pack_conv3d_g_weights(
+        return derived(self).get('pack2d', (self.weight,), lambda: pack_conv2d_g_weights(
             self.weight, self.in_channels, self.out_channels, swap=True))
 
+    def forward_fused(self, x):
+        return conv2d_g(x, self._packed(), self.out_channels, transposed=True)
+
     def forward(self, x, output_size=None):
-        why = self.why_not(x) if output_size is None else 'explicit output_size'
-        if why is None:
-            return _ConvGFn.apply(x, self.weight, self._packed(), 'convT', self.stride, self.padding)
-        if output_size is None and x.is_cuda and x.dtype == torch.float32 and 'coverage' not in why:
-            why32 = _split_why_not(self, x, 'convT')
-            if why32 is None:  # an fp32 model: the same kernel in split precision
-                return _ConvGSplitFn.apply(x, self.weight,
-                                           _split_packs(self, self.in_channels, self.out_channels, True), 'convT',
-                                           self.stride, self.padding)
-            why = f'{why}; split precision: {why32}'
-        _torch_path(self, x, why)
-        return super().forward(x, output_size)
+        if output_size is not None:
+            return self._torch_forward(x, 'explicit output_size', output_size)
+        return self._forward(x, self.train_why_not(x) if self._recording(x) else self.why_not(x))

@@ -1036,7 +1036,7 @@ def _channels_last_2d(module, feats):
     The 4-D weights are re-laid once; shapes, values and state_dict keys are untouched.
 
     Training (autograd recording) runs NHWC as well since round 4: the 3x3 convolutions train through the
-    MFMA kernels (conv3d._Conv2dGFn: forward, backward-data, backward-weight), the 1x1 convolutions of an
+    MFMA kernels (conv3d._ConvGFn: forward, backward-data, backward-weight), the 1x1 convolutions of an
     NHWC tensor are matrix products, GroupNorm is the HIP kernel in either layout and the bilinear resizes
     have a matrix-product backward (bilinear_resize) -- the three things that made torch's NHWC training
     path 2.1 s per DfMStereoPath step in round 3 (MIOpen's naive NHWC convolutions, ATen's channels-last

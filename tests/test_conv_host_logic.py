@@ -208,3 +208,116 @@ def test_workspace_sizes_of_the_round_6_entry_points(cv):
     d.batch, d.num_depths, d.h_out, d.w_out = 64, 288, 376, 1248      # a table beyond 2 GiB is not asked for
     n = lib.dfm_plane_sweep_bwd_prev_gather_workspace_bytes(ctypes.byref(d))
     assert n == ((64 * 288 * 12 * 4 + 255) // 256) * 256
+
+
+# kind, cin, cout, size, stride, padding: the smallest shapes at which each branch of the backward algebra is distinct
+BACKWARD_CASES = [
+    ('conv3d', 32, 64, (4, 5, 6), 1, 1),                  # plain; flip 7
+    ('conv3d', 64, 32, (4, 6, 8), 2, 1),                  # all axes transposed
+    ('conv3d', 32, 32, (4, 6, 8), (1, 1, 2), 1),          # mixed transposed / mirrored axes
+    ('conv3d', 32, 32, (3, 5, 4), 1, (1, 1, 0)),          # padding 0 becomes 2
+    ('conv3d', 32, 32, (5, 7, 9), 2, 1),                  # odd extents: None (aten's convolution_backward)
+    ('convT3d', 64, 32, (3, 4, 5), 2, 1),                 # the stride-2 correlation back
+    ('conv2d', 64, 32, (9, 11), 1, 1),                    # depth-1, flip 7
+    ('conv2d', 64, 32, (10, 12), 2, 1),                   # depth-1, flip 4, weight gradient pads the depth axis
+    ('conv2d', 3, 32, (6, 8), 1, 1),                      # narrow input padded to 32, gradients sliced back
+    ('convT2d', 32, 32, (5, 6), 2, 1),                    # depth-1 transposed
+]
+
+
+@pytest.mark.parametrize('kind,cin,cout,size,stride,padding', BACKWARD_CASES)
+def test_backward_algebra_of_a_geometry_equals_autograd(cv, kind, cin, cout, size, stride, padding):
+    """ConvGeom.backward_data / backward_weight, evaluated with the float64 references of tests/conv_variants.py on
+    integer operands, equal float64 autograd of torch's convolution exactly.  ``swap`` is transpose(0, 1) of the
+    weight and ``flip`` mirrors the kernel axes of its mask (4 = d, 2 = h, 1 = w), as include/dfm_hip.h defines them."""
+    from tests import conv_variants as V
+    nd = len(size)
+    conv = {'conv3d': F.conv3d, 'conv2d': F.conv2d}.get(kind)
+    gen = torch.Generator().manual_seed(7)
+    ints = lambda *shape: torch.randint(-4, 5, shape, generator=gen).double()  # noqa: E731
+    x = ints(2, cin, *size).requires_grad_(True)
+    if conv is not None:
+        w = ints(cout, cin, *(3,) * nd).requires_grad_(True)
+        cls = torch.nn.Conv3d if nd == 3 else torch.nn.Conv2d
+        module = cls(cin, cout, 3, stride=stride, padding=padding, bias=False)
+        y = conv(x, w, stride=stride, padding=padding)
+    else:
+        w = ints(cin, cout, *(3,) * nd).requires_grad_(True)
+        tconv, cls = (F.conv_transpose3d, torch.nn.ConvTranspose3d) if nd == 3 else \
+            (F.conv_transpose2d, torch.nn.ConvTranspose2d)
+        module = cls(cin, cout, 3, stride=2, padding=1, output_padding=1, bias=False)
+        y = tconv(x, w, stride=2, padding=1, output_padding=1)
+    gy = ints(*y.shape)
+    y.backward(gy)
+    g = cv.ConvGeom.of(module)
+    # the operands as the kernel sees them: depth-1 volumes, the 2-D kernel in the centre depth slice, a narrow
+    # input and its weight zero-padded to one 32-channel chunk
+    x5, w5, gy5 = x.detach(), w.detach(), gy
+    if nd == 2:
+        x5, gy5 = x5.unsqueeze(2), gy5.unsqueeze(2)
+        w5 = torch.zeros(*w5.shape[:2], 3, 3, 3, dtype=torch.float64)
+        w5[:, :, 1] = w.detach()
+    if cin < 32:
+        x5 = torch.cat([x5, x5.new_zeros(2, 32 - cin, *x5.shape[2:])], 1)
+        w5 = torch.cat([w5, w5.new_zeros(cout, 32 - cin, 3, 3, 3)], 1)
+    assert (g.cin, g.cout) == (x5.shape[1], gy5.shape[1]) and g.out_size(tuple(x5.shape[2:])) == tuple(gy5.shape[2:])
+    assert torch.equal(V.ref_conv(x5, w5.transpose(0, 1) if g.swap else w5, g.stride, g.padding, g.transposed,
+                                  g.kernel1), y.detach().unsqueeze(2) if nd == 2 else y.detach())
+    back = g.backward_data(tuple(x5.shape[2:]))
+    if back is None:
+        # the aten case: a stride-2 axis whose padding is not 1 or whose extent is odd
+        st, pd = cv._triple(stride), cv._triple(padding)
+        assert kind == 'conv3d' and not all(s == 1 or (s == 2 and p == 1 and n % 2 == 0)
+                                            for n, s, p in zip(size, st, pd))
+    else:
+        wb = w5.transpose(0, 1) if back.swap else w5
+        wb = torch.flip(wb, [2 + a for a, bit in enumerate((4, 2, 1)) if back.flip & bit])
+        gx = V.ref_conv(gy5, wb, back.stride, back.padding, back.transposed, back.kernel1)[:, :cin]
+        assert torch.equal(gx.squeeze(2) if nd == 2 else gx, x.grad)
+    assert (kind, tuple(size)) != ('conv3d', (5, 7, 9)) or back is None
+    wg = g.backward_weight()
+    ops = {'input': x5, 'grad_output': gy5}
+    gw = V.ref_wgrad(ops[wg.x_in], ops[wg.g_out], wg.stride, wg.padding)
+    gw = gw[:, :cin] if conv is not None else gw
+    assert torch.equal(gw[:, :, 1] if nd == 2 else gw, w.grad)
+
+
+def _one_of_each_class(cv, covered):
+    if covered:
+        return [cv.MfmaConv3d(32, 32, 3, padding=1, bias=False), cv.MfmaConv3dTo1(32, 1, 3, 1, 1, bias=False),
+                cv.MfmaConv3dG(32, 64, 3, stride=2, padding=1, bias=False),
+                cv.MfmaConvTranspose3d(64, 32, 3, stride=2, padding=1, output_padding=1, bias=False),
+                cv.MfmaConv2d(32, 32, 3, stride=1, padding=1),
+                cv.MfmaConvTranspose2d(32, 32, 3, stride=2, padding=1, output_padding=1, bias=False)]
+    return [cv.MfmaConv3d(48, 48, 3, stride=3, padding=1, bias=False), cv.MfmaConv3dTo1(48, 1, 3, 3, 1, bias=False),
+            cv.MfmaConv3dG(48, 48, 3, stride=3, padding=1, bias=False),
+            cv.MfmaConvTranspose3d(48, 48, 3, stride=3, padding=1, bias=False),
+            cv.MfmaConv2d(48, 48, 3, stride=3, padding=1),
+            cv.MfmaConvTranspose2d(48, 48, 3, stride=3, padding=1, bias=False)]
+
+
+def test_fp32_dispatch_asks_the_configuration_not_the_text_of_its_reason(cv, monkeypatch):
+    """whether an fp32 input may try split precision is ``config_why_not()`` -- a value -- whatever its text says: with
+    the word "coverage" gone from every reason an uncovered configuration (48 channels, stride 3) still never asks
+    for the split path, and a covered one still reports 'CPU tensor' for a CPU tensor"""
+    asked = []
+    for m in _one_of_each_class(cv, False) + _one_of_each_class(cv, True):
+        monkeypatch.setattr(type(m), 'UNCOVERED', 'this configuration is not one the kernel takes')
+        monkeypatch.setattr(type(m), 'split_why_not', lambda self, x: asked.append(type(self).__name__))
+    for m in _one_of_each_class(cv, False):
+        assert m.config_why_not() == 'this configuration is not one the kernel takes'
+        x = torch.zeros(1, 48, *(6,) * (m._DIMS - 2))
+        assert m.why_not(x) == 'CPU tensor' and not m.eligible(x)
+        # the decision itself, on what a GPU tensor would report (the dispatch is pure: nothing is launched)
+        ran = []
+        monkeypatch.setattr(m, '_run', lambda x, arith: ran.append(arith))
+        monkeypatch.setattr(m, '_torch_forward', lambda x, why, *a: ran.append(why))
+        fake = type('FakeGpuTensor', (), dict(is_cuda=True, dtype=torch.float32))()
+        m._forward(fake, m.config_why_not())
+        assert ran == ['this configuration is not one the kernel takes'] and not asked, (type(m).__name__, ran, asked)
+    for m in _one_of_each_class(cv, True):
+        assert m.config_why_not() is None
+        x = torch.zeros(1, m.in_channels, *(6,) * (m._DIMS - 2))
+        assert m.why_not(x) == 'CPU tensor' and not m.eligible(x)
+        y = m(x)                                     # torch's convolution, without a warning or a split attempt
+        assert y.shape[1] == m.out_channels and not asked

@@ -312,7 +312,7 @@ def test_conv3d_to1_backward_exact(cv):
 ])
 @pytest.mark.parametrize('precision', ['bf16', 'fp32'])
 def test_module_gradients_exact(cv, kind, cin, cout, size, stride, padding, precision):
-    """MfmaConv3dG / MfmaConvTranspose3d: _ConvGFn in bf16, _ConvGSplitFn (split precision) in fp32; integer
+    """MfmaConv3dG / MfmaConvTranspose3d: _ConvGFn in bf16 and in split precision (fp32); integer
     operands, so both are exact against float64 autograd"""
     n = 2
     x = _ints((n, cin, *size), 51 + cin)
@@ -344,7 +344,7 @@ def test_module_gradients_exact(cv, kind, cin, cout, size, stride, padding, prec
 @pytest.mark.parametrize('kind,stride,size', [('conv', 1, (9, 21)), ('conv', 2, (10, 22)), ('convT', 2, (5, 11))])
 @pytest.mark.parametrize('precision', ['bf16', 'fp32'])
 def test_2d_module_gradients_exact(cv, kind, stride, size, precision):
-    """MfmaConv2d / MfmaConvTranspose2d under autograd: _Conv2dGFn (bf16) and the depth-1 _ConvGSplitFn (fp32)"""
+    """MfmaConv2d / MfmaConvTranspose2d under autograd: _ConvGFn on depth-1 views, in bf16 and in split precision (fp32)"""
     n, cin, cout = 2, 64, 32
     x = _ints((n, cin, *size), 61)
     if kind == 'conv':

@@ -105,7 +105,7 @@ def test_fp32_split_packs(m, kind):
                                                     bias=False).to(DEV)
     conv = make()
     x = _vol(32, dtype=torch.float32).contiguous()
-    assert m.conv3d._split_why_not(conv, x, kind) is None
+    assert conv.split_why_not(x) is None
     _follows(m, lambda: conv(x), _scale(conv.weight), lambda: _twin(make, conv)(x))
 
 

@@ -96,7 +96,7 @@ def _load(module, seed):
 @pytest.mark.gpu
 def test_dfm_backbone_forward_vs_reference_module(mods, gold, monkeypatch):
     """fp32, the reference's default precision: every 3x3x3 convolution of the aggregation stacks runs the
-    MFMA kernel in split precision (conv3d._ConvGSplitFn: three bf16 launches accumulated in fp32) -- no
+    MFMA kernel in split precision (conv3d._ConvGFn in its split arithmetic: three bf16 launches accumulated in fp32) -- no
     torch / MIOpen convolution behind this comparison with the reference module's output"""
     import importlib
     cv = importlib.import_module('depth-from-motion_amd.conv3d')
