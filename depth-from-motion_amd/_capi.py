@@ -166,6 +166,17 @@ class AnchorTargetDesc(ctypes.Structure):
         [(n, ctypes.c_float) for n in ('dir_offset', 'dir_limit_offset', 'pos_weight')]
 
 
+ANCHOR_HEAD_MAX_BATCH = 64  # DFM_ANCHOR_HEAD_MAX_BATCH
+BBOX_CODE_MIN, BBOX_CODE_MAX = 7, 16  # the box widths dfm_delta_xyzwlhr_decode / dfm_anchor_head_candidates take
+
+
+class AnchorHeadDesc(ctypes.Structure):
+    """struct dfm_anchor_head_desc"""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        'batch', 'h', 'w', 'anchors_per_location', 'num_classes', 'box_code_size', 'nms_pre', 'dtype')] + \
+        [(n, ctypes.c_int64 * 4) for n in ('cls_stride', 'reg_stride', 'dir_stride')]
+
+
 DFM_ERR_UNSUPPORTED = -2  # include/dfm_hip.h
 BOX_NMS_MAX_N = 16384  # DFM_BOX_NMS_MAX_N
 
@@ -317,6 +328,22 @@ SIGNATURES = _signatures()
 EXPORTS = tuple(SIGNATURES)
 
 
+def _bbox_decode_signatures():
+    """the same for include/dfm_hip_bbox_decode.h, the header dfm_hip.h includes for the anchor head's maps -> boxes
+    entry points (tests/test_bbox_decode.py checks this table against that header and the built library)"""
+    vp = fp = ctypes.c_void_p
+    ci, i32, sz, ahp = ctypes.c_int, ctypes.c_int32, ctypes.c_size_t, ctypes.POINTER(AnchorHeadDesc)
+    return {
+        'dfm_anchor_head_candidates_workspace_bytes': (sz, [ahp]),
+        'dfm_anchor_head_candidates': (ci, [ahp, vp, vp, vp, fp, fp, fp, fp, vp, vp, vp, sz, vp]),
+        'dfm_delta_xyzwlhr_decode': (ci, [fp, fp, i32, i32, fp, vp]),
+    }
+
+
+BBOX_DECODE_SIGNATURES = _bbox_decode_signatures()
+BBOX_DECODE_EXPORTS = tuple(BBOX_DECODE_SIGNATURES)
+
+
 _lib = None
 
 
@@ -331,7 +358,7 @@ def lib():
             '`python -c "import __graft_entry__ as g; g.build()"` '
             '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
     h = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in (*SIGNATURES.items(), *BBOX_DECODE_SIGNATURES.items()):
         fn = getattr(h, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = h

@@ -16,7 +16,8 @@ Three ways to use this package from there, all routed to the HIP kernels:
    functions, ``diff_iou_rotated_3d`` and ``bbox_overlaps_nearest_3d`` where their modules are already
    imported), replaces ``MultiViewDfM.feature_transformation`` by
    ``MultiViewDfMMixin.feature_transformation`` and, where ``train_mixins`` is already imported,
-   ``AnchorTrainMixin.anchor_target_3d`` by ``HipAnchorTrainMixin.anchor_target_3d``.
+   ``AnchorTrainMixin.anchor_target_3d`` by ``HipAnchorTrainMixin.anchor_target_3d`` and, where ``anchor3d_head`` is,
+   ``Anchor3DHead.get_bboxes`` by ``HipAnchor3DHeadMixin.get_bboxes``.
 2. ``DfMStereoPath`` -- the KITTI student's path (neck -> backbone_stereo -> depth_head ->
    feature_transformation -> height compression -> backbone_3d) built from the ``model`` dict of
    ``configs/dfm/dfm_r34_1x8_kitti-3d-3class.py`` with the detector's attribute injection;
@@ -36,6 +37,8 @@ from .box_nms import box3d_multiclass_nms, nms_bev, nms_normal_bev
 from .iou3d_loss import diff_iou_rotated_3d
 from . import anchor_target as _anchor_target
 from .anchor_target import HipAnchorTrainMixin, bbox_overlaps_nearest_3d
+from . import bbox_decode as _bbox_decode
+from .bbox_decode import HipAnchor3DHeadMixin
 from .geometry import prepare_coordinates_3d, prepare_depth
 from .conv3d import MfmaConv3dTo1
 from .graphs import GraphedCallable
@@ -403,6 +406,30 @@ def _patch_anchor_target():
     return functions, methods
 
 
+# the anchor head's inference side: Anchor3DHead.get_bboxes (inherited by LIGAAnchor3DHead) is rebound, the replaced
+# method kept for the fallback policy.  Only where anchor3d_head.py is already imported, as above: it imports mmdet.
+_ANCHOR_HEAD_MODULES = ('mmdet3d.models.dense_heads.anchor3d_head',)
+
+
+def _patch_anchor_head():
+    """-> methods rebound"""
+    methods = []
+    for mod_name in _ANCHOR_HEAD_MODULES:
+        mod = sys.modules.get(mod_name)
+        cls = getattr(mod, 'Anchor3DHead', None) if mod is not None else None
+        if cls is not None and hasattr(cls, 'get_bboxes'):
+            current = vars(cls).get('get_bboxes')
+            ours = vars(HipAnchor3DHeadMixin)['get_bboxes']
+            if current is not ours:
+                _bbox_decode._REFERENCE['get_bboxes'] = current
+                cls.get_bboxes = ours
+                # the helpers the rebound method calls on ``self``
+                for helper in ('_get_bboxes_unsupported', '_get_bboxes_fallback', '_mlvl_anchors'):
+                    setattr(cls, helper, vars(HipAnchor3DHeadMixin)[helper])
+            methods.append('Anchor3DHead.get_bboxes')
+    return methods
+
+
 def patch_reference(precision=None, strict=False):
     """Route a real mmdet3d (the reference fork) to the HIP path.  Call once after
     ``import mmdet3d`` and before building the model from ``configs/dfm/*``.  Returns a report
@@ -430,6 +457,7 @@ def patch_reference(precision=None, strict=False):
     functions, methods = _patch_anchor_target()
     report['functions'] += functions
     report['methods'] += methods
+    report['methods'] += _patch_anchor_head()
     try:
         det = importlib.import_module('mmdet3d.models.detectors.multiview_dfm')
         det.MultiViewDfM.feature_transformation = MultiViewDfMMixin.feature_transformation

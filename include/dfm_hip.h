@@ -1363,6 +1363,11 @@ DFM_API int dfm_spp_tail_fwd(const dfm_spp_desc *desc, const void *const *pooled
                              const void *const *sources, void *out, void *workspace,
                              size_t workspace_bytes, void *stream);
 
+/* the 3-D anchor head's maps to NMS candidates and the box decode (dfm_anchor_head_candidates,
+ * dfm_anchor_head_candidates_workspace_bytes, dfm_delta_xyzwlhr_decode): declared, with their semantics, in a header
+ * of their own, which is part of this one */
+#include "dfm_hip_bbox_decode.h"
+
 #ifdef __cplusplus
 }
 #endif
