@@ -49,7 +49,7 @@ struct ColVolume {
     __device__ __forceinline__ float at(int d) { return elem<T>::load(col[(size_t)d * HW]); }
 };
 // ... or evaluated from the low-resolution cost (nested W -> H -> D fma upsample, align_corners=True:
-// depth_head_kernel's expressions; frustum_to_voxel.hip's fused_disp uses the same)
+// depth_head_kernel's expressions; f2v_common.h's fused_disp uses the same)
 template <typename T>
 struct ColFused {
     const T *cost;   // sample b's (cd, ch, cw) volume

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "dfm_hip.h"
 
 namespace dfm {
@@ -96,6 +98,22 @@ template <> struct elem<bf16_t> {
     static __device__ __forceinline__ float load(bf16_t v) { return bf16_to_f32(v); }
     static __device__ __forceinline__ bf16_t store(float v) { return f32_to_bf16(v); }
 };
+
+// Host side: a launch templated on the element type, or on a bool, written ONCE -- f is a generic lambda that
+// takes a value of the element type (float{} / bf16_t{}: T = decltype of it) or a std::bool_constant
+// (its ::value is a constant expression).  dtype has been validated (DFM_F32 or DFM_BF16) before.
+template <typename F>
+inline void by_dtype(int32_t dtype, F &&f)
+{
+    if (dtype == DFM_F32) f(float{});
+    else f(bf16_t{});
+}
+template <typename F>
+inline void by_bool(bool on, F &&f)
+{
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 // unpack one 16-byte channel block into CB floats
 __device__ __forceinline__ void unpack16(const uint4 &q, float (&f)[4])

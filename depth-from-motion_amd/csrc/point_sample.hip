@@ -22,7 +22,7 @@
 // non-temporal 16-byte stores: the batched channels-last kernel writes whole contiguous KiBs per
 // instruction and gains 6 % (waymo_cl 0.2366 -> 0.2235 ms, profiles/archive/r04_c7_lift_nt_vs_plain.txt);
 // -DDFM_LIFT_PLAIN builds the plain-store variant.  (FrustumToVoxel's lane-per-voxel kernel must NOT
-// use nt: its stores are partial lines per instruction, see frustum_to_voxel.hip.)
+// use nt: its stores are partial lines per instruction, see f2v_common.h: lift_store16.)
 template <typename T>
 __device__ __forceinline__ void lift_store16(T *p, const float (&f)[dfm::vec16<T>::N])
 {

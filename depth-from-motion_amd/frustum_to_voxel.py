@@ -1,7 +1,7 @@
 """Host-side mirror of the sampling stage of ``FrustumToVoxel.forward``
 (mmdet3d/models/necks/feature_transformation.py:82-158): one HIP launch
-(``dfm_frustum_to_voxel_fwd``) produces cat(Voxel, Voxel_2D), the input of
-``voxel_convs``."""
+(``dfm_frustum_to_voxel_fwd``, csrc/frustum_to_voxel.hip) produces cat(Voxel, Voxel_2D), the input of
+``voxel_convs``; its backward is csrc/frustum_to_voxel_bwd.hip (gather, else pixel-major scatter)."""
 import contextlib
 import ctypes
 
@@ -15,79 +15,55 @@ from .depth_head import LazyDepthDistribution
 from .geometry import stack_meta
 
 
+def _forward(desc, stereo, sem, coords, cam4, depth, scale):
+    """the forward launch.  ``depth``, the source of the depth distribution: ``(soft,)`` -- the materialised
+    softmax, None when no attention wants it -- or ``(cost, col_max, col_sum)``, the DepthHead fused into the
+    sampling (evaluated from the low-resolution cost, ``scale`` = the head's upsampling factor)"""
+    out = _alloc_out(desc, stereo)
+    nbytes = _capi.lib().dfm_frustum_to_voxel_workspace_bytes(ctypes.byref(desc))
+    if len(depth) == 3:
+        launch('dfm_frustum_to_voxel_fused_fwd', desc, stereo, *depth, scale, sem, coords, cam4, out, WS, STREAM,
+               ws_bytes=nbytes)
+    else:
+        launch('dfm_frustum_to_voxel_fwd', desc, stereo, *depth, sem, coords, cam4, out, WS, STREAM, ws_bytes=nbytes)
+    return out
+
+
 class _F2vFn(torch.autograd.Function):
+    """the sampling with autograd, for either depth source of ``_forward``; the distribution is detached in the
+    reference (feature_transformation.py:136), so the backward only reads it -- with the head fused it is
+    evaluated from the low-resolution cost in both directions.  Backward: the gather form where it applies,
+    else the scatter (which ignores the input layouts)"""
 
     @staticmethod
-    def forward(ctx, stereo, sem, soft, coords, cam4, desc):
-        lib = _capi.lib()
-        out = _alloc_out(desc, stereo)
-        nbytes = lib.dfm_frustum_to_voxel_workspace_bytes(ctypes.byref(desc))
-        launch('dfm_frustum_to_voxel_fwd', desc, stereo, soft, sem, coords, cam4, out, WS, STREAM, ws_bytes=nbytes)
-        ctx.desc = desc
-        ctx.has_sem = sem is not None
+    def forward(ctx, stereo, sem, coords, cam4, desc, scale, *depth):
+        out = _forward(desc, stereo, sem, coords, cam4, depth, scale)
+        ctx.desc, ctx.scale, ctx.fused, ctx.n_in = desc, scale, len(depth) == 3, 6 + len(depth)
         ctx.shapes = (stereo.shape, None if sem is None else sem.shape, stereo.dtype)
-        ctx.save_for_backward(coords, cam4, *(() if soft is None else (soft,)))
+        ctx.save_for_backward(coords, cam4, *(t for t in depth if t is not None))
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        coords, cam4, *rest = ctx.saved_tensors
-        soft = rest[0] if rest else None
-        lib = _capi.lib()
+        coords, cam4, *depth = ctx.saved_tensors
+        soft = None if ctx.fused or not depth else depth[0]
         desc = ctx.desc
         st_shape, sem_shape, dtype = ctx.shapes
         device = grad_out.device
         go = _grad_in_output_layout(grad_out, desc, dtype)
-        g_sem = torch.zeros(sem_shape, dtype=torch.float32, device=device) if ctx.has_sem else None
-        g_st = _try_gather_backward(desc, go, soft, None, 0, coords, cam4, st_shape, dtype, g_sem, device)
-        if g_st is not None:
-            return g_st.to(dtype), (g_sem.to(dtype) if g_sem is not None else None), None, None, None, None
-        g_st = torch.zeros(st_shape, dtype=torch.float32, device=device)
-        nbytes = lib.dfm_frustum_to_voxel_bwd_workspace_bytes(ctypes.byref(desc))
-        launch('dfm_frustum_to_voxel_bwd', desc, go, soft, coords, cam4, g_st, g_sem, WS, STREAM, ws_bytes=nbytes)
-        return g_st.to(dtype), (g_sem.to(dtype) if g_sem is not None else None), None, None, None, None
-
-
-class _F2vFusedFn(torch.autograd.Function):
-    """the DepthHead fused into the sampling, with autograd (training): forward =
-    dfm_frustum_to_voxel_fused_fwd, backward = dfm_frustum_to_voxel_fused_bwd -- the depth distribution
-    (detached in the reference, feature_transformation.py:136) is evaluated from the low-resolution cost in
-    both directions"""
-
-    @staticmethod
-    def forward(ctx, stereo, sem, cost, col_max, col_sum, scale, coords, cam4, desc):
-        lib = _capi.lib()
-        out = _alloc_out(desc, stereo)
-        nbytes = lib.dfm_frustum_to_voxel_workspace_bytes(ctypes.byref(desc))
-        launch('dfm_frustum_to_voxel_fused_fwd', desc, stereo, cost, col_max, col_sum, scale, sem, coords, cam4, out,
-               WS, STREAM, ws_bytes=nbytes)
-        ctx.desc, ctx.scale = desc, scale
-        ctx.has_sem = sem is not None
-        ctx.shapes = (stereo.shape, None if sem is None else sem.shape, stereo.dtype)
-        ctx.save_for_backward(coords, cam4, cost, col_max, col_sum)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        coords, cam4, cost, col_max, col_sum = ctx.saved_tensors
-        lib = _capi.lib()
-        desc = ctx.desc
-        st_shape, sem_shape, dtype = ctx.shapes
-        device = grad_out.device
-        go = _grad_in_output_layout(grad_out, desc, dtype)
-        g_sem = torch.zeros(sem_shape, dtype=torch.float32, device=device) if ctx.has_sem else None
-        bdesc = desc
-        g_st = _try_gather_backward(desc, go, None, (cost, col_max, col_sum), ctx.scale, coords, cam4, st_shape, dtype,
-                                    g_sem, device)
-        if g_st is not None:
-            return (g_st.to(dtype), (g_sem.to(dtype) if g_sem is not None else None), None, None, None, None, None,
-                    None, None)
-        g_st = torch.zeros(st_shape, dtype=torch.float32, device=device)
-        nbytes = lib.dfm_frustum_to_voxel_bwd_workspace_bytes(ctypes.byref(bdesc))
-        launch('dfm_frustum_to_voxel_fused_bwd', bdesc, go, cost, col_max, col_sum, ctx.scale, coords, cam4, g_st,
-               g_sem, WS, STREAM, ws_bytes=nbytes)
-        return (g_st.to(dtype), (g_sem.to(dtype) if g_sem is not None else None), None, None, None, None, None,
-                None, None)
+        g_sem = torch.zeros(sem_shape, dtype=torch.float32, device=device) if sem_shape is not None else None
+        g_st = _try_gather_backward(desc, go, soft, tuple(depth) if ctx.fused else None, ctx.scale, coords, cam4,
+                                    st_shape, dtype, g_sem, device)
+        if g_st is None:
+            g_st = torch.zeros(st_shape, dtype=torch.float32, device=device)
+            nbytes = _capi.lib().dfm_frustum_to_voxel_bwd_workspace_bytes(ctypes.byref(desc))
+            if ctx.fused:
+                launch('dfm_frustum_to_voxel_fused_bwd', desc, go, *depth, ctx.scale, coords, cam4, g_st, g_sem, WS,
+                       STREAM, ws_bytes=nbytes)
+            else:
+                launch('dfm_frustum_to_voxel_bwd', desc, go, soft, coords, cam4, g_st, g_sem, WS, STREAM,
+                       ws_bytes=nbytes)
+        return (g_st.to(dtype), g_sem.to(dtype) if g_sem is not None else None) + (None,) * (ctx.n_in - 2)
 
 
 _grid_cache = Derived(capacity=16)
@@ -146,7 +122,7 @@ def _check_regular_grid(coords, nz, ny, nx):
 
 
 def _try_gather_backward(desc, go, soft, fused, scale, coords, cam4, st_shape, dtype, g_sem, device):
-    """the gather form of the backward (csrc/frustum_to_voxel.hip: f2v_bwd_gather_kernel) -> the gradient of the cost
+    """the gather form of the backward (csrc/frustum_to_voxel_bwd.hip: f2v_bwd_gather_kernel) -> the gradient of the cost
     volume (the kernel overwrites it: no zero fill), None: not applicable.  A channels-last cost volume (the NDHWC
     stack) gets its gradient in its own layout and type -- what the prediction convolution's backward produces for
     the same tensor, so that autograd's accumulation is one contiguous addition; a planar volume gets planar fp32."""
@@ -211,7 +187,6 @@ def frustum_to_voxel_sample(stereo_feat, stereo_feat_softmax, img_metas, cur_sem
         (B, C + Cs, Nz, Ny, Nx), same dtype as stereo_feat
     """
     require_gpu(stereo_feat, 'stereo_feat')
-    lib = _capi.lib()
     device = stereo_feat.device
     if stereo_feat.dtype not in DTYPES:
         raise TypeError('stereo_feat must be float32 or bfloat16')
@@ -265,16 +240,8 @@ def frustum_to_voxel_sample(stereo_feat, stereo_feat_softmax, img_metas, cur_sem
     cam4[:, :cam.shape[1], :cam.shape[2]] = cam
     cam4 = cam4.reshape(B, 16).contiguous() if cam.is_cuda and cam.device == device else \
         upload(cam4.cpu().reshape(B, 16), device)
-    if lazy is not None and torch.is_grad_enabled() and (stereo.requires_grad or
-                                                         (sem is not None and sem.requires_grad)):
-        # training with the depth head fused (the backward ignores the input layouts, like _F2vFn's)
-        return _F2vFusedFn.apply(stereo, sem, lazy.cost, lazy.col_max, lazy.col_sum, int(lazy.scale), coords, cam4,
-                                 desc)
-    if lazy is not None:
-        lib = _capi.lib()
-        out = _alloc_out(desc, stereo)
-        nbytes = lib.dfm_frustum_to_voxel_workspace_bytes(ctypes.byref(desc))
-        launch('dfm_frustum_to_voxel_fused_fwd', desc, stereo, lazy.cost, lazy.col_max, lazy.col_sum, lazy.scale, sem,
-               coords, cam4, out, WS, STREAM, ws_bytes=nbytes)
-        return out
-    return _F2vFn.apply(stereo, sem, soft, coords, cam4, desc)
+    depth, scale = ((soft,), 0) if lazy is None else ((lazy.cost, lazy.col_max, lazy.col_sum), int(lazy.scale))
+    if lazy is not None and not (torch.is_grad_enabled() and (stereo.requires_grad or
+                                                               (sem is not None and sem.requires_grad))):
+        return _forward(desc, stereo, sem, coords, cam4, depth, scale)   # inference with the depth head fused
+    return _F2vFn.apply(stereo, sem, coords, cam4, desc, scale, *depth)

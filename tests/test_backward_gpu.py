@@ -1,6 +1,7 @@
 """GPU: backward passes of the sampling ops against torch-CPU autograd of the
 same expressions (grid_sample / Upsample / softmax).  Accumulation is by fp32
 atomics in unspecified order: rtol 1e-4, atol 1e-5."""
+import ctypes
 import importlib
 import os
 
@@ -96,7 +97,8 @@ def _f2v_torch(stereo, soft, sem, coords, cam2img, pad, dmin, dmax, sem_atten=Tr
 @pytest.mark.parametrize('channels', [3, 8])
 def test_frustum_to_voxel_backward_attention_switches(pkg, channels, sem_atten, stereo_atten):
     """gradients with stereo_atten_feat / sem_atten_feat (feature_transformation.py:141,154) through
-    both backward kernels (scalar: 3 channels; pixel-major scratch: 8)"""
+    the pixel-major backward, which takes every channel count (3: an odd one; 8: whole 16-byte blocks, so the
+    forward is the pixel-major kernel too); the lane-per-voxel scatter has its own tests below"""
     z = np.load(os.path.join(util.GOLDEN, 'f2v_batch2.npz'))
     reps = channels // z['stereo'].shape[1] + 1
     rng = np.random.RandomState(7)
@@ -166,6 +168,129 @@ def test_frustum_to_voxel_backward_few_channels(pkg, channels):
     (out * go.cuda()).sum().backward()
     np.testing.assert_allclose(sg.grad.cpu().numpy(), sr.grad.numpy(), **TOL)
     np.testing.assert_allclose(mg.grad.cpu().numpy(), mr.grad.numpy(), **TOL)
+
+
+def _f2v_c_abi(pkg, case, dtype, sem_atten, stereo_atten):
+    """the raw library's view of ``case`` (a dict of CPU tensors, see _f2v_batch2_case): descriptor, device
+    tensors in ``dtype`` and zeroed fp32 gradients, for calls of dfm_frustum_to_voxel_*bwd through ``launch``"""
+    dev = torch.device('cuda:0')
+    stereo, sem, soft, coords = case['stereo'], case['sem'], case['soft'], case['coords']
+    d = pkg._capi.F2vDesc()
+    d.batch, d.channels, d.d, d.h, d.w = stereo.shape
+    d.sem_channels, d.hsem, d.wsem = sem.shape[1:]
+    d.ds, d.hs, d.ws = soft.shape[2:]
+    d.nz, d.ny, d.nx = coords.shape[:3]
+    d.pad_h, d.pad_w = float(case['pad'][0]), float(case['pad'][1])
+    d.depth_min, d.depth_span = case['dmin'], case['dmax'] - case['dmin']
+    d.dtype = pkg._capi.DFM_F32 if dtype == torch.float32 else pkg._capi.DFM_BF16
+    d.stereo_atten, d.no_sem_atten = int(stereo_atten), int(not sem_atten)
+    cam4 = case['cam'].reshape(-1, 16).contiguous().to(dev)
+    g_sem = torch.zeros(sem.shape, device=dev) if sem.shape[1] else None
+    return (d, case['go'].to(dev).to(dtype), soft.to(dev).to(dtype), coords.contiguous().to(dev), cam4,
+            torch.zeros(stereo.shape, device=dev), g_sem)
+
+
+_F2V_CASES = {}
+
+
+def _f2v_batch2_case(channels, sem_atten, stereo_atten, soft=None):
+    """f2v_batch2 widened to ``channels`` (as test_frustum_to_voxel_backward_attention_switches does) with the
+    gradients of torch autograd through ``_f2v_torch``; computed once per key, read-only"""
+    key = (channels, sem_atten, stereo_atten, soft is None)
+    if key not in _F2V_CASES:
+        z = np.load(os.path.join(util.GOLDEN, 'f2v_batch2.npz'))
+        reps = channels // z['stereo'].shape[1] + 1
+        rng = np.random.RandomState(7)
+        stereo = torch.from_numpy(np.tile(z['stereo'], (1, reps, 1, 1, 1))[:, :channels] *
+                                  rng.rand(1, channels, 1, 1, 1).astype(np.float32)).contiguous()
+        sem = torch.from_numpy(np.tile(z['sem'], (1, reps, 1, 1))[:, :channels] *
+                               rng.rand(1, channels, 1, 1).astype(np.float32)).contiguous()
+        case = dict(stereo=stereo, sem=sem, soft=torch.from_numpy(z['softmax']) if soft is None else soft,
+                    coords=torch.from_numpy(z['coordinates_3d']), cam=torch.from_numpy(z['cam2img']),
+                    pad=tuple(int(v) for v in z['pad_shape']), dmin=float(z['depth_min']), dmax=float(z['depth_max']))
+        _f2v_reference_grads(case, rng, sem_atten, stereo_atten)
+        _F2V_CASES[key] = case
+    return _F2V_CASES[key]
+
+
+def _f2v_reference_grads(case, rng, sem_atten, stereo_atten):
+    sr, mr = case['stereo'].clone().requires_grad_(True), case['sem'].clone().requires_grad_(True)
+    ref = _f2v_torch(sr, case['soft'], mr, case['coords'], case['cam'], case['pad'], case['dmin'], case['dmax'],
+                     sem_atten, stereo_atten)
+    case['go'] = torch.from_numpy(rng.randn(*ref.shape).astype(np.float32))
+    (ref * case['go']).sum().backward()
+    case['g_stereo'], case['g_sem'] = sr.grad, mr.grad
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['fp32', 'bf16'])
+@pytest.mark.parametrize('sem_atten,stereo_atten', [(True, False), (False, True)])
+@pytest.mark.parametrize('channels', [3, 8])
+def test_frustum_to_voxel_backward_lane_per_voxel_scatter(pkg, channels, sem_atten, stereo_atten, dtype):
+    """f2v_bwd_kernel, the scatter the library takes when the caller passes NO workspace (the package always
+    passes one): through the C ABI.  fp32: against torch autograd of ``_f2v_torch``; bf16: against the pixel-major
+    form (the same call with a workspace) on the identical bf16 inputs -- both accumulate in fp32, so the fp32
+    tolerance holds there too."""
+    L = importlib.import_module('depth-from-motion_amd._launch')
+    case = _f2v_batch2_case(channels, sem_atten, stereo_atten)
+    desc, go, soft, coords, cam4, g_st, g_sem = _f2v_c_abi(pkg, case, dtype, sem_atten, stereo_atten)
+    L.launch('dfm_frustum_to_voxel_bwd', desc, go, soft, coords, cam4, g_st, g_sem, None, 0, L.STREAM)
+    if dtype == torch.float32:
+        want_st, want_sem = case['g_stereo'].numpy(), case['g_sem'].numpy()
+    else:
+        p_st, p_sem = torch.zeros_like(g_st), torch.zeros_like(g_sem)
+        nbytes = pkg._capi.lib().dfm_frustum_to_voxel_bwd_workspace_bytes(ctypes.byref(desc))
+        L.launch('dfm_frustum_to_voxel_bwd', desc, go, soft, coords, cam4, p_st, p_sem, L.WS, L.STREAM,
+                 ws_bytes=nbytes)
+        want_st, want_sem = p_st.cpu().numpy(), p_sem.cpu().numpy()
+    assert np.abs(want_st).max() > 0 and np.abs(want_sem).max() > 0
+    np.testing.assert_allclose(g_st.cpu().numpy(), want_st, **TOL)
+    np.testing.assert_allclose(g_sem.cpu().numpy(), want_sem, **TOL)
+
+
+@pytest.mark.parametrize('sem_atten,stereo_atten', [(True, False), (False, True)])
+def test_frustum_to_voxel_fused_backward_lane_per_voxel_scatter(pkg, sem_atten, stereo_atten):
+    """the same kernel with the depth head fused (dfm_frustum_to_voxel_fused_bwd, NULL workspace): the
+    distribution evaluated from a low-resolution cost, against autograd through the materialised softmax"""
+    L = importlib.import_module('depth-from-motion_amd._launch')
+    dev = torch.device('cuda:0')
+    B, _, Ds, Hs, Ws = np.load(os.path.join(util.GOLDEN, 'f2v_batch2.npz'))['softmax'].shape
+    gen = torch.Generator().manual_seed(Ds)
+    cost = (torch.randn(B, 1, Ds // 4, Hs // 4, Ws // 4, generator=gen) * 4).to(dev)
+    samples = torch.tensor([2 + (k + 0.5) * (57.6 / Ds) for k in range(Ds)])
+    soft = pkg.depth_head_forward(cost, samples, 4)[1]
+    lazy, _ = pkg.depth_head_statistics(cost, samples, 4)
+    case = _f2v_batch2_case(3, sem_atten, stereo_atten, soft=soft.cpu())
+    desc, go, _, coords, cam4, g_st, g_sem = _f2v_c_abi(pkg, case, torch.float32, sem_atten, stereo_atten)
+    L.launch('dfm_frustum_to_voxel_fused_bwd', desc, go, lazy.cost, lazy.col_max, lazy.col_sum, int(lazy.scale),
+             coords, cam4, g_st, g_sem, None, 0, L.STREAM)
+    assert float(case['g_stereo'].abs().max()) > 0 and float(case['g_sem'].abs().max()) > 0
+    np.testing.assert_allclose(g_st.cpu().numpy(), case['g_stereo'].numpy(), **TOL)
+    np.testing.assert_allclose(g_sem.cpu().numpy(), case['g_sem'].numpy(), **TOL)
+
+
+def test_frustum_to_voxel_backward_too_many_channels_for_the_lds_tile(pkg):
+    """f2v_bwd_kernel through its other door: C = 240, Cs = 0 WITH a workspace.  The pixel-major form's LDS tile
+    would be 240 * 65 * 4 + 64 * 96 = 68544 bytes > 64 KiB, so the library must fall back to the lane-per-voxel
+    scatter.  2 x 3 x 4 voxels inside the frustum of a 16 x 32 image; stereo_atten, so the distribution is read."""
+    L = importlib.import_module('depth-from-motion_amd._launch')
+    rng = np.random.RandomState(11)
+    B, C, D, H, W = 2, 240, 2, 3, 4
+    xs, ys, zs = torch.linspace(2.0, 4.0, 4), torch.linspace(-1.0, 1.0, 3), torch.linspace(-0.5, 0.5, 2)
+    coords = torch.stack(torch.meshgrid(zs, ys, xs, indexing='ij')[::-1], -1).contiguous()   # (Nz, Ny, Nx, xyz)
+    cam = torch.eye(4).repeat(B, 1, 1)
+    cam[:, 0, 0] = cam[:, 1, 1] = 20.0
+    cam[:, 0, 2], cam[:, 1, 2] = 16.0, 8.0      # u = 16 - 20 y / x in [6, 26], v = 8 - 20 z / x in [3, 13]
+    cam[1, 0, 2] = 15.0                          # (the second sample looks elsewhere)
+    case = dict(stereo=torch.from_numpy(rng.randn(B, C, D, H, W).astype(np.float32)), sem=torch.zeros(B, 0, H, W),
+                soft=torch.softmax(torch.from_numpy(rng.randn(B, 1, 4, 6, 8).astype(np.float32)), 2),
+                coords=coords, cam=cam, pad=(16, 32), dmin=1.0, dmax=5.0)
+    _f2v_reference_grads(case, rng, True, True)
+    desc, go, soft, coords_g, cam4, g_st, g_sem = _f2v_c_abi(pkg, case, torch.float32, True, True)
+    assert g_sem is None
+    nbytes = pkg._capi.lib().dfm_frustum_to_voxel_bwd_workspace_bytes(ctypes.byref(desc))
+    L.launch('dfm_frustum_to_voxel_bwd', desc, go, soft, coords_g, cam4, g_st, g_sem, L.WS, L.STREAM, ws_bytes=nbytes)
+    assert float(case['g_stereo'].abs().amax((1, 2, 3, 4)).min()) > 0   # both samples see the voxels
+    np.testing.assert_allclose(g_st.cpu().numpy(), case['g_stereo'].numpy(), **TOL)
 
 
 @pytest.mark.parametrize('channels', [1, 2])
