@@ -30,6 +30,7 @@ from .anchor_target import (BboxOverlapsNearest3D, HipAnchorTrainMixin, anchor_t
                             bbox_overlaps_nearest_3d)
 from .bbox_decode import (HipAnchor3DHeadMixin, anchor3d_get_bboxes, anchor_head_candidates,  # noqa: F401
                           delta_xyzwlhr_decode)
+from .atss_target import BboxOverlaps2D, HipATSSTargetMixin, atss_target_2d, bbox_overlaps  # noqa: F401
 from .data_geometry import (fold_ref_frame_matrices, select_ref_frames, stage_geometry,  # noqa: F401
                             video_cur2prevs)
 from .point_sample import (mv_feature_transformation, point_sample, voxel_centers,  # noqa: F401
@@ -46,4 +47,5 @@ __all__ = ['build_dfm_cost', 'plane_sweep_grid', 'point_sample', 'mv_feature_tra
            'nms_bev', 'nms_normal_bev', 'box_iou_rotated', 'diff_iou_rotated_3d', 'diff_iou_rotated_2d', 'iou3d_loss',
            'IOU3DLoss', 'iou3d_loss_from_deltas', 'bbox_overlaps_nearest_3d', 'BboxOverlapsNearest3D',
            'anchor_target_3d', 'HipAnchorTrainMixin', 'delta_xyzwlhr_decode', 'anchor_head_candidates',
-           'anchor3d_get_bboxes', 'HipAnchor3DHeadMixin']
+           'anchor3d_get_bboxes', 'HipAnchor3DHeadMixin', 'bbox_overlaps', 'BboxOverlaps2D', 'atss_target_2d',
+           'HipATSSTargetMixin']

@@ -177,6 +177,19 @@ class AnchorHeadDesc(ctypes.Structure):
         [(n, ctypes.c_int64 * 4) for n in ('cls_stride', 'reg_stride', 'dir_stride')]
 
 
+ATSS_MAX_LEVELS, ATSS_MAX_TOPK, ATSS_MAX_BATCH = 8, 16, 64  # DFM_ATSS_MAX_*
+ATSS_THRESH_MEANSTD, ATSS_THRESH_RATIO = 0, 1  # DFM_ATSS_THRESH_*
+ATSS_CODER_DELTA_XYWH = 0  # DFM_ATSS_CODER_DELTA_XYWH
+
+
+class AtssTargetDesc(ctypes.Structure):
+    """struct dfm_atss_target_desc"""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        'num_anchors', 'num_levels', 'batch', 'gt_width', 'topk', 'num_classes', 'thresh_mode', 'reg_width', 'coder',
+        'sampler', 'num_ignore_boxes')] + [('ignore_iof_thr', ctypes.c_float), ('pos_weight', ctypes.c_float),
+                                           ('target_means', ctypes.c_float * 4), ('target_stds', ctypes.c_float * 4)]
+
+
 DFM_ERR_UNSUPPORTED = -2  # include/dfm_hip.h
 BOX_NMS_MAX_N = 16384  # DFM_BOX_NMS_MAX_N
 
@@ -344,6 +357,23 @@ BBOX_DECODE_SIGNATURES = _bbox_decode_signatures()
 BBOX_DECODE_EXPORTS = tuple(BBOX_DECODE_SIGNATURES)
 
 
+def _atss_target_signatures():
+    """the same for include/dfm_hip_atss_target.h: 2-D box overlaps and the 2-D ATSS head's training targets
+    (tests/test_atss_target.py checks this table against that header and the built library)"""
+    vp = fp = ctypes.c_void_p
+    ci, i32, sz, adp = ctypes.c_int, ctypes.c_int32, ctypes.c_size_t, ctypes.POINTER(AtssTargetDesc)
+    return {
+        'dfm_bbox_overlaps_2d': (ci, [fp, i32, fp, i32, i32, i32, fp, vp]),
+        'dfm_atss_target_workspace_bytes': (sz, [adp, i32]),
+        'dfm_atss_target_2d': (ci, [adp, fp, ctypes.POINTER(i32), vp, fp, ctypes.POINTER(i32), vp, vp, fp, fp, fp, vp,
+                                    vp, vp, sz, vp]),
+    }
+
+
+ATSS_TARGET_SIGNATURES = _atss_target_signatures()
+ATSS_TARGET_EXPORTS = tuple(ATSS_TARGET_SIGNATURES)
+
+
 _lib = None
 
 
@@ -358,7 +388,8 @@ def lib():
             '`python -c "import __graft_entry__ as g; g.build()"` '
             '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
     h = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in (*SIGNATURES.items(), *BBOX_DECODE_SIGNATURES.items()):
+    for name, (restype, argtypes) in (*SIGNATURES.items(), *BBOX_DECODE_SIGNATURES.items(),
+                                      *ATSS_TARGET_SIGNATURES.items()):
         fn = getattr(h, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = h

@@ -39,6 +39,8 @@ from . import anchor_target as _anchor_target
 from .anchor_target import HipAnchorTrainMixin, bbox_overlaps_nearest_3d
 from . import bbox_decode as _bbox_decode
 from .bbox_decode import HipAnchor3DHeadMixin
+from . import atss_target as _atss_target
+from .atss_target import HipATSSTargetMixin
 from .geometry import prepare_coordinates_3d, prepare_depth
 from .conv3d import MfmaConv3dTo1
 from .graphs import GraphedCallable
@@ -430,6 +432,30 @@ def _patch_anchor_head():
     return methods
 
 
+# the 2-D ATSS head's target assignment: LIGAATSSHead inherits get_targets from mmdet's ATSSHead; the class gets
+# this package's method, the inherited one is kept for the fallback policy.  mmdet's bbox_overlaps is rebound nowhere.
+# Only where liga_atss_head.py is already imported, as above: it imports mmdet.
+_ATSS_HEAD_MODULES = ('mmdet3d.models.dense_heads.liga_atss_head',)
+
+
+def _patch_atss_target():
+    """-> methods rebound"""
+    methods = []
+    for mod_name in _ATSS_HEAD_MODULES:
+        mod = sys.modules.get(mod_name)
+        cls = getattr(mod, 'LIGAATSSHead', None) if mod is not None else None
+        if cls is not None and hasattr(cls, 'get_targets'):
+            ours = vars(HipATSSTargetMixin)['get_targets']
+            if vars(cls).get('get_targets') is not ours:
+                _atss_target._REFERENCE['get_targets'] = cls.get_targets        # (inherited from ATSSHead)
+                cls.get_targets = ours
+                # the helpers the rebound method calls on ``self``
+                for helper in ('_atss_target_unsupported', '_atss_target_fallback'):
+                    setattr(cls, helper, vars(HipATSSTargetMixin)[helper])
+            methods.append('LIGAATSSHead.get_targets')
+    return methods
+
+
 def patch_reference(precision=None, strict=False):
     """Route a real mmdet3d (the reference fork) to the HIP path.  Call once after
     ``import mmdet3d`` and before building the model from ``configs/dfm/*``.  Returns a report
@@ -458,6 +484,7 @@ def patch_reference(precision=None, strict=False):
     report['functions'] += functions
     report['methods'] += methods
     report['methods'] += _patch_anchor_head()
+    report['methods'] += _patch_atss_target()
     try:
         det = importlib.import_module('mmdet3d.models.detectors.multiview_dfm')
         det.MultiViewDfM.feature_transformation = MultiViewDfMMixin.feature_transformation

@@ -1368,6 +1368,10 @@ DFM_API int dfm_spp_tail_fwd(const dfm_spp_desc *desc, const void *const *pooled
  * of their own, which is part of this one */
 #include "dfm_hip_bbox_decode.h"
 
+/* 2-D box overlaps and the 2-D ATSS head's training targets (dfm_bbox_overlaps_2d, dfm_atss_target_2d,
+ * dfm_atss_target_workspace_bytes): likewise */
+#include "dfm_hip_atss_target.h"
+
 #ifdef __cplusplus
 }
 #endif

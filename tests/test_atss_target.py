@@ -1,0 +1,352 @@
+"""CPU: the ATSS-target feature above the kernels -- the fixture's stored overlaps against box pairs computed by hand,
+the fixture's cases, guards and error figures, the exported names, the registry entry, the new header against its
+binding table and the library, the C entries' argument checks, the refusal of CPU tensors and the rebinding of a stub
+LIGAATSSHead.
+
+Fixture numbers (tests/golden/atss_target.npz, generator tests/golden/make_golden_atss_target.py): the fp32 CPU run of
+the reference differs from its fp64 run by at most ``fp32_target_error`` = 1.2e-6 in an encoded target (deltas divided
+by 0.1 and 0.2: values up to ~10, one fp32 ulp there is 9.5e-7) and by ``fp32_overlap_error`` = 1.5e-7 in a standalone
+overlap.  The GPU tests read these two."""
+import ctypes
+import importlib
+import math
+import os
+import re
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from tests import util
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ('dfm_bbox_overlaps_2d', 'dfm_atss_target_workspace_bytes', 'dfm_atss_target_2d')
+NAMES = ('bbox_overlaps', 'BboxOverlaps2D', 'atss_target_2d', 'HipATSSTargetMixin')
+# case: (level sizes, GT boxes per image, GT width)
+FIVE = [1024, 256, 64, 16, 4]
+CASES = {'tiny': ([24, 6], [3], 6), 'posw': ([24, 6], [3], 6), 'odd': ([63, 20, 6], [5], 6), 'five': (FIVE, [12, 5], 6),
+         'empty': (FIVE, [6, 0], 6), 'g70': (FIVE, [70], 6), 'border': (FIVE, [6, 6], 6), 'valid': (FIVE, [6, 6], 6),
+         'centre4': (FIVE, [6], 4), 'rules': (FIVE, [6], 6)}
+
+
+@pytest.fixture(scope='module')
+def pkg():
+    importlib.import_module('depth-from-motion_amd.build').build_hip()
+    return importlib.import_module('depth-from-motion_amd')
+
+
+@pytest.fixture(scope='module')
+def z():
+    return np.load(os.path.join(util.GOLDEN, 'atss_target.npz'))
+
+
+def iou(a, b):
+    w = max(0.0, min(a[2], b[2]) - max(a[0], b[0]))
+    h = max(0.0, min(a[3], b[3]) - max(a[1], b[1]))
+    return w * h / max((a[2] - a[0]) * (a[3] - a[1]) + (b[2] - b[0]) * (b[3] - b[1]) - w * h, 1e-6)
+
+
+def test_stored_overlaps_match_hand_computed_pairs(z):
+    b1, b2 = z['hand/boxes1'], z['hand/boxes2']
+    got, iof = z['hand/aligned_iou'], z['hand/aligned_iof']
+    assert b1.shape == b2.shape == (8, 4) and got.dtype == np.float64
+    # 2 x 2 squares one unit apart in x, then in y: overlap 2, union 6; over the first box 2 / 4
+    assert abs(got[0] - 1 / 3) < 1e-15 and iof[0] == 0.5 and abs(got[1] - 1 / 3) < 1e-15 and iof[1] == 0.5
+    # containment both ways: 4 of 16; over the first box 4 / 16, then 4 / 4
+    assert got[2] == 0.25 and iof[2] == 0.25 and got[3] == 0.25 and iof[3] == 1.0
+    # disjoint boxes, and two empty boxes (0 / max(0, 1e-6))
+    assert got[4] == 0.0 and iof[4] == 0.0 and got[5] == 0.0 and iof[5] == 0.0
+    # the same box, and squares one unit apart along the diagonal: 1 of 4 + 4 - 1
+    assert got[6] == 1.0 and iof[6] == 1.0 and abs(got[7] - 1 / 7) < 1e-15 and iof[7] == 0.25
+    assert np.array_equal(np.diag(z['hand/iou']), got) and np.array_equal(np.diag(z['hand/iof']), iof)
+    assert z['overlaps/iou'].shape == (130, 37) and z['overlaps/aligned_iof'].shape == (37,)
+    assert np.array_equal(np.diag(z['overlaps/iou'][:37]), z['overlaps/aligned_iou'])
+    assert np.array_equal(np.diag(z['overlaps/iof'][:37]), z['overlaps/aligned_iof'])
+    assert (z['overlaps/iou'] > 0).sum() > 37 and z['overlaps/iou'].max() <= 1.0
+    i, j = 5, 5
+    assert abs(z['overlaps/iou'][i, j] - iou(z['overlaps/boxes1'][i].astype(float),
+                                            z['overlaps/boxes2'][j].astype(float))) < 1e-15
+
+
+def test_stored_error_figures_and_guards(z):
+    for key in ('fp32_overlap_error', 'fp32_target_error'):
+        v = float(z[key])
+        assert 0 < v < 1e-5 and math.isfinite(v), key
+    assert float(z['fp32_overlap_error']) <= 1.5e-7 and float(z['fp32_target_error']) <= 1.2e-6   # the docstring's
+    assert float(z['guard']) == 1e-5 and float(z['cut_guard']) == 1e-3 and float(z['inset_guard']) == 1e-3
+    # the smallest margins the generator saw, each above its guard
+    assert math.isfinite(float(z['margin_cut'])) and float(z['margin_cut']) >= 1e-3
+    assert float(z['margin_thr']) >= 1e-5 and float(z['margin_inset']) >= 1e-3 and float(z['margin_claim']) >= 1e-5
+    assert int(z['topk']) == 9 and int(z['num_classes']) == 3
+    assert z['target_means'].tolist() == [0, 0, 0, 0] and z['target_stds'].tolist() == [0.1, 0.1, 0.2, 0.2]
+    assert os.path.getsize(os.path.join(util.GOLDEN, 'atss_target.npz')) < 512 * 1024
+
+
+@pytest.mark.parametrize('case', sorted(CASES))
+def test_cases_are_stored_whole(z, case):
+    sizes, G, width = CASES[case]
+    A, B = sum(sizes), len(G)
+    assert z[f'{case}/level_sizes'].tolist() == sizes and z[f'{case}/anchors'].shape == (A, 4)
+    assert z[f'{case}/anchors'].dtype == np.float32 and z[f'{case}/gt_boxes'].dtype == np.float32
+    assert np.diff(z[f'{case}/gt_offsets']).tolist() == G and z[f'{case}/gt_offsets'][0] == 0
+    assert z[f'{case}/gt_boxes'].shape == (sum(G), width) and z[f'{case}/gt_labels'].dtype == np.int64
+    labels, lw, bt, bw, assigned, counts, inside = (z[f'{case}/{k}'] for k in (
+        'labels', 'label_weights', 'bbox_targets', 'bbox_weights', 'assigned_gt_inds', 'counts', 'inside'))
+    assert labels.shape == assigned.shape == lw.shape == inside.shape == (B, A)
+    assert labels.dtype == np.int64 and assigned.dtype == np.int64 and bt.dtype == np.float64
+    assert bt.shape == bw.shape == (B, A, 4) and counts.shape == (B, 2) and counts.dtype == np.int32
+    assert np.array_equal(counts[:, 0], (assigned > 0).sum(1))
+    assert np.array_equal(counts.sum(1), (assigned >= 0).sum(1))
+    assert np.array_equal(assigned >= 0, inside != 0)
+    assert int(z[f'{case}/num_total_pos']) == np.maximum(counts[:, 0], 1).sum()
+    assert int(z[f'{case}/num_total_neg']) == np.maximum(counts[:, 1], 1).sum()
+    pos = assigned > 0
+    off = z[f'{case}/gt_offsets']
+    for b in range(B):                                            # a positive carries its GT's label
+        assert np.array_equal(labels[b][pos[b]], z[f'{case}/gt_labels'][off[b]:off[b + 1]][assigned[b][pos[b]] - 1])
+        assert assigned[b].max() <= G[b]
+    assert np.all(labels[~pos] == 3) and np.all(bt[~pos] == 0) and np.all(bw[pos] == 1) and np.all(bw[~pos] == 0)
+    assert np.all(lw[pos] == (2.0 if case == 'posw' else 1.0)) and np.all(lw[(assigned == 0)] == 1)
+    assert np.all(lw[assigned < 0] == 0)
+    assert np.array_equal(z[f'{case}/anchors_out'], z[f'{case}/anchors'][None] * (inside[..., None] != 0))
+    cent = z[f'{case}/centerness']
+    assert cent.shape == (counts[:, 0].sum(),) and np.all((cent > 0) & (cent <= 1))
+    # the anchors are what the docstring says: squares of side 16 x stride on the stride's lattice, y-major
+    a = z[f'{case}/anchors']
+    side = a[:, 2] - a[:, 0]
+    assert np.array_equal(side, a[:, 3] - a[:, 1]) and side[0] * 2 == side[sizes[0]]
+    stride = side[0] / 16
+    assert a[1, 0] - a[0, 0] == stride and a[0, 0] == -8 * stride
+
+
+def test_cases_reach_every_branch(z):
+    assert z['empty/counts'][1].tolist() == [0, 1364] and np.all(z['empty/labels'][1] == 3)
+    assert len(z['g70/gt_labels']) > 64                            # more than one chunk of 64 GT boxes
+    assert np.array_equal(z['posw/gt_boxes'], z['tiny/gt_boxes']) and float(z['posw/pos_weight']) == 2
+    # border: the inside rows differ per image, only a part of the finest level counts, the coarser ones do not
+    inside = z['border/inside'] != 0
+    assert int(z['border/allowed_border']) == 16 and z['border/img_shapes'].tolist() == [[60, 250], [64, 256]]
+    assert not np.array_equal(inside[0], inside[1]) and 0 < inside[0, :1024].sum() < inside[1, :1024].sum() < 1024
+    assert inside[:, 1024:].sum() == 0 and np.all(z['border/counts'][:, 0] > 0)
+    # valid: the pad shape of image 0 cuts the last column of the coarsest level (3 of 4 count: k_l = 3)
+    inside = z['valid/inside'] != 0
+    assert int(z['valid/allowed_border']) == -1 and np.array_equal(inside, z['valid/valid_flags'] != 0)
+    assert inside[0, 1360:].tolist() == [True, True, True, False] and inside[1].all()
+    assert 0 < inside[0, :1024].sum() < 1024
+    for case in CASES:
+        if case not in ('border', 'valid'):
+            assert z[f'{case}/inside'].all() and z[f'{case}/valid_flags'].all(), case
+
+
+def test_rules_case_tells_its_four_stories(z):
+    gt, assigned, a = z['rules/gt_boxes'], z['rules/assigned_gt_inds'][0], z['rules/anchors'].astype(np.float64)
+    labels = z['rules/labels'][0]
+    # off: the point lies outside the box; the GT has candidates (it is an ordinary box) and no positive
+    assert not (gt[0, 0] < gt[0, 4] < gt[0, 2]) and not (assigned == 1).any()
+    # twin: identical boxes, different labels; the lower index wins every anchor
+    assert np.array_equal(gt[1], gt[2]) and z['rules/gt_labels'][1] != z['rules/gt_labels'][2]
+    assert (assigned == 2).sum() > 0 and (assigned == 3).sum() == 0
+    assert set(labels[assigned == 2].tolist()) == {int(z['rules/gt_labels'][1])}
+    # claim: the anchor both GTs claim goes to the later one, whose overlap is higher
+    i = int(z['rules/claim_anchor'])
+    first, second = iou(a[i], gt[3, :4].astype(np.float64)), iou(a[i], gt[4, :4].astype(np.float64))
+    assert assigned[i] == 5 and second > first + 1e-5 and (assigned == 4).any()
+    # small: a 6 x 6 box whose positives all lie in the finest level
+    assert gt[5, 2] - gt[5, 0] == 6 and gt[5, 3] - gt[5, 1] == 6
+    won = np.nonzero(assigned == 6)[0]
+    assert len(won) >= 1 and won.max() < 1024
+
+
+def test_tiny_second_level_is_taken_whole(z):
+    cand = z['tiny/candidates']                                   # (N, G): 9 of level 1, then all 6 of level 2
+    assert cand.shape == (15, 3)
+    for g in range(3):
+        assert np.all(cand[:9, g] < 24) and len(set(cand[:9, g].tolist())) == 9
+        assert sorted(cand[9:, g].tolist()) == list(range(24, 30))
+
+
+def test_names_are_exported(pkg):
+    for name in NAMES:
+        assert callable(getattr(pkg, name)) and name in pkg.__all__, name
+    mod = importlib.import_module('depth-from-motion_amd.atss_target')
+    assert set(NAMES) == set(mod.__all__)
+
+
+def test_registry_builds_the_iou_calculator(pkg):
+    reg = importlib.import_module('depth-from-motion_amd.registry')
+    calc = reg.build(dict(type='BboxOverlaps2D'))                 # ATSS3DCenterAssigner's default iou_calculator
+    assert isinstance(calc, pkg.BboxOverlaps2D)
+    assert pkg.BboxOverlaps2D not in reg.path_classes()
+
+
+def test_header_binding_and_library_agree_on_the_new_symbols(pkg):
+    """the new entry points live in include/dfm_hip_atss_target.h, which dfm_hip.h includes; their binding table is
+    _capi.ATSS_TARGET_SIGNATURES, applied by _capi.lib() beside the two others"""
+    main = open(os.path.join(ROOT, 'include', 'dfm_hip.h')).read()
+    assert '#include "dfm_hip_atss_target.h"' in main
+    text = open(os.path.join(ROOT, 'include', 'dfm_hip_atss_target.h')).read()
+    code = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    decls = {}
+    for m in re.finditer(r'^DFM_API\s+([\w\s\*]+?)\b(dfm_\w+)\s*\(([^)]*)\)\s*;', code, flags=re.M):
+        decls[m.group(2)] = (' '.join(m.group(1).split()), m.group(3).count(',') + 1)
+    capi = pkg._capi
+    assert sorted(decls) == sorted(NEW) == sorted(capi.ATSS_TARGET_SIGNATURES)
+    assert capi.ATSS_TARGET_EXPORTS == tuple(capi.ATSS_TARGET_SIGNATURES)
+    assert not set(NEW) & set(capi.EXPORTS) and not set(NEW) & set(capi.BBOX_DECODE_EXPORTS)
+    assert len(capi.EXPORTS) == 114                               # the main header keeps its declarations
+    restypes = {'int': ctypes.c_int, 'size_t': ctypes.c_size_t}
+    h, lib = ctypes.CDLL(capi.LIB_PATH), capi.lib()
+    for name, (ret, nparams) in decls.items():
+        restype, argtypes = capi.ATSS_TARGET_SIGNATURES[name]
+        assert len(argtypes) == nparams and restype is restypes[ret], name
+        assert hasattr(h, name), f'{name} not exported by the library'
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    for phrase in ('ASCENDING anchor index', 'those with the lowest indices are taken', 'LOWEST GT index',
+                   'An iou of 0.0 can win', 'unbiased std (divisor N - 1)', 'N <= 1 gives', 'FINITE by contract',
+                   'max(a1 + a2 - overlap, 1e-6)', 'max(a1, 1e-6)', '> 0.01', 'No host synchronisation'):
+        assert phrase in text, phrase                             # the semantics are stated in the header
+    for name, value in (('DFM_ATSS_MAX_LEVELS', capi.ATSS_MAX_LEVELS), ('DFM_ATSS_MAX_TOPK', capi.ATSS_MAX_TOPK),
+                        ('DFM_ATSS_MAX_BATCH', capi.ATSS_MAX_BATCH)):
+        assert int(re.search(rf'#define {name} (\d+)', text).group(1)) == value
+    assert (capi.ATSS_MAX_LEVELS, capi.ATSS_MAX_TOPK, capi.ATSS_MAX_BATCH) == (8, 16, 64)
+    # the descriptor's size follows the header: 11 ints, 2 floats, 2 x 4 floats
+    assert ctypes.sizeof(capi.AtssTargetDesc) == 4 * (11 + 2 + 8)
+    assert lib.dfm_version() == 3
+
+
+def desc(pkg, **kw):
+    d = pkg._capi.AtssTargetDesc(num_anchors=30, num_levels=2, batch=1, gt_width=6, topk=9, num_classes=3,
+                                 reg_width=4, ignore_iof_thr=-1.0, pos_weight=-1.0)
+    for c in range(4):
+        d.target_stds[c] = 1.0
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+def test_bad_arguments_are_rejected_without_touching_the_gpu(pkg):
+    lib = pkg._capi.lib()
+    buf = ctypes.create_string_buffer(4096 + 16)
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)      # 16-byte aligned host memory, never dereferenced
+    odd = ctypes.c_void_p(p.value + 8)
+    unsupported = pkg._capi.DFM_ERR_UNSUPPORTED
+    # (boxes1, n, boxes2, m, mode, aligned, out, stream)
+    ov = lib.dfm_bbox_overlaps_2d
+    assert ov(None, -1, None, 4, 0, 0, None, None) == -1
+    assert ov(None, 4, None, 4, 2, 0, None, None) == -1 and b'mode' in lib.dfm_last_error()
+    assert ov(None, 4, None, 5, 0, 1, None, None) == -1 and b'aligned' in lib.dfm_last_error()
+    assert ov(None, 0, None, 5, 1, 0, None, None) == 0            # an empty set: a valid no-op
+    assert ov(None, 4, None, 4, 0, 0, None, None) == -1 and b'NULL' in lib.dfm_last_error()
+    assert ov(p, 4, p, 4, 0, 0, None, None) == -1
+    assert ov(odd, 4, p, 4, 0, 0, p, None) == -1 and b'16-byte' in lib.dfm_last_error()
+    # (desc, anchors, level_sizes, inside, gt, gt_offsets, gt_labels, 5 outputs, counts, workspace, bytes, stream)
+    at = lib.dfm_atss_target_2d
+    sizes = (ctypes.c_int32 * 2)(24, 6)
+    off = (ctypes.c_int32 * 2)(0, 3)
+    outs = (p,) * 6
+
+    def call(d, anchors=p, levels=sizes, inside=None, gt=p, offsets=off, labels=p, outputs=outs, ws=p, ws_bytes=4096):
+        return at(ctypes.byref(d) if d is not None else None, anchors, levels, inside, gt, offsets, labels, *outputs,
+                  ws, ws_bytes, None)
+    assert call(None) == -1
+    assert call(desc(pkg, thresh_mode=1)) == unsupported and b'thresh_mode' in lib.dfm_last_error()
+    assert call(desc(pkg, reg_width=6)) == unsupported and b'reg_width' in lib.dfm_last_error()
+    assert call(desc(pkg, coder=1)) == unsupported and b'coder' in lib.dfm_last_error()
+    assert call(desc(pkg, sampler=1)) == unsupported and b'sampler' in lib.dfm_last_error()
+    assert call(desc(pkg, ignore_iof_thr=0.5, num_ignore_boxes=2)) == unsupported and b'ignore' in lib.dfm_last_error()
+    for topk in (0, 17):
+        assert call(desc(pkg, topk=topk)) == -1 and b'topk' in lib.dfm_last_error()
+    assert call(desc(pkg, num_levels=9)) == -1 and b'DFM_ATSS_MAX_LEVELS' in lib.dfm_last_error()
+    assert call(desc(pkg, num_levels=0)) == -1
+    assert call(desc(pkg, batch=65)) == -1 and b'DFM_ATSS_MAX_BATCH' in lib.dfm_last_error()
+    assert call(desc(pkg, gt_width=7)) == -1 and b'gt_width' in lib.dfm_last_error()
+    assert call(desc(pkg, num_anchors=-1)) == -1
+    assert call(desc(pkg, batch=0)) == 0 and call(desc(pkg, num_anchors=0)) == 0        # nothing to do: no-ops
+    assert call(desc(pkg), levels=None) == -1 and b'level_sizes' in lib.dfm_last_error()
+    assert call(desc(pkg), levels=(ctypes.c_int32 * 2)(24, 7)) == -1 and b'sum' in lib.dfm_last_error()
+    assert call(desc(pkg), levels=(ctypes.c_int32 * 2)(31, -1)) == -1
+    assert call(desc(pkg), offsets=None) == -1 and b'gt_offsets' in lib.dfm_last_error()
+    assert call(desc(pkg), offsets=(ctypes.c_int32 * 2)(1, 2)) == -1
+    assert call(desc(pkg), offsets=(ctypes.c_int32 * 2)(0, -1)) == -1
+    assert call(desc(pkg), anchors=None) == -1 and b'NULL' in lib.dfm_last_error()
+    assert call(desc(pkg), anchors=odd) == -1 and b'16-byte' in lib.dfm_last_error()
+    assert call(desc(pkg), gt=None) == -1 and b'gt_boxes' in lib.dfm_last_error()
+    for k in range(6):
+        assert call(desc(pkg), outputs=outs[:k] + (None,) + outs[k + 1:]) == -1
+    assert call(desc(pkg), outputs=(p, p, odd, p, p, p)) == -1 and b'16-byte' in lib.dfm_last_error()
+    # workspace: 30 keys of 8 bytes, then two tables of 3 GT x 2 levels x 9 entries of 4 bytes (216 -> 224)
+    size = lib.dfm_atss_target_workspace_bytes
+    assert size(ctypes.byref(desc(pkg)), 3) == 240 + 2 * 224
+    assert size(ctypes.byref(desc(pkg)), 0) == 240 and size(ctypes.byref(desc(pkg, topk=0)), 3) == 0
+    assert size(None, 3) == 0 and size(ctypes.byref(desc(pkg)), -1) == 0
+    assert call(desc(pkg), ws=None) == -3 and call(desc(pkg), ws_bytes=240 + 2 * 224 - 1) == -3
+    assert b'workspace' in lib.dfm_last_error()
+    assert call(desc(pkg), ws=odd) == -1 and b'aligned' in lib.dfm_last_error()
+
+
+def test_cpu_tensors_are_refused(pkg):
+    boxes = torch.zeros(4, 4)
+    gt = torch.zeros(2, 6)
+    cfg = dict(topk=9, num_classes=3)
+    for call in (lambda: pkg.bbox_overlaps(boxes, boxes),
+                 lambda: pkg.BboxOverlaps2D()(boxes, boxes, 'iof', True),
+                 lambda: pkg.atss_target_2d(boxes, [4], [gt], [torch.zeros(2, dtype=torch.int64)], **cfg)):
+        with pytest.raises(RuntimeError, match='no CPU path'):
+            call()
+
+
+def test_patch_reference_rebinds_a_stub_liga_atss_head_module(pkg):
+    """LIGAATSSHead.get_targets is rebound where its module is already imported, and never imported for it; the
+    inherited method is kept for the fallback policy; bbox_overlaps is rebound nowhere"""
+    name = 'mmdet3d.models.dense_heads.liga_atss_head'
+    chain = ('mmdet3d', 'mmdet3d.models', 'mmdet3d.models.dense_heads', name)
+    before = {k: sys.modules.get(k) for k in chain}
+    integ = importlib.import_module('depth-from-motion_amd.integration')
+    at = importlib.import_module('depth-from-motion_amd.atss_target')
+    kept = dict(at._REFERENCE)
+    try:
+        for k in chain:
+            sys.modules.pop(k, None)
+        assert integ._patch_atss_target() == [] and name not in sys.modules
+        for k in chain:
+            m = types.ModuleType(k)
+            m.__path__ = []
+            sys.modules[k] = m
+
+        class ATSSHead(object):
+            def get_targets(self, *args):
+                return 'reference', args
+
+        class LIGAATSSHead(ATSSHead):
+            pass
+        original = ATSSHead.__dict__['get_targets']
+        sys.modules[name].LIGAATSSHead = LIGAATSSHead
+        sys.modules[name].bbox_overlaps = mmdet_overlaps = lambda *a, **k: None
+        assert integ._patch_atss_target() == ['LIGAATSSHead.get_targets']  # what patch_reference adds to its report
+        assert LIGAATSSHead.__dict__['get_targets'] is pkg.HipATSSTargetMixin.__dict__['get_targets']
+        assert ATSSHead.__dict__['get_targets'] is original and at._REFERENCE['get_targets'] is original
+        assert sys.modules[name].bbox_overlaps is mmdet_overlaps
+        assert integ._patch_atss_target() == ['LIGAATSSHead.get_targets'] and \
+            at._REFERENCE['get_targets'] is original                                                      # twice
+        # a configuration the kernels do not cover goes to the kept method under 'warn' and is an error under 'raise'
+        head = LIGAATSSHead()
+        head.assigner = type('ATSS3DCenterAssigner', (), dict(thresh_mode='ratio'))()
+        args = ([[torch.zeros(4, 4)]], [[torch.ones(4, dtype=torch.bool)]], [torch.zeros(0, 6)], [dict()], None, None,
+                1, True)
+        with pytest.warns(RuntimeWarning, match='ratio'):
+            assert head.get_targets(*args) == ('reference', args)
+        head.fallback_policy = 'raise'
+        with pytest.raises(pkg.MfmaPathError, match='ratio'):
+            head.get_targets(*args)
+    finally:
+        at._REFERENCE.clear()
+        at._REFERENCE.update(kept)
+        at._WARNED.clear()
+        for k, v in before.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
