@@ -31,6 +31,8 @@ from .anchor_target import (BboxOverlapsNearest3D, HipAnchorTrainMixin, anchor_t
 from .bbox_decode import (HipAnchor3DHeadMixin, anchor3d_get_bboxes, anchor_head_candidates,  # noqa: F401
                           delta_xyzwlhr_decode)
 from .atss_target import BboxOverlaps2D, HipATSSTargetMixin, atss_target_2d, bbox_overlaps  # noqa: F401
+from .deform_conv import (ModulatedDeformConv2d, ModulatedDeformConv2dPack, deform_sample,  # noqa: F401
+                          modulated_deform_conv2d)
 from .data_geometry import (fold_ref_frame_matrices, select_ref_frames, stage_geometry,  # noqa: F401
                             video_cur2prevs)
 from .point_sample import (mv_feature_transformation, point_sample, voxel_centers,  # noqa: F401
@@ -48,4 +50,5 @@ __all__ = ['build_dfm_cost', 'plane_sweep_grid', 'point_sample', 'mv_feature_tra
            'IOU3DLoss', 'iou3d_loss_from_deltas', 'bbox_overlaps_nearest_3d', 'BboxOverlapsNearest3D',
            'anchor_target_3d', 'HipAnchorTrainMixin', 'delta_xyzwlhr_decode', 'anchor_head_candidates',
            'anchor3d_get_bboxes', 'HipAnchor3DHeadMixin', 'bbox_overlaps', 'BboxOverlaps2D', 'atss_target_2d',
-           'HipATSSTargetMixin']
+           'HipATSSTargetMixin', 'deform_sample', 'modulated_deform_conv2d', 'ModulatedDeformConv2d',
+           'ModulatedDeformConv2dPack']

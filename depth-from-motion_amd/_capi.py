@@ -190,6 +190,14 @@ class AtssTargetDesc(ctypes.Structure):
                                            ('target_means', ctypes.c_float * 4), ('target_stds', ctypes.c_float * 4)]
 
 
+class DeformDesc(ctypes.Structure):
+    """struct dfm_deform_desc"""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        'n', 'cin', 'h', 'w', 'ho', 'wo', 'stride_h', 'stride_w', 'pad_h', 'pad_w', 'dil_h', 'dil_w', 'deform_groups',
+        'mask_is_logit', 'dtype', 'om_dtype')] + [('offset_stride', ctypes.c_int64 * 4),
+                                                  ('mask_stride', ctypes.c_int64 * 4)]
+
+
 DFM_ERR_UNSUPPORTED = -2  # include/dfm_hip.h
 BOX_NMS_MAX_N = 16384  # DFM_BOX_NMS_MAX_N
 
@@ -374,6 +382,21 @@ ATSS_TARGET_SIGNATURES = _atss_target_signatures()
 ATSS_TARGET_EXPORTS = tuple(ATSS_TARGET_SIGNATURES)
 
 
+def _deform_conv_signatures():
+    """the same for include/dfm_hip_deform_conv.h: the columns of the modulated deformable convolution and their
+    backward (tests/test_deform_conv.py checks this table against that header and the built library)"""
+    vp = fp = ctypes.c_void_p
+    ci, ddp, i64p = ctypes.c_int, ctypes.POINTER(DeformDesc), ctypes.POINTER(ctypes.c_int64)
+    return {
+        'dfm_deform_sample_fwd': (ci, [ddp, vp, vp, vp, vp, vp]),
+        'dfm_deform_conv_bwd_cols': (ci, [ddp, vp, vp, vp, vp, fp, i64p, fp, i64p, fp, vp]),
+    }
+
+
+DEFORM_CONV_SIGNATURES = _deform_conv_signatures()
+DEFORM_CONV_EXPORTS = tuple(DEFORM_CONV_SIGNATURES)
+
+
 _lib = None
 
 
@@ -389,7 +412,7 @@ def lib():
             '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
     h = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in (*SIGNATURES.items(), *BBOX_DECODE_SIGNATURES.items(),
-                                      *ATSS_TARGET_SIGNATURES.items()):
+                                      *ATSS_TARGET_SIGNATURES.items(), *DEFORM_CONV_SIGNATURES.items()):
         fn = getattr(h, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = h

@@ -17,7 +17,9 @@ Three ways to use this package from there, all routed to the HIP kernels:
    imported), replaces ``MultiViewDfM.feature_transformation`` by
    ``MultiViewDfMMixin.feature_transformation`` and, where ``train_mixins`` is already imported,
    ``AnchorTrainMixin.anchor_target_3d`` by ``HipAnchorTrainMixin.anchor_target_3d`` and, where ``anchor3d_head`` is,
-   ``Anchor3DHead.get_bboxes`` by ``HipAnchor3DHeadMixin.get_bboxes``.
+   ``Anchor3DHead.get_bboxes`` by ``HipAnchor3DHeadMixin.get_bboxes``.  Where ``mmcv.ops`` is already imported its
+   ``modulated_deform_conv2d`` is rebound and ``ModulatedDeformConv2dPack`` registered as ``'DCNv2'`` in mmcv's
+   ``CONV_LAYERS``.
 2. ``DfMStereoPath`` -- the KITTI student's path (neck -> backbone_stereo -> depth_head ->
    feature_transformation -> height compression -> backbone_3d) built from the ``model`` dict of
    ``configs/dfm/dfm_r34_1x8_kitti-3d-3class.py`` with the detector's attribute injection;
@@ -41,6 +43,8 @@ from . import bbox_decode as _bbox_decode
 from .bbox_decode import HipAnchor3DHeadMixin
 from . import atss_target as _atss_target
 from .atss_target import HipATSSTargetMixin
+from . import deform_conv as _deform_conv
+from .deform_conv import ModulatedDeformConv2dPack, modulated_deform_conv2d
 from .geometry import prepare_coordinates_3d, prepare_depth
 from .conv3d import MfmaConv3dTo1
 from .graphs import GraphedCallable
@@ -456,6 +460,39 @@ def _patch_atss_target():
     return methods
 
 
+# the backbone's deformable convolutions (the Waymo configs' ResNet-101 with dcn=dict(type='DCNv2')): mmcv's function
+# is rebound in the modules that hold it by name, and the Pack is registered as 'DCNv2' in mmcv's CONV_LAYERS, which
+# is where mmdet's ResNet builds its dcn layers from.  The replaced function and class are kept for the fallback
+# policy.  Only where those modules are already imported, as above: this package never imports mmcv.
+_DEFORM_MODULES = ('mmcv.ops.modulated_deform_conv', 'mmcv.ops')
+_CONV_LAYER_MODULES = ('mmcv.cnn.bricks.registry', 'mmcv.cnn.bricks', 'mmcv.cnn')
+
+
+def _patch_deform_conv():
+    """-> (functions rebound, conv layers registered)"""
+    functions, layers = [], []
+    for mod_name in _DEFORM_MODULES:
+        mod = sys.modules.get(mod_name)
+        current = getattr(mod, 'modulated_deform_conv2d', None) if mod is not None else None
+        if current is not None:
+            if current is not modulated_deform_conv2d:
+                _deform_conv._REFERENCE.setdefault('modulated_deform_conv2d', current)
+                mod.modulated_deform_conv2d = modulated_deform_conv2d
+            functions.append(f'{mod_name}.modulated_deform_conv2d')
+    for mod_name in _CONV_LAYER_MODULES:
+        mod = sys.modules.get(mod_name)
+        reg = getattr(mod, 'CONV_LAYERS', None) if mod is not None else None
+        if reg is not None:
+            previous = reg.get('DCNv2')
+            if previous is not ModulatedDeformConv2dPack:
+                if previous is not None:
+                    _deform_conv._REFERENCE.setdefault('DCNv2', previous)
+                reg.register_module(name='DCNv2', force=True, module=ModulatedDeformConv2dPack)
+            layers.append('DCNv2 (mmcv CONV_LAYERS)')
+            break   # the three modules hold the same registry object
+    return functions, layers
+
+
 def patch_reference(precision=None, strict=False):
     """Route a real mmdet3d (the reference fork) to the HIP path.  Call once after
     ``import mmdet3d`` and before building the model from ``configs/dfm/*``.  Returns a report
@@ -485,6 +522,9 @@ def patch_reference(precision=None, strict=False):
     report['methods'] += methods
     report['methods'] += _patch_anchor_head()
     report['methods'] += _patch_atss_target()
+    functions, layers = _patch_deform_conv()
+    report['functions'] += functions
+    report['modules'] += layers
     try:
         det = importlib.import_module('mmdet3d.models.detectors.multiview_dfm')
         det.MultiViewDfM.feature_transformation = MultiViewDfMMixin.feature_transformation

@@ -1372,6 +1372,9 @@ DFM_API int dfm_spp_tail_fwd(const dfm_spp_desc *desc, const void *const *pooled
  * dfm_atss_target_workspace_bytes): likewise */
 #include "dfm_hip_atss_target.h"
 
+/* modulated deformable convolution, DCNv2 (dfm_deform_sample_fwd, dfm_deform_conv_bwd_cols): likewise */
+#include "dfm_hip_deform_conv.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,428 @@
+"""CPU: the deformable-convolution feature above the kernels -- the fixture against its generator's stand-in and against
+results worked out without it (half a plain convolution, the right-hand difference, zero rows at non-finite offsets),
+the exported names, the modules' parameters, state-dict keys and the ``_version`` rename, the new header against its
+binding table and the library, argument checks that need no device, the refusal of CPU tensors and the rebinding of
+stub ``mmcv.ops`` modules.
+
+Fixture (tests/golden/deform_conv.npz, generator tests/golden/make_golden_deform_conv.py): the inputs of every case,
+the SHA-256 of the stand-in's fp32 columns and the fp32-vs-fp64 error figures; tests/deform_conv_ref.py runs the
+stand-in on the stored inputs once per process."""
+import ctypes
+import importlib
+import os
+import re
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import deform_conv_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ('dfm_deform_sample_fwd', 'dfm_deform_conv_bwd_cols')
+NAMES = ('deform_sample', 'modulated_deform_conv2d', 'ModulatedDeformConv2d', 'ModulatedDeformConv2dPack')
+
+
+@pytest.fixture(scope='module')
+def pkg():
+    importlib.import_module('depth-from-motion_amd.build').build_hip()
+    return importlib.import_module('depth-from-motion_amd')
+
+
+def test_the_case_table_is_stored_whole():
+    z = ref.fixture()
+    want = {'one_chunk': (1, 32, 32, 5, 7, 1), 'chunks': (2, 64, 96, 9, 13, 1), 'stride2': (2, 64, 64, 9, 13, 2),
+            'dil2': (1, 32, 32, 9, 9, 1), 'zero_offset': (1, 32, 64, 6, 6, 1), 'zero_offset_s2': (1, 32, 64, 6, 6, 2),
+            'far': (1, 32, 32, 6, 8, 1), 'special': (1, 32, 32, 5, 5, 1), 'bias_raw': (1, 32, 32, 5, 7, 1),
+            'g2': (1, 64, 32, 5, 7, 1)}
+    assert set(ref.case_names()) == set(want)
+    for case, shape in want.items():
+        g = ref.geometry(case)
+        assert (g['n'], g['cin'], g['cout'], g['h'], g['w'], g['stride']) == shape, case
+        i = ref.inputs(case)
+        assert tuple(i['x'].shape) == shape[:2] + shape[3:5] and tuple(i['weight'].shape) == (shape[2], shape[1], 3, 3)
+        assert ('raw' in i) == g['raw'] and ('bias' in i) == g['bias'] and ('offset' in i) != g['raw']
+        # every x, weight and grad_out is exactly a bfloat16: one set of columns serves both kernels
+        for k in ('x', 'weight', 'grad_out'):
+            assert torch.equal(i[k], i[k].to(torch.bfloat16).float()), (case, k)
+        err = z[f'{case}.err']
+        assert err.shape == (5,) and np.all(err >= 2.0 ** -23) and np.all(err < 2e-6), (case, err)
+    assert ref.geometry('dil2')['dilation'] == 2 and ref.geometry('dil2')['padding'] == 2
+    assert ref.geometry('g2')['groups'] == 2
+    assert os.path.getsize(os.path.join(ROOT, 'tests', 'golden', 'deform_conv.npz')) <= 1 << 20
+
+
+@pytest.mark.parametrize('case', ['one_chunk', 'chunks', 'stride2', 'dil2', 'zero_offset', 'zero_offset_s2', 'far',
+                                  'special', 'bias_raw', 'g2'])
+def test_recomputed_columns_are_the_generators(case):
+    """the fp32 columns the GPU tests compare with hash to what the generator stored"""
+    r32, _ = ref.reference(case)
+    assert ref.generator().columns_digest(r32['col']) == str(ref.fixture()[f'{case}.col_sha256'])
+    g = ref.geometry(case)
+    ho, wo = ref.generator().out_size(g['h'], g['w'], g['stride'], g['padding'], g['dilation'])
+    assert tuple(r32['col'].shape) == (g['n'], ho, wo, 9, g['cin'])
+
+
+def test_general_position_cases_keep_their_guard():
+    gen = ref.generator()
+    for case in gen.GENERAL + ('special',):
+        g, i = ref.geometry(case), ref.inputs(case)
+        offset = i['raw'][:, :18 * g['groups']] if g['raw'] else i['offset']
+        for c in gen.coordinates(case, offset):
+            c = c[torch.isfinite(c) & (c.abs() < 1e20)].double()
+            assert ((c - c.round()).abs() >= gen.GUARD * 0.999).all(), case
+
+
+@pytest.mark.parametrize('case', ['zero_offset', 'zero_offset_s2'])
+def test_zero_offset_is_half_a_plain_convolution(case):
+    g, i = ref.geometry(case), ref.inputs(case)
+    assert not i['raw'].any()
+    _, r64 = ref.reference(case)
+    want = 0.5 * F.conv2d(i['x'].double(), i['weight'].double(), stride=g['stride'], padding=1)
+    assert torch.allclose(r64['out'], want, rtol=0, atol=1e-13)
+    assert np.allclose(ref.fixture()[f'{case}.out'], r64['out'].numpy(), rtol=0, atol=1e-12)   # (fp64 sums reorder)
+    # the fp32 columns are exactly half the unfolded input: sigmoid(0) = 0.5 and every weight is 0 or 1
+    r32, _ = ref.reference(case)
+    unf = F.unfold(i['x'], 3, padding=1, stride=g['stride'])               # (1, Cin * 9, P), channel-major
+    ho, wo = r32['col'].shape[1:3]
+    unf = unf.view(1, g['cin'], 9, ho, wo).permute(0, 3, 4, 2, 1)
+    assert torch.equal(r32['col'], 0.5 * unf)
+
+
+@pytest.mark.parametrize('case', ['zero_offset', 'zero_offset_s2'])
+def test_zero_offset_pins_the_right_hand_derivative(case):
+    """at an integer coordinate d val / d h = v[h0 + 1] - v[h0] (a corner outside the map 0), and a tap sitting
+    exactly on row or column -1 is outside: gradient 0.  Worked out here with shifted copies of the padded input."""
+    g, i = ref.geometry(case), ref.inputs(case)
+    _, r64 = ref.reference(case)
+    x, wgt, go = i['x'].double(), i['weight'].double(), i['grad_out'].double()
+    s, (h, w) = g['stride'], x.shape[2:]
+    ho, wo = go.shape[2:]
+    xp = F.pad(x, (2, 2, 2, 2))                                              # xp[r + 2, c + 2] = x[r, c]
+    want = torch.zeros(1, 18, ho, wo, dtype=torch.float64)
+    for k in range(9):
+        ti, tj = k // 3, k % 3
+        gcol = torch.einsum('nohw,oc->nchw', go, wgt[:, :, ti, tj])          # d loss / d col[k]
+        for oy in range(ho):
+            for ox in range(wo):
+                r, c = oy * s - 1 + ti, ox * s - 1 + tj
+                if r < 0 or c < 0:                                           # exactly -1: not inside
+                    continue
+                v = xp[0, :, r + 2:r + 4, c + 2:c + 4]                       # (Cin, 2, 2): v00 v01 / v10 v11
+                want[0, 2 * k, oy, ox] = 0.5 * (gcol[0, :, oy, ox] * (v[:, 1, 0] - v[:, 0, 0])).sum()
+                want[0, 2 * k + 1, oy, ox] = 0.5 * (gcol[0, :, oy, ox] * (v[:, 0, 1] - v[:, 0, 0])).sum()
+    assert torch.allclose(r64['grad_offset'], want, rtol=0, atol=1e-12)
+    assert np.allclose(ref.fixture()[f'{case}.grad_offset'], r64['grad_offset'].numpy(), rtol=0, atol=1e-12)
+    assert (want != 0).sum() > want.numel() // 2
+
+
+def test_special_offsets_give_zero_rows_and_zero_gradients():
+    i = ref.inputs('special')
+    r32, r64 = ref.reference('special')
+    off = i['offset'].view(1, 9, 2, 5, 5)
+    bad = ~(torch.isfinite(off) & (off.abs() < 1e20)).all(dim=2)              # (1, 9, Ho, Wo)
+    assert int(bad.sum()) == 9
+    assert torch.isnan(off).any() and torch.isinf(off).any() and (off.abs() == 1e30).any()
+    rows = bad.permute(0, 2, 3, 1)                                            # (1, Ho, Wo, 9)
+    for r in (r32, r64):
+        assert not r['col'][rows].any() and torch.isfinite(r['col']).all() and r['col'][~rows].any()
+        assert not r['grad_offset'].view(1, 9, 2, 5, 5).permute(0, 1, 3, 4, 2)[bad].any()
+        assert not r['grad_mask'][bad].any() and r['grad_mask'][~bad].any()
+        for q in ('out', 'grad_x', 'grad_weight', 'grad_offset', 'grad_mask'):
+            assert torch.isfinite(r[q]).all(), q
+    assert np.allclose(ref.fixture()['special.out'], r64['out'].numpy(), rtol=0, atol=1e-12)   # (fp64 sums reorder)
+
+
+def test_far_case_reaches_every_band():
+    gen = ref.generator()
+    i = ref.inputs('far')
+    hc, wc = gen.coordinates('far', i['offset'])
+    h, w = 6, 8
+    inside = (hc > -1) & (wc > -1) & (hc < h) & (wc < w)
+    assert 0.1 < inside.float().mean() < 0.5                                 # most samples outside, many inside
+    assert ((hc > -1) & (hc < 0) & inside).any() and ((hc > h - 1) & (hc < h) & inside).any()
+    assert ((wc > -1) & (wc < 0) & inside).any() and ((wc > w - 1) & (wc < w) & inside).any()
+    assert (hc == -1).any() and (hc == h).any() and (wc == w).any() and (wc == -1).any()
+    assert ((hc == h - 1) & (wc == w - 1)).any() and ((hc == 0) & (wc == 0)).any()
+    assert i['offset'].abs().max() > h + 2
+
+
+def test_names_are_exported(pkg):
+    for name in NAMES:
+        assert name in pkg.__all__ and hasattr(pkg, name), name
+    dc = importlib.import_module('depth-from-motion_amd.deform_conv')
+    assert pkg.modulated_deform_conv2d is dc.modulated_deform_conv2d
+    import inspect
+    assert list(inspect.signature(dc.modulated_deform_conv2d).parameters) == [
+        'input', 'offset', 'mask', 'weight', 'bias', 'stride', 'padding', 'dilation', 'groups', 'deform_groups']
+
+
+def test_modules_parameters_and_state_dict_keys(pkg):
+    torch.manual_seed(0)
+    m = pkg.ModulatedDeformConv2d(8, 16, 3, stride=2, padding=1, deform_groups=2)
+    assert list(m.state_dict()) == ['weight', 'bias'] and tuple(m.weight.shape) == (16, 8, 3, 3)
+    assert not m.bias.any() and m.weight.abs().max() <= 1 / (8 * 9) ** 0.5 and m.weight.std() > 0
+    assert (m.stride, m.padding, m.dilation, m.kernel_size) == ((2, 2), (1, 1), (1, 1), (3, 3))
+    assert list(pkg.ModulatedDeformConv2d(8, 16, 3, bias=False).state_dict()) == ['weight']
+    p = pkg.ModulatedDeformConv2dPack(8, 16, 3, stride=2, padding=1, dilation=1, deform_groups=2)
+    assert list(p.state_dict()) == ['weight', 'bias', 'conv_offset.weight', 'conv_offset.bias']
+    co = p.conv_offset
+    assert type(co) is torch.nn.Conv2d and tuple(co.weight.shape) == (54, 8, 3, 3) and co.bias is not None
+    assert (co.stride, co.padding, co.dilation) == ((2, 2), (1, 1), (1, 1))
+    assert not co.weight.any() and not co.bias.any()                          # zero-initialised
+    assert pkg.ModulatedDeformConv2dPack._version == 2 and pkg.ModulatedDeformConv2d._version == 2
+    with pytest.raises(ValueError, match='deform_groups'):
+        pkg.ModulatedDeformConv2d(8, 16, 3, deform_groups=3)
+    assert 'deform_groups=2' in repr(p)
+
+
+def load_whole_dict(module, state_dict):
+    """a checkpoint loader that hands EVERY module the whole state dict with its prefix, as mmcv's load_state_dict
+    (mmcv/runner/checkpoint.py) does -- torch's own loader filters the dict by prefix before a module sees it, so a
+    key outside the module's prefix (``conv2_offset.weight`` for the module ``conv2``) never reaches its hook"""
+    metadata = getattr(state_dict, '_metadata', None)
+    state_dict = dict(state_dict)                        # the hook renames in place: keep the caller's dict
+    missing, unexpected, errors = [], [], []
+
+    def load(mod, prefix=''):
+        local = {} if metadata is None else metadata.get(prefix[:-1], {})
+        mod._load_from_state_dict(state_dict, prefix, local, True, missing, unexpected, errors)
+        for name, child in mod._modules.items():
+            if child is not None:
+                load(child, prefix + name + '.')
+
+    load(module)
+    return missing, unexpected, errors
+
+
+def test_version_1_checkpoints_are_renamed_on_load(pkg):
+    class Block(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.conv2 = pkg.ModulatedDeformConv2dPack(8, 8, 3, padding=1)
+
+    src, dst = Block(), Block()
+    with torch.no_grad():
+        src.conv2.conv_offset.weight.normal_()
+        src.conv2.conv_offset.bias.normal_()
+    sd = src.state_dict()
+    assert sd._metadata['conv2']['version'] == 2
+    old = {k.replace('conv2.conv_offset.', 'conv2_offset.'): v for k, v in sd.items()}
+    assert 'conv2_offset.weight' in old and 'conv2.conv_offset.weight' not in old   # no version: an early file
+    missing, unexpected, errors = load_whole_dict(dst, old)
+    assert not missing and not errors
+    assert torch.equal(dst.conv2.conv_offset.weight, src.conv2.conv_offset.weight)
+    assert torch.equal(dst.conv2.conv_offset.bias, src.conv2.conv_offset.bias)
+    assert torch.equal(dst.conv2.weight, src.conv2.weight)
+    # a file that says version 2 is taken at its word: old names are NOT renamed
+    dst2 = Block()
+    versioned = type(sd)(old)
+    versioned._metadata = sd._metadata
+    missing, _, _ = load_whole_dict(dst2, versioned)
+    assert sorted(missing) == ['conv2.conv_offset.bias', 'conv2.conv_offset.weight']
+    assert not dst2.conv2.conv_offset.weight.any()
+    # and a current state dict loads through torch's own loader as it is
+    dst3 = Block()
+    dst3.load_state_dict(sd, strict=True)
+    assert torch.equal(dst3.conv2.conv_offset.weight, src.conv2.conv_offset.weight)
+
+
+def test_header_binding_and_library_agree_on_the_new_symbols(pkg):
+    main = open(os.path.join(ROOT, 'include', 'dfm_hip.h')).read()
+    assert '#include "dfm_hip_deform_conv.h"' in main
+    text = open(os.path.join(ROOT, 'include', 'dfm_hip_deform_conv.h')).read()
+    code = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    decls = {}
+    for m in re.finditer(r'^DFM_API\s+([\w\s\*]+?)\b(dfm_\w+)\s*\(([^)]*)\)\s*;', code, flags=re.M):
+        decls[m.group(2)] = (' '.join(m.group(1).split()), m.group(3).count(',') + 1)
+    capi = pkg._capi
+    assert sorted(decls) == sorted(NEW) == sorted(capi.DEFORM_CONV_SIGNATURES)
+    assert capi.DEFORM_CONV_EXPORTS == tuple(capi.DEFORM_CONV_SIGNATURES)
+    assert not set(NEW) & (set(capi.EXPORTS) | set(capi.BBOX_DECODE_EXPORTS) | set(capi.ATSS_TARGET_EXPORTS))
+    h, lib = ctypes.CDLL(capi.LIB_PATH), capi.lib()
+    for name, (ret, nparams) in decls.items():
+        restype, argtypes = capi.DEFORM_CONV_SIGNATURES[name]
+        assert ret == 'int' and restype is ctypes.c_int and len(argtypes) == nparams, name
+        assert hasattr(h, name), f'{name} not exported by the library'
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    for phrase in ('tap k = 3 i + j', 'h > -1 && w > -1 && h < H && w < W', 'after the test only',
+                   'a corner outside the map is 0', '(((hh * hw) * v00 + (hh * lw) * v01) + (lh * hw) * v10) + (lh * lw) * v11',
+                   'right-hand difference', 'no atomics', 'rounded once'):
+        assert phrase in text, phrase                                         # the semantics are stated in the header
+    # the descriptor's size follows the header: 16 ints, 2 x 4 64-bit strides
+    assert ctypes.sizeof(capi.DeformDesc) == 4 * 16 + 8 * 8
+
+
+def desc(pkg, **kw):
+    d = pkg._capi.DeformDesc(n=1, cin=32, h=5, w=7, ho=5, wo=7, stride_h=1, stride_w=1, pad_h=1, pad_w=1, dil_h=1,
+                             dil_w=1, deform_groups=1, dtype=0, om_dtype=0)
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return ctypes.byref(d)
+
+
+def test_bad_arguments_are_rejected_without_touching_the_gpu(pkg):
+    lib = pkg._capi.lib()
+    buf = ctypes.create_string_buffer(4096 + 16)
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)      # 16-byte aligned host memory, never dereferenced
+    odd = ctypes.c_void_p(p.value + 4)
+    unsupported = pkg._capi.DFM_ERR_UNSUPPORTED
+    fwd, bwd = lib.dfm_deform_sample_fwd, lib.dfm_deform_conv_bwd_cols
+    strides = (ctypes.c_int64 * 4)(1, 1, 1, 1)
+    assert fwd(None, p, p, p, p, None) == -1 and b'NULL descriptor' in lib.dfm_last_error()
+    for bad, word in ((dict(n=0), b'size'), (dict(stride_h=0), b'stride'), (dict(dil_w=0), b'dilation'),
+                      (dict(pad_h=-1), b'padding'), (dict(deform_groups=3), b'deform_groups'),
+                      (dict(ho=4), b'output size'), (dict(wo=8), b'output size'),
+                      (dict(h=2, w=2, ho=1, wo=1, pad_h=0, pad_w=0, dil_h=2, dil_w=2), b'output size')):
+        assert fwd(desc(pkg, **bad), p, p, p, p, None) == -1 and word in lib.dfm_last_error(), bad
+        assert bwd(desc(pkg, **bad), p, p, p, p, p, strides, p, strides, p, None) == -1, bad
+    for bad, word in ((dict(dtype=2), b'dtype'), (dict(om_dtype=5), b'dtype'), (dict(cin=30), b'16-byte'),
+                      (dict(cin=36, dtype=1), b'16-byte'), (dict(cin=32, deform_groups=16), b'16-byte'),
+                      (dict(n=1 << 20, h=64, w=64, ho=64, wo=64), b'2^31'),
+                      (dict(stride_h=1 << 25, ho=1), b'2^24')):
+        assert fwd(desc(pkg, **bad), p, p, p, p, None) == unsupported and word in lib.dfm_last_error(), bad
+    assert fwd(desc(pkg), None, p, p, p, None) == -1 and b'NULL' in lib.dfm_last_error()
+    assert fwd(desc(pkg), p, p, p, None, None) == -1
+    assert fwd(desc(pkg), odd, p, p, p, None) == -1 and b'aligned' in lib.dfm_last_error()
+    assert fwd(desc(pkg), p, p, p, odd, None) == -1
+    assert bwd(desc(pkg), p, p, p, None, p, strides, p, strides, p, None) == -1 and b'NULL' in lib.dfm_last_error()
+    assert bwd(desc(pkg), p, p, p, p, p, strides, None, strides, p, None) == -1 and b'together' in lib.dfm_last_error()
+    assert bwd(desc(pkg), p, p, p, p, p, None, p, strides, p, None) == -1 and b'stride' in lib.dfm_last_error()
+    assert bwd(desc(pkg), p, p, p, p, None, None, None, None, None, None) == 0     # nothing asked for: a valid no-op
+
+
+def test_python_argument_validation_needs_no_device(pkg):
+    dc = importlib.import_module('depth-from-motion_amd.deform_conv')
+    assert dc.deform_conv_out_size((9, 13), 2, 1, 1) == (5, 7) and dc.deform_conv_out_size((9, 9), 1, 2, 2) == (9, 9)
+    with pytest.raises(ValueError, match='deform_groups'):
+        dc._check_geometry((1, 32, 5, 7), 1, 1, 1, 3)
+    with pytest.raises(ValueError, match='smaller'):
+        dc._check_geometry((1, 32, 2, 2), 1, 0, 2, 1)
+    with pytest.raises(ValueError, match='stride'):
+        dc._check_geometry((1, 32, 5, 7), 0, 1, 1, 1)
+    with pytest.raises(ValueError, match=r'\(N, Cin, H, W\)'):
+        dc._check_geometry((32, 5, 7), 1, 1, 1, 1)
+    z = torch.zeros
+    with pytest.raises(ValueError, match='offset is'):
+        dc._check_maps((1, 32, 5, 7), (5, 7), z(1, 9, 5, 7), z(1, 9, 5, 7), 1)
+    with pytest.raises(ValueError, match='mask is'):
+        dc._check_maps((1, 32, 5, 7), (5, 7), z(1, 18, 5, 7), z(1, 18, 5, 7), 1)
+    with pytest.raises(ValueError, match='27 G'):
+        dc._check_maps((1, 32, 5, 7), (5, 7), z(1, 18, 5, 7), None, 1)
+    dc._check_maps((1, 32, 5, 7), (5, 7), z(1, 36, 5, 7), z(1, 18, 5, 7), 2)
+    assert dc._unsupported((8, 8, 3, 3), 1) is None
+    assert 'kernel_size' in dc._unsupported((8, 8, 1, 1), 1) and 'groups=2' in dc._unsupported((8, 4, 3, 3), 2)
+    w2 = dc.weight_matrix(torch.arange(2 * 3 * 9.).view(2, 3, 3, 3))
+    assert tuple(w2.shape) == (2, 27) and w2[1, 3 * 4 + 2] == 27 + 2 * 9 + 4          # [co][k][ci] = W[co][ci][k]
+
+
+def test_cpu_tensors_are_refused(pkg):
+    x = torch.zeros(1, 32, 5, 7)
+    with pytest.raises(RuntimeError, match='no CPU path'):
+        pkg.deform_sample(x, torch.zeros(1, 18, 5, 7), torch.zeros(1, 9, 5, 7), padding=1)
+    with pytest.raises(RuntimeError, match='no CPU path'):
+        pkg.modulated_deform_conv2d(x, torch.zeros(1, 18, 5, 7), torch.zeros(1, 9, 5, 7), torch.zeros(8, 32, 3, 3),
+                                    padding=1)
+    with pytest.raises(RuntimeError, match='no CPU path'):
+        pkg.ModulatedDeformConv2dPack(32, 8, 3, padding=1)(x)
+
+
+def test_unsupported_settings_follow_the_fallback_policy(pkg):
+    dc = importlib.import_module('depth-from-motion_amd.deform_conv')
+    x, off, msk = torch.zeros(1, 8, 5, 5), torch.zeros(1, 18, 5, 5), torch.zeros(1, 9, 5, 5)
+    kept = dict(dc._REFERENCE)
+    dc._REFERENCE.clear()
+    try:
+        with pytest.raises(pkg.MfmaPathError, match='groups=2.*no mmcv op'):
+            pkg.modulated_deform_conv2d(x, off, msk, torch.zeros(8, 4, 3, 3), padding=1, groups=2)
+        m = pkg.ModulatedDeformConv2dPack(8, 8, 1)
+        with pytest.raises(pkg.MfmaPathError, match='kernel_size'):
+            m(x)
+        calls = []
+        dc._REFERENCE['modulated_deform_conv2d'] = lambda *a: calls.append(a) or 'mmcv'
+        with pytest.warns(RuntimeWarning, match='groups=2'):
+            assert pkg.modulated_deform_conv2d(x, off, msk, torch.zeros(8, 4, 3, 3), None, 1, 1, 1, 2, 1) == 'mmcv'
+        assert calls[0][8] == 2 and calls[0][0] is x
+        m.fallback_policy = 'raise'
+        with pytest.raises(pkg.MfmaPathError, match='kernel_size'):
+            m(x)
+        m.fallback_policy = 'silent'
+        assert m(x) == 'mmcv'
+        offset, mask = calls[-1][1], calls[-1][2]                             # the Pack hands mmcv's op the chunks
+        assert tuple(offset.shape) == (1, 2, 5, 5) and tuple(mask.shape) == (1, 1, 5, 5) and (mask == 0.5).all()
+    finally:
+        dc._REFERENCE.clear()
+        dc._REFERENCE.update(kept)
+        dc._WARNED.clear()
+
+
+def test_patch_rebinds_stub_mmcv_modules_and_touches_nothing_when_absent(pkg):
+    integ = importlib.import_module('depth-from-motion_amd.integration')
+    dc = importlib.import_module('depth-from-motion_amd.deform_conv')
+    chain = ('mmcv', 'mmcv.ops', 'mmcv.ops.modulated_deform_conv', 'mmcv.cnn', 'mmcv.cnn.bricks',
+             'mmcv.cnn.bricks.registry')
+    before = {k: sys.modules.get(k) for k in chain}
+    kept = dict(dc._REFERENCE)
+    try:
+        for k in chain:
+            sys.modules.pop(k, None)
+        dc._REFERENCE.clear()
+        assert integ._patch_deform_conv() == ([], []) and not any(k in sys.modules for k in chain)
+        assert dc._REFERENCE == {}
+
+        class Registry:
+            def __init__(self):
+                self.table = {}
+
+            def get(self, key):
+                return self.table.get(key)
+
+            def register_module(self, name=None, force=False, module=None):
+                assert force or name not in self.table
+                self.table[name] = module
+
+        def mmcv_op(*args):
+            return 'mmcv'
+
+        class MmcvPack:
+            pass
+
+        reg = Registry()
+        reg.table['DCNv2'] = MmcvPack
+        reg.table['Conv2d'] = torch.nn.Conv2d
+        for k in chain:
+            sys.modules[k] = types.ModuleType(k)
+        sys.modules['mmcv.ops'].modulated_deform_conv2d = mmcv_op
+        sys.modules['mmcv.ops.modulated_deform_conv'].modulated_deform_conv2d = mmcv_op
+        sys.modules['mmcv.ops'].nms = other = object()
+        sys.modules['mmcv.cnn'].CONV_LAYERS = reg
+        sys.modules['mmcv.cnn.bricks.registry'].CONV_LAYERS = reg
+        functions, layers = integ._patch_deform_conv()
+        assert functions == ['mmcv.ops.modulated_deform_conv.modulated_deform_conv2d',
+                             'mmcv.ops.modulated_deform_conv2d']
+        assert layers == ['DCNv2 (mmcv CONV_LAYERS)']
+        assert sys.modules['mmcv.ops'].modulated_deform_conv2d is pkg.modulated_deform_conv2d
+        assert sys.modules['mmcv.ops.modulated_deform_conv'].modulated_deform_conv2d is pkg.modulated_deform_conv2d
+        assert sys.modules['mmcv.ops'].nms is other
+        assert reg.table['DCNv2'] is pkg.ModulatedDeformConv2dPack and reg.table['Conv2d'] is torch.nn.Conv2d
+        assert dc._REFERENCE == {'modulated_deform_conv2d': mmcv_op, 'DCNv2': MmcvPack}   # kept for the fallback
+        # a second call changes nothing and loses nothing
+        assert integ._patch_deform_conv() == (functions, layers)
+        assert dc._REFERENCE == {'modulated_deform_conv2d': mmcv_op, 'DCNv2': MmcvPack}
+        # the captured op is what an unsupported setting falls back to
+        x = torch.zeros(1, 8, 5, 5)
+        with pytest.warns(RuntimeWarning, match='kernel_size'):
+            assert pkg.modulated_deform_conv2d(x, x, x, torch.zeros(8, 8, 1, 1)) == 'mmcv'
+    finally:
+        for k, v in before.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
+        dc._REFERENCE.clear()
+        dc._REFERENCE.update(kept)
+        dc._WARNED.clear()
