@@ -17,8 +17,9 @@ from .depth_head import LazyDepthDistribution, depth_head_forward, depth_head_st
 from .group_norm import HipGroupNorm, group_norm  # noqa: F401
 from .geometry import prepare_coordinates_3d, prepare_depth  # noqa: F401
 from .frustum_to_voxel import frustum_to_voxel_sample  # noqa: F401
-from .integration import (DfMImitationMixin, DfMStereoPath, MultiViewDfMMixin, MultiViewVoxelPath,  # noqa: F401
-                          enable_fast_path, inject_detector_attributes, patch_reference)
+from .integration import (DfMImitationMixin, DfMLidarTeacherMixin, DfMStereoPath, LidarTeacher,  # noqa: F401
+                          MultiViewDfMMixin, MultiViewVoxelPath, enable_fast_path, inject_detector_attributes,
+                          patch_reference)
 from .conv3d import MfmaPathError, fallback_policy, set_fallback_policy, set_fp32_mode  # noqa: F401
 from .depth_head import depth_distribution_loss  # noqa: F401
 from .imitation import (ImitationLoss, NormalizeLayer, imitation_reg_layer_loss,  # noqa: F401
@@ -33,6 +34,9 @@ from .bbox_decode import (HipAnchor3DHeadMixin, anchor3d_get_bboxes, anchor_head
 from .atss_target import BboxOverlaps2D, HipATSSTargetMixin, atss_target_2d, bbox_overlaps  # noqa: F401
 from .deform_conv import (ModulatedDeformConv2d, ModulatedDeformConv2dPack, deform_sample,  # noqa: F401
                           modulated_deform_conv2d)
+from .voxelize import HardSimpleVFE, Voxelization, hard_voxelize, hard_voxelize_batch  # noqa: F401
+from .sparse_conv import (CustomSparseEncoder, SparseConv3d, SparseConvTensor, SparseSequential,  # noqa: F401
+                          SubMConv3d, make_sparse_convmodule, sparse_conv_plan)
 from .data_geometry import (fold_ref_frame_matrices, select_ref_frames, stage_geometry,  # noqa: F401
                             video_cur2prevs)
 from .point_sample import (mv_feature_transformation, point_sample, voxel_centers,  # noqa: F401
@@ -51,4 +55,6 @@ __all__ = ['build_dfm_cost', 'plane_sweep_grid', 'point_sample', 'mv_feature_tra
            'anchor_target_3d', 'HipAnchorTrainMixin', 'delta_xyzwlhr_decode', 'anchor_head_candidates',
            'anchor3d_get_bboxes', 'HipAnchor3DHeadMixin', 'bbox_overlaps', 'BboxOverlaps2D', 'atss_target_2d',
            'HipATSSTargetMixin', 'deform_sample', 'modulated_deform_conv2d', 'ModulatedDeformConv2d',
-           'ModulatedDeformConv2dPack']
+           'ModulatedDeformConv2dPack', 'hard_voxelize', 'hard_voxelize_batch', 'Voxelization', 'HardSimpleVFE',
+           'SparseConvTensor', 'SubMConv3d', 'SparseConv3d', 'SparseSequential', 'make_sparse_convmodule',
+           'CustomSparseEncoder', 'sparse_conv_plan', 'LidarTeacher', 'DfMLidarTeacherMixin']

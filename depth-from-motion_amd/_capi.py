@@ -198,6 +198,33 @@ class DeformDesc(ctypes.Structure):
                                                   ('mask_stride', ctypes.c_int64 * 4)]
 
 
+VOXEL_MAX_BATCH = 64  # DFM_VOXEL_MAX_BATCH
+
+
+class VoxelDesc(ctypes.Structure):
+    """struct dfm_voxel_desc"""
+    _fields_ = [('batch', ctypes.c_int32), ('ndim', ctypes.c_int32), ('grid', ctypes.c_int32 * 3),
+                ('max_num_points', ctypes.c_int32), ('max_voxels', ctypes.c_int32), ('lo', ctypes.c_float * 3),
+                ('vs', ctypes.c_float * 3), ('offset', ctypes.c_int64 * (VOXEL_MAX_BATCH + 1))]
+
+
+class SparseConvDesc(ctypes.Structure):
+    """struct dfm_sparse_conv_desc"""
+    _fields_ = [('batch', ctypes.c_int32), ('in_size', ctypes.c_int32 * 3), ('kernel', ctypes.c_int32 * 3),
+                ('stride', ctypes.c_int32 * 3), ('padding', ctypes.c_int32 * 3), ('subm', ctypes.c_int32)]
+
+
+class SparseConvPlan(ctypes.Structure):
+    """struct dfm_sparse_conv_plan"""
+    _fields_ = [('out_size', ctypes.c_int32 * 3), ('taps', ctypes.c_int32), ('out_rows', ctypes.c_int64),
+                ('in_capacity', ctypes.c_int64), ('out_capacity', ctypes.c_int64)]
+
+
+# DFM_SPARSE_STATUS_*: bits of the device status word of the sparse-convolution index kernels
+SPARSE_STATUS = {1: 'a hash-table probe loop ran out of slots', 2: 'two input rows share one coordinate (duplicate)',
+                 4: 'more output rows than the row bound', 8: 'a coordinate outside the grid or the batch'}
+SPARSE_MAX_TAPS = 27  # DFM_SPARSE_MAX_TAPS
+
 DFM_ERR_UNSUPPORTED = -2  # include/dfm_hip.h
 BOX_NMS_MAX_N = 16384  # DFM_BOX_NMS_MAX_N
 
@@ -397,6 +424,33 @@ DEFORM_CONV_SIGNATURES = _deform_conv_signatures()
 DEFORM_CONV_EXPORTS = tuple(DEFORM_CONV_SIGNATURES)
 
 
+def _sparse_conv_signatures():
+    """the same for include/dfm_hip_sparse_conv.h: hard voxelization and the sparse 3-D convolutions of the LiDAR
+    teacher (tests/test_lidar_teacher.py checks this table against that header and the built library)"""
+    vp = fp = ctypes.c_void_p
+    ci, i32, i64, sz = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
+    vdp, sdp, spp, s3 = (ctypes.POINTER(VoxelDesc), ctypes.POINTER(SparseConvDesc), ctypes.POINTER(SparseConvPlan),
+                         ctypes.POINTER(i32))
+    return {
+        'dfm_voxel_keys': (ci, [vdp, fp, fp, vp]),
+        'dfm_voxel_heads': (ci, [vdp, fp, fp, fp, fp, vp]),
+        'dfm_voxel_keep': (ci, [vdp, fp, fp, fp, vp]),
+        'dfm_voxel_fill': (ci, [vdp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]),
+        'dfm_sparse_conv_out_shape': (ci, [sdp, i64, spp]),
+        'dfm_sparse_conv_workspace_bytes': (sz, [sdp, i64]),
+        'dfm_sparse_index_build': (ci, [fp, i64, i32, s3, fp, fp, i64, fp, vp]),
+        'dfm_sparse_subm_neighbours': (ci, [fp, i64, i32, s3, fp, fp, i64, fp, vp]),
+        'dfm_sparse_conv_out_rows': (ci, [sdp, fp, i64, fp, fp, fp, fp, vp]),
+        'dfm_sparse_conv_neighbours': (ci, [sdp, fp, i64, fp, fp, fp, vp]),
+        'dfm_sparse_conv_fwd': (ci, [i32, i32, i32, fp, i64, fp, fp, i64, fp, fp, fp, i32, fp, vp]),
+        'dfm_sparse_dense': (ci, [fp, fp, i64, i32, i32, s3, fp, vp]),
+    }
+
+
+SPARSE_CONV_SIGNATURES = _sparse_conv_signatures()
+SPARSE_CONV_EXPORTS = tuple(SPARSE_CONV_SIGNATURES)
+
+
 _lib = None
 
 
@@ -412,7 +466,8 @@ def lib():
             '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
     h = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in (*SIGNATURES.items(), *BBOX_DECODE_SIGNATURES.items(),
-                                      *ATSS_TARGET_SIGNATURES.items(), *DEFORM_CONV_SIGNATURES.items()):
+                                      *ATSS_TARGET_SIGNATURES.items(), *DEFORM_CONV_SIGNATURES.items(),
+                                      *SPARSE_CONV_SIGNATURES.items()):
         fn = getattr(h, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = h

@@ -13,8 +13,9 @@ from which the loss and the ``NormalizeLayer`` buffer update follow by scalar / 
 (``reduce_imitation_statistics``; pure torch, runs on CPU tensors under gloo as well).  The ``(Npos, C)``
 gather exists nowhere.  The backward is one dense pass (``dfm_imitation_loss_bwd``).
 
-The LiDAR teacher itself is out of scope: its two feature tensors are inputs, as they are to the reference
-function.  The 1x1 ``conv_imitation`` layers are library GEMMs.
+The LiDAR teacher's two feature tensors are inputs, as they are to the reference function;
+``integration.LidarTeacher`` (hard voxelization and the sparse encoder on the HIP path, forward only, eval only)
+produces them from the point clouds.  The 1x1 ``conv_imitation`` layers are library GEMMs.
 """
 import ctypes
 

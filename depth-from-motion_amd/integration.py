@@ -19,7 +19,9 @@ Three ways to use this package from there, all routed to the HIP kernels:
    ``AnchorTrainMixin.anchor_target_3d`` by ``HipAnchorTrainMixin.anchor_target_3d`` and, where ``anchor3d_head`` is,
    ``Anchor3DHead.get_bboxes`` by ``HipAnchor3DHeadMixin.get_bboxes``.  Where ``mmcv.ops`` is already imported its
    ``modulated_deform_conv2d`` is rebound and ``ModulatedDeformConv2dPack`` registered as ``'DCNv2'`` in mmcv's
-   ``CONV_LAYERS``.
+   ``CONV_LAYERS``; likewise ``Voxelization``, ``SparseConvTensor``, ``SparseSequential`` and the layer types
+   ``SubMConv3d`` / ``SparseConv3d`` of the LiDAR teacher (``LidarTeacher`` below), and
+   ``DfM.extract_lidar_model_feat``.
 2. ``DfMStereoPath`` -- the KITTI student's path (neck -> backbone_stereo -> depth_head ->
    feature_transformation -> height compression -> backbone_3d) built from the ``model`` dict of
    ``configs/dfm/dfm_r34_1x8_kitti-3d-3class.py`` with the detector's attribute injection;
@@ -45,6 +47,9 @@ from . import atss_target as _atss_target
 from .atss_target import HipATSSTargetMixin
 from . import deform_conv as _deform_conv
 from .deform_conv import ModulatedDeformConv2dPack, modulated_deform_conv2d
+from . import sparse_conv as _sparse_conv
+from .sparse_conv import SparseConv3d, SparseConvTensor, SparseSequential, SubMConv3d
+from .voxelize import Voxelization
 from .geometry import prepare_coordinates_3d, prepare_depth
 from .conv3d import MfmaConv3dTo1
 from .graphs import GraphedCallable
@@ -266,8 +271,26 @@ class MultiViewDfMMixin:
         return out
 
 
-class DfMImitationMixin:
-    """``get_imitation_reg_layer_loss`` of ``DfM`` (dfm.py:468-540) on the HIP path, for a subclass of the
+class DfMLidarTeacherMixin:
+    """``extract_lidar_model_feat`` of ``DfM`` (dfm.py:373-382) on the HIP path, same signature, for a detector whose
+    ``lidar_model`` holds this package's ``voxel_layer`` / ``voxel_encoder`` / ``middle_encoder`` / ``backbone`` (a
+    ``LidarTeacher``, or the reference's VoxelNet built after ``patch_reference()``): batched voxelization with the
+    batch size taken from the list, no ``.item()``."""
+
+    @torch.no_grad()
+    def extract_lidar_model_feat(self, points):
+        lm = self.lidar_model
+        if not hasattr(lm.voxel_layer, 'forward_batch'):   # a teacher built from mmcv's classes: the reference's method
+            return _sparse_conv._REFERENCE['DfM.extract_lidar_model_feat'](self, points)
+        voxels, coors, num_points, _ = lm.voxel_layer.forward_batch(list(points))
+        voxel_features = lm.voxel_encoder(voxels, num_points, coors)
+        spatial_feat, volume_feat = lm.middle_encoder(voxel_features, coors, len(points))
+        return volume_feat, lm.backbone(spatial_feat)
+
+
+class DfMImitationMixin(DfMLidarTeacherMixin):
+    """``extract_lidar_model_feat`` (from ``DfMLidarTeacherMixin``) and ``get_imitation_reg_layer_loss`` of ``DfM``
+    (dfm.py:468-540) on the HIP path, for a subclass of the
     reference detector (``class FastDfM(DfMImitationMixin, DfM)``): one fused launch instead of
     ``points_in_boxes_part`` and the gather / normalise / reduce passes.  The host class provides
     ``bbox_head_3d.anchors``, ``norm_imitation`` and ``normalizer_clamp_value`` as the reference does; the
@@ -280,6 +303,59 @@ class DfMImitationMixin:
             features_preds, features_targets, imitation_cfg, gt_bboxes_3d, points,
             norm_layer=self.norm_imitation[imitation_cfg['stereo_feature_layer']],
             normalizer_clamp_value=self.normalizer_clamp_value, training=self.training)
+
+
+class LidarTeacher(nn.Module):
+    """The frozen LiDAR teacher of the KITTI configs from their ``lidar_model`` dict (``type='VoxelNet'``:
+    ``voxel_layer``, ``voxel_encoder=HardSimpleVFE``, ``middle_encoder=CustomSparseEncoder``,
+    ``backbone=BEVHourglass``), without mmdet3d.  Submodule names are VoxelNet's (``voxel_layer``, ``voxel_encoder``,
+    ``middle_encoder``, ``backbone``), so a teacher checkpoint's keys load as they are.
+
+    ``forward(points_list)`` -> ``(volume_feat (B, C, D, H, W), bev_feat)``, what ``DfM.extract_lidar_model_feat``
+    (dfm.py:373-382) returns: batched voxelization -> VFE -> sparse encoder -> BEV hourglass.  The batch size is the
+    length of the list (the reference reads it back from ``coors[-1, 0].item()``), row counts stay on the device:
+    NO host wait.  Forward only and always in eval mode, as the reference forces it (dfm.py:72-76, 111-116):
+    parameters are frozen and ``train()`` leaves every module in ``eval()``."""
+
+    def __init__(self, lidar_model_cfg):
+        super().__init__()
+        cfg = dict(lidar_model_cfg)
+        kind = cfg.pop('type', 'VoxelNet')
+        if kind != 'VoxelNet':
+            raise KeyError(f'LidarTeacher builds a VoxelNet teacher, got type={kind!r}')
+        for stage in ('neck', 'bbox_head'):
+            if cfg.get(stage) is not None:
+                raise NotImplementedError(f'LidarTeacher: lidar_model.{stage} is not None (the configs set it to None)')
+        self.voxel_layer = Voxelization(**cfg['voxel_layer'])
+        self.voxel_encoder = registry.build(cfg['voxel_encoder'])
+        self.middle_encoder = registry.build(cfg['middle_encoder'])
+        backbone = dict(cfg['backbone'])
+        if (backbone.get('norm_cfg') or {}).get('type') == 'SyncBN':
+            # eval only: a SyncBN is a BatchNorm2d here, under the same sub-module name ('bn') and keys
+            backbone['norm_cfg'] = dict(backbone['norm_cfg'], type='BN')
+        self.backbone = registry.build_backbone(backbone)
+        if not getattr(self.middle_encoder, 'output_volume_feat', False):
+            raise ValueError('LidarTeacher needs middle_encoder.output_volume_feat=True (the imitation loss reads the '
+                             'volume features)')
+        for param in self.parameters():
+            param.requires_grad_(False)
+        self.train(False)
+
+    def train(self, mode=True):
+        return super().train(False)   # the teacher is eval only
+
+    @torch.no_grad()
+    def forward(self, points_list):
+        if isinstance(points_list, torch.Tensor):
+            points_list = [points_list]
+        voxels, coors, num_points, _ = self.voxel_layer.forward_batch(list(points_list))
+        voxel_features = self.voxel_encoder(voxels, num_points, coors)
+        spatial_feat, volume_feat = self.middle_encoder(voxel_features, coors, len(points_list))
+        return volume_feat, self.backbone(spatial_feat)
+
+    def check_status(self):
+        """ONE host wait: raises ``DfmHipError`` when the last forward's index kernels reported a problem"""
+        self.middle_encoder.check_status()
 
 
 class MultiViewVoxelPath(MultiViewDfMMixin, nn.Module):
@@ -493,6 +569,58 @@ def _patch_deform_conv():
     return functions, layers
 
 
+# the LiDAR teacher's ops: mmcv's Voxelization and spconv wrapper classes are rebound in the modules that hold them
+# by name, the layer types registered in mmcv's CONV_LAYERS (where make_sparse_convmodule builds them from).  What was
+# there before is kept.  Only where those modules are already imported: this package never imports mmcv or mmdet3d.
+_TEACHER_CLASSES = dict(Voxelization=Voxelization, SparseConvTensor=SparseConvTensor,
+                        SparseSequential=SparseSequential, SubMConv3d=SubMConv3d, SparseConv3d=SparseConv3d)
+_TEACHER_MODULES = ('mmcv.ops', 'mmcv.ops.voxelize', 'mmcv.ops.sparse_conv', 'mmcv.ops.sparse_structure',
+                    'mmcv.ops.sparse_modules', 'mmdet3d.ops', 'mmdet3d.ops.sparse_block',
+                    'mmdet3d.models.middle_encoders.sparse_encoder', 'mmdet3d.models.detectors.voxelnet')
+
+
+def _patch_lidar_teacher():
+    """-> (names rebound, conv layers registered, methods replaced)"""
+    functions, layers, methods = [], [], []
+    for mod_name in _TEACHER_MODULES:
+        mod = sys.modules.get(mod_name)
+        if mod is None:
+            continue
+        for attr, cls in _TEACHER_CLASSES.items():
+            current = getattr(mod, attr, None)
+            if current is None:
+                continue
+            if current is not cls:
+                _sparse_conv._REFERENCE.setdefault(f'{mod_name}.{attr}', current)
+                setattr(mod, attr, cls)
+            functions.append(f'{mod_name}.{attr}')
+        if getattr(mod, 'make_sparse_convmodule', None) is not None:
+            if mod.make_sparse_convmodule is not _sparse_conv.make_sparse_convmodule:
+                _sparse_conv._REFERENCE.setdefault(f'{mod_name}.make_sparse_convmodule', mod.make_sparse_convmodule)
+                mod.make_sparse_convmodule = _sparse_conv.make_sparse_convmodule
+            functions.append(f'{mod_name}.make_sparse_convmodule')
+    for mod_name in _CONV_LAYER_MODULES:
+        mod = sys.modules.get(mod_name)
+        reg = getattr(mod, 'CONV_LAYERS', None) if mod is not None else None
+        if reg is not None:
+            for name, cls in (('SubMConv3d', SubMConv3d), ('SparseConv3d', SparseConv3d)):
+                previous = reg.get(name)
+                if previous is not cls:
+                    if previous is not None:
+                        _sparse_conv._REFERENCE.setdefault(f'CONV_LAYERS.{name}', previous)
+                    reg.register_module(name=name, force=True, module=cls)
+                layers.append(f'{name} (mmcv CONV_LAYERS)')
+            break   # the three modules hold the same registry object
+    det = sys.modules.get('mmdet3d.models.detectors.dfm')
+    cls = getattr(det, 'DfM', None) if det is not None else None
+    if cls is not None and hasattr(cls, 'extract_lidar_model_feat'):
+        if cls.extract_lidar_model_feat is not DfMLidarTeacherMixin.extract_lidar_model_feat:
+            _sparse_conv._REFERENCE.setdefault('DfM.extract_lidar_model_feat', cls.extract_lidar_model_feat)
+            cls.extract_lidar_model_feat = DfMLidarTeacherMixin.extract_lidar_model_feat
+        methods.append('DfM.extract_lidar_model_feat')
+    return functions, layers, methods
+
+
 def patch_reference(precision=None, strict=False):
     """Route a real mmdet3d (the reference fork) to the HIP path.  Call once after
     ``import mmdet3d`` and before building the model from ``configs/dfm/*``.  Returns a report
@@ -525,6 +653,10 @@ def patch_reference(precision=None, strict=False):
     functions, layers = _patch_deform_conv()
     report['functions'] += functions
     report['modules'] += layers
+    functions, layers, methods = _patch_lidar_teacher()
+    report['functions'] += functions
+    report['modules'] += layers
+    report['methods'] += methods
     try:
         det = importlib.import_module('mmdet3d.models.detectors.multiview_dfm')
         det.MultiViewDfM.feature_transformation = MultiViewDfMMixin.feature_transformation

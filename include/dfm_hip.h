@@ -1374,6 +1374,8 @@ DFM_API int dfm_spp_tail_fwd(const dfm_spp_desc *desc, const void *const *pooled
 
 /* modulated deformable convolution, DCNv2 (dfm_deform_sample_fwd, dfm_deform_conv_bwd_cols): likewise */
 #include "dfm_hip_deform_conv.h"
+/* the LiDAR teacher: hard voxelization (dfm_voxel_*) and sparse 3-D convolutions (dfm_sparse_*): likewise */
+#include "dfm_hip_sparse_conv.h"
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,464 @@
+"""CPU: the LiDAR teacher above its kernels -- the new header against its binding table and the library, the host-only
+plan entries against the grids of the configs and of the fixture, argument checks that need no device, the encoder's
+state-dict contract, LidarTeacher from the three KITTI configs, the refusals (CPU tensors, training mode, inputs that
+require grad, unsupported settings) and the rebinding of stub mmcv / mmdet3d modules.
+
+Fixture: tests/golden/lidar_teacher.npz (generator tests/golden/make_golden_lidar_teacher.py); tests/
+lidar_teacher_ref.py rebuilds the cases' state dicts."""
+import ctypes
+import importlib
+import os
+import re
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from tests import lidar_teacher_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ('dfm_voxel_keys', 'dfm_voxel_heads', 'dfm_voxel_keep', 'dfm_voxel_fill', 'dfm_sparse_conv_out_shape',
+       'dfm_sparse_conv_workspace_bytes', 'dfm_sparse_index_build', 'dfm_sparse_subm_neighbours',
+       'dfm_sparse_conv_out_rows', 'dfm_sparse_conv_neighbours', 'dfm_sparse_conv_fwd', 'dfm_sparse_dense')
+NAMES = ('hard_voxelize', 'hard_voxelize_batch', 'Voxelization', 'HardSimpleVFE', 'SparseConvTensor', 'SubMConv3d',
+         'SparseConv3d', 'SparseSequential', 'make_sparse_convmodule', 'CustomSparseEncoder', 'LidarTeacher')
+KITTI_CONFIGS = ('dfm_r34_1x8_kitti-3d-3class.py', 'dfm_r34_1x8_kitti-3d-3class_wophotodist.py',
+                 'dfm_r34_1x8_kitti-3d-3class_wophotodist_wodistnorm.py')
+# the lidar_model dict of configs/dfm/dfm_r34_1x8_kitti-3d-3class*.py:13-43 (the three configs share it)
+LIDAR_MODEL = dict(
+    type='VoxelNet',
+    voxel_layer=dict(max_num_points=5, point_cloud_range=[2, -30.4, -3, 59.6, 30.4, 1], voxel_size=[0.05, 0.05, 0.1],
+                     max_voxels=(40000, 40000)),
+    voxel_encoder=dict(type='HardSimpleVFE', num_features=3),
+    middle_encoder=dict(type='CustomSparseEncoder', in_channels=3, output_channels=32,
+                        encoder_strides=((1, ), (2, 1, 1), (2, 1, 1), ((2, 1, 1), 1, 1)),
+                        sparse_shape=[41, 1216, 1152], order=('conv', 'norm', 'act'),
+                        norm_cfg=dict(type='SyncBN', eps=1e-3, momentum=0.01), with_final_bnrelu=False,
+                        output_volume_feat=True),
+    backbone=dict(type='BEVHourglass', in_channels=160, out_channels=64, norm_cfg=dict(type='SyncBN'),
+                  output_prehg_feat=False),
+    neck=None, bbox_head=None, init_cfg=dict(type='Pretrained', checkpoint='teacher.pth'))
+
+
+@pytest.fixture(scope='module')
+def pkg():
+    importlib.import_module('depth-from-motion_amd.build').build_hip()
+    return importlib.import_module('depth-from-motion_amd')
+
+
+def test_names_are_exported_and_registered(pkg):
+    for name in NAMES:
+        assert name in pkg.__all__ and hasattr(pkg, name), name
+    reg = importlib.import_module('depth-from-motion_amd.registry')
+    for name in ('Voxelization', 'HardSimpleVFE', 'SubMConv3d', 'SparseConv3d', 'CustomSparseEncoder'):
+        assert reg.registered()[name] is getattr(pkg, name)
+        assert getattr(pkg, name) not in reg.path_classes()
+    assert 'VoxelNet' not in reg.registered()          # the teacher is built by LidarTeacher, not by type name
+    import inspect
+    sc = importlib.import_module('depth-from-motion_amd.sparse_conv')
+    assert list(inspect.signature(sc.make_sparse_convmodule).parameters) == [
+        'in_channels', 'out_channels', 'kernel_size', 'indice_key', 'stride', 'padding', 'conv_type', 'norm_cfg',
+        'order']
+    assert list(inspect.signature(sc.CustomSparseEncoder.__init__).parameters)[1:] == [
+        'in_channels', 'sparse_shape', 'order', 'norm_cfg', 'base_channels', 'output_channels', 'encoder_channels',
+        'encoder_strides', 'encoder_paddings', 'block_type', 'with_final_bnrelu', 'output_volume_feat']
+    assert list(inspect.signature(sc.CustomSparseEncoder.forward).parameters) == [
+        'self', 'voxel_features', 'coors', 'batch_size']
+    assert list(inspect.signature(pkg.Voxelization.__init__).parameters)[1:6] == [
+        'voxel_size', 'point_cloud_range', 'max_num_points', 'max_voxels', 'deterministic']
+    assert list(inspect.signature(pkg.DfMImitationMixin.extract_lidar_model_feat).parameters) == ['self', 'points']
+
+
+def test_header_binding_and_library_agree_on_the_new_symbols(pkg):
+    main = open(os.path.join(ROOT, 'include', 'dfm_hip.h')).read()
+    assert '#include "dfm_hip_sparse_conv.h"' in main
+    text = open(os.path.join(ROOT, 'include', 'dfm_hip_sparse_conv.h')).read()
+    code = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    decls = {}
+    for m in re.finditer(r'^DFM_API\s+([\w\s\*]+?)\b(dfm_\w+)\s*\(([^)]*)\)\s*;', code, flags=re.M):
+        decls[m.group(2)] = (' '.join(m.group(1).split()), m.group(3).count(',') + 1)
+    capi = pkg._capi
+    assert sorted(decls) == sorted(NEW) == sorted(capi.SPARSE_CONV_SIGNATURES)
+    assert capi.SPARSE_CONV_EXPORTS == tuple(capi.SPARSE_CONV_SIGNATURES)
+    assert not set(NEW) & (set(capi.EXPORTS) | set(capi.BBOX_DECODE_EXPORTS) | set(capi.ATSS_TARGET_EXPORTS) |
+                           set(capi.DEFORM_CONV_EXPORTS))
+    h, lib = ctypes.CDLL(capi.LIB_PATH), capi.lib()
+    for name, (ret, nparams) in decls.items():
+        restype, argtypes = capi.SPARSE_CONV_SIGNATURES[name]
+        assert (ret, restype) in (('int', ctypes.c_int), ('size_t', ctypes.c_size_t)), name
+        assert len(argtypes) == nparams, name
+        assert hasattr(h, name), f'{name} not exported by the library'
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    for phrase in ('a row\n * with b < 0 does not exist', 'The padding argument is ignored', '(kD, kH, kW, Cin, Cout)',
+                   'active rows only', 'never on the linear key', 'v_mfma_f32_16x16x4_f32', 'No atomics on feature data',
+                   'under any permutation of the input rows', 'The order of output rows is unspecified',
+                   'first appearance of a point', 'IEEE\n * fp32 division'):
+        assert phrase in text, phrase                     # the semantics are stated in the header
+    # the structs follow the header
+    assert ctypes.sizeof(capi.SparseConvDesc) == 4 * 14 and ctypes.sizeof(capi.SparseConvPlan) == 4 * 4 + 8 * 3
+    assert ctypes.sizeof(capi.VoxelDesc) == 4 * 7 + 4 * 6 + 4 + 8 * 65    # 4 bytes of padding before the offsets
+    assert capi.SPARSE_MAX_TAPS == 27 and sorted(capi.SPARSE_STATUS) == [1, 2, 4, 8]
+
+
+def test_plan_reproduces_the_grids(pkg):
+    plan = pkg.sparse_conv_plan
+    # the teacher: [41, 1216, 1152] -> [21, 608, 576] -> [11, 304, 288] -> [5, 304, 288]
+    p = plan(2, [41, 1216, 1152], 3, 2, 1, in_rows=80000)
+    assert p['out_shape'] == [21, 608, 576] and p['taps'] == 27 and p['out_rows'] == 8 * 80000
+    assert p['in_capacity'] == 262144 and p['out_capacity'] == 2097152        # powers of two >= twice the rows
+    p2 = plan(2, p['out_shape'], 3, 2, 1, in_rows=p['out_rows'])
+    assert p2['out_shape'] == [11, 304, 288] and p2['out_rows'] == 2 * 11 * 304 * 288   # capped by the cells
+    p3 = plan(2, p2['out_shape'], 3, (2, 1, 1), (0, 1, 1), in_rows=1000)
+    assert p3['out_shape'] == [5, 304, 288] and p3['out_rows'] == 18 * 1000   # prod ceil(k / s) = 2 * 3 * 3
+    assert plan(2, [5, 304, 288], 1, 1, 0, in_rows=77)['out_shape'] == [5, 304, 288]
+    assert plan(2, [5, 304, 288], (3, 1, 1), (2, 1, 1), 0, in_rows=77) == dict(
+        out_shape=[2, 304, 288], taps=3, out_rows=154, in_capacity=256, out_capacity=512,
+        workspace_bytes=(256 + 512) * 12 + 3 * 154 * 4)
+    s = plan(3, [41, 1216, 1152], 3, 1, 1, in_rows=1000, subm=True)
+    assert s['out_shape'] == [41, 1216, 1152] and s['out_rows'] == 1000 and s['out_capacity'] == 0
+    # the fixture's grids: every stage of both encoder cases, the floor of the size formula at the odd one
+    z = ref.fixture()
+    for case, want in (('enc_9_24_20', [[9, 24, 20], [9, 24, 20], [5, 12, 10], [3, 6, 5], [1, 6, 5], [1, 6, 5]]),
+                       ('enc_11_25_19', [[11, 25, 19], [11, 25, 19], [6, 13, 10], [3, 7, 5], [1, 7, 5], [1, 7, 5]])):
+        shape = [int(s) for s in z[f'enc.{case}.sparse_shape']]
+        assert shape == want[0]
+        got = [shape, shape]
+        for stride, padding in ((2, 1), (2, 1), ((2, 1, 1), (0, 1, 1))):
+            got.append(plan(2, got[-1], 3, stride, padding, in_rows=10)['out_shape'])
+        got.append(plan(2, got[-1], 1, 1, 0, in_rows=10)['out_shape'])
+        assert got == want
+        for i, g in enumerate(want):
+            assert [int(s) for s in z[f'enc.{case}.stage{i}.shape']] == g
+    assert plan(1, [4, 4, 4], 3, 1, 0, in_rows=0)['out_rows'] == 0            # no rows: a valid plan
+
+
+def test_plan_rejects_bad_geometry_without_a_gpu(pkg):
+    capi = pkg._capi
+    lib = capi.lib()
+
+    def call(in_rows=10, **kw):
+        d = capi.SparseConvDesc(batch=2, subm=0)
+        for a in range(3):
+            d.in_size[a], d.kernel[a], d.stride[a], d.padding[a] = 8, 3, 1, 1
+        for k, v in kw.items():
+            if isinstance(v, tuple):
+                for a in range(3):
+                    getattr(d, k)[a] = v[a]
+            else:
+                setattr(d, k, v)
+        plan = capi.SparseConvPlan()
+        rc = lib.dfm_sparse_conv_out_shape(ctypes.byref(d), in_rows, ctypes.byref(plan))
+        assert (lib.dfm_sparse_conv_workspace_bytes(ctypes.byref(d), in_rows) == 0) == (rc != 0)
+        return rc, lib.dfm_last_error()
+
+    assert call()[0] == 0
+    for bad, word in ((dict(in_size=(0, 8, 8)), b'grid size'), (dict(in_size=(8, -1, 8)), b'grid size'),
+                      (dict(kernel=(3, 0, 3)), b'kernel size'), (dict(stride=(1, 1, 0)), b'stride'),
+                      (dict(padding=(0, -1, 0)), b'padding'), (dict(batch=0), b'batch'),
+                      (dict(in_size=(2, 8, 8), padding=(0, 1, 1)), b'larger than the padded input'),   # k > in + 2 p
+                      (dict(in_rows=-1), b'in_rows'), (dict(subm=1, kernel=(3, 1, 1)), b'subm')):
+        rc, msg = call(**bad)
+        assert rc == -1 and word in msg, (bad, msg)
+    for bad, word in ((dict(kernel=(3, 3, 5), padding=(1, 1, 2)), b'offsets'),
+                      (dict(batch=1 << 20, in_size=(1 << 14, 1 << 14, 1 << 14)), b'2^62'),   # past the key width
+                      (dict(in_rows=1 << 31), b'2^31'),
+                      (dict(in_rows=1 << 29, in_size=(1 << 10, 1 << 10, 1 << 12)), b'2^31')):
+        rc, msg = call(**bad)
+        assert rc == capi.DFM_ERR_UNSUPPORTED and word in msg, (bad, msg)
+    assert lib.dfm_sparse_conv_out_shape(None, 1, ctypes.byref(capi.SparseConvPlan())) == -1
+    d = capi.SparseConvDesc(batch=1)
+    assert lib.dfm_sparse_conv_out_shape(ctypes.byref(d), 1, None) == -1 and b'NULL' in lib.dfm_last_error()
+    with pytest.raises(capi.DfmHipError, match='larger than the padded input'):
+        pkg.sparse_conv_plan(1, [2, 8, 8], 3, 1, (0, 1, 1))
+
+
+def test_null_pointers_and_bad_descriptors_return_errors_without_a_gpu(pkg):
+    capi = pkg._capi
+    lib = capi.lib()
+    buf = ctypes.create_string_buffer(1 << 16)
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)      # aligned host memory, never dereferenced
+    odd = ctypes.c_void_p(p.value + 4)
+    size = (ctypes.c_int32 * 3)(8, 8, 8)
+    ib, sn = lib.dfm_sparse_index_build, lib.dfm_sparse_subm_neighbours
+    assert ib(None, 10, 1, size, p, p, 32, p, None) == -1 and b'NULL' in lib.dfm_last_error()
+    assert ib(p, 10, 1, size, None, p, 32, p, None) == -1 and ib(p, 10, 1, size, p, p, 32, None, None) == -1
+    assert ib(p, 10, 1, None, p, p, 32, p, None) == -1 and b'grid' in lib.dfm_last_error()
+    assert ib(p, 10, 0, size, p, p, 32, p, None) == -1
+    assert ib(p, 10, 1, size, p, p, 24, p, None) == -1 and b'power of two' in lib.dfm_last_error()
+    assert ib(p, 10, 1, size, p, p, 16, p, None) == -1                         # capacity < 2 * rows
+    assert ib(odd, 10, 1, size, p, p, 32, p, None) == -1 and b'aligned' in lib.dfm_last_error()
+    assert ib(None, 0, 1, size, p, p, 16, p, None) == 0                        # no rows: a valid no-op
+    assert sn(p, 10, 1, size, p, p, 32, None, None) == -1 and sn(p, 10, 1, size, None, p, 32, p, None) == -1
+    d = capi.SparseConvDesc(batch=1, subm=0)
+    for a in range(3):
+        d.in_size[a], d.kernel[a], d.stride[a], d.padding[a] = 8, 3, 2, 1
+    dref = ctypes.byref(d)
+    assert lib.dfm_sparse_conv_out_rows(dref, None, 10, p, p, p, p, None) == -1
+    assert lib.dfm_sparse_conv_out_rows(dref, p, 10, p, p, None, p, None) == -1
+    assert lib.dfm_sparse_conv_out_rows(None, p, 10, p, p, p, p, None) == -1
+    assert lib.dfm_sparse_conv_neighbours(dref, None, 10, p, p, p, None) == -1
+    assert lib.dfm_sparse_conv_neighbours(dref, p, 10, p, None, p, None) == -1
+    d.stride[0] = 0
+    assert lib.dfm_sparse_conv_out_rows(dref, p, 10, p, p, p, p, None) == -1 and b'stride' in lib.dfm_last_error()
+    fwd = lib.dfm_sparse_conv_fwd
+    assert fwd(16, 16, 27, None, 10, p, p, 10, p, p, p, 1, p, None) == -1 and b'NULL' in lib.dfm_last_error()
+    assert fwd(16, 16, 27, p, 10, p, p, 10, None, p, p, 1, p, None) == -1
+    assert fwd(16, 16, 27, p, 10, p, p, 10, p, p, None, 1, p, None) == -1 and b'together' in lib.dfm_last_error()
+    assert fwd(16, 16, 27, p, 10, None, p, 10, p, p, p, 1, p, None) == -1       # no table for 27 offsets
+    assert fwd(16, 16, 27, p, 10, p, p, 10, p, p, p, 1, odd, None) == -1 and b'aligned' in lib.dfm_last_error()
+    assert fwd(0, 16, 27, p, 10, p, p, 10, p, p, p, 1, p, None) == -1
+    for cin, cout in ((5, 16), (128, 16), (16, 48), (16, 128)):
+        assert fwd(cin, cout, 27, p, 10, p, p, 10, p, p, p, 1, p, None) == capi.DFM_ERR_UNSUPPORTED
+        assert b'channels' in lib.dfm_last_error()
+    assert fwd(16, 16, 28, p, 10, p, p, 10, p, p, p, 1, p, None) == capi.DFM_ERR_UNSUPPORTED
+    assert fwd(16, 16, 27, None, 0, p, None, 0, p, None, None, 0, None, None) == 0   # no rows: a valid no-op
+    assert lib.dfm_sparse_dense(p, p, 10, 16, 1, size, None, None) == -1
+    assert lib.dfm_sparse_dense(None, p, 10, 16, 1, size, p, None) == -1
+    assert lib.dfm_sparse_dense(p, p, 10, 0, 1, size, p, None) == -1
+    # voxelization
+    vd = capi.VoxelDesc(batch=1, ndim=4, max_num_points=5, max_voxels=10)
+    for j in range(3):
+        vd.grid[j], vd.vs[j] = 8, 0.1
+    vd.offset[1] = 100
+    for b in range(2, 65):
+        vd.offset[b] = 100
+    v = ctypes.byref(vd)
+    assert lib.dfm_voxel_keys(v, None, p, None) == -1 and b'NULL' in lib.dfm_last_error()
+    assert lib.dfm_voxel_keys(None, p, p, None) == -1
+    assert lib.dfm_voxel_heads(v, p, None, p, p, None) == -1 and lib.dfm_voxel_keep(v, p, p, None, None) == -1
+    assert lib.dfm_voxel_fill(v, p, p, p, p, p, p, p, None, p, None) == -1
+    for field, value, word in (('batch', 0, b'batch'), ('batch', 65, b'batch'), ('ndim', 2, b'ndim'),
+                               ('max_num_points', 0, b'start at 1'), ('max_voxels', 0, b'start at 1')):
+        keep = getattr(vd, field)
+        setattr(vd, field, value)
+        assert lib.dfm_voxel_keys(v, p, p, None) == -1 and word in lib.dfm_last_error(), field
+        setattr(vd, field, keep)
+    vd.vs[1] = 0.0
+    assert lib.dfm_voxel_keys(v, p, p, None) == -1 and b'voxel size' in lib.dfm_last_error()
+    vd.vs[1] = 0.1
+    vd.offset[1] = 0
+    assert lib.dfm_voxel_keys(v, None, None, None) == 0                         # an empty cloud: a valid no-op
+
+
+def test_encoder_state_dict_is_the_references(pkg):
+    for case in ('enc_9_24_20', 'enc_11_25_19'):
+        z = ref.fixture()
+        gen = ref.generator()
+        enc = pkg.CustomSparseEncoder(sparse_shape=[int(s) for s in z[f'enc.{case}.sparse_shape']], **gen.ENCODER_CFG)
+        got = [(k, tuple(v.shape)) for k, v in enc.state_dict().items()]
+        assert got == ref.key_shapes(f'enc.{case}')              # the reference's keys, in its order, and shapes
+        missing, unexpected = enc.load_state_dict(ref.state_dict(f'enc.{case}'), strict=True)
+        assert not missing and not unexpected
+    keys = [k for k, _ in got]
+    for k in ('conv_input.0.weight', 'conv_input.1.weight', 'conv_input.1.bias', 'conv_input.1.running_mean',
+              'conv_input.1.running_var', 'conv_input.1.num_batches_tracked', 'encoder_layers.encoder_layer2.0.0.weight',
+              'encoder_layers.encoder_layer4.2.1.running_var', 'conv_out.0.weight'):
+        assert k in keys, k
+    assert dict(got)['conv_input.0.weight'] == (3, 3, 3, 3, 16)                # (kD, kH, kW, Cin, Cout)
+    assert dict(got)['conv_out.0.weight'] == (1, 1, 1, 64, 32) and len(keys) == 1 + 5 + 10 * 6 + 1
+    # indice keys, strides and paddings of the teacher's layers
+    l2, l4 = enc.encoder_layers.encoder_layer2, enc.encoder_layers.encoder_layer4
+    assert type(l2[0][0]) is pkg.SparseConv3d and l2[0][0].indice_key == 'spconv2' and l2[0][0].stride == (2, 2, 2)
+    assert type(l2[1][0]) is pkg.SubMConv3d and l2[1][0].indice_key == l2[2][0].indice_key == 'subm2'
+    assert l4[0][0].stride == (2, 1, 1) and l4[0][0].padding == (0, 1, 1)
+    assert enc.conv_input[0].indice_key == enc.encoder_layers.encoder_layer1[0][0].indice_key == 'subm1'
+    assert type(enc.conv_input[1]) is torch.nn.BatchNorm1d and enc.conv_input[1].eps == 1e-3
+    bn1d = pkg.make_sparse_convmodule(16, 16, 3, 'k', norm_cfg=dict(type='BN1d', eps=1e-3, momentum=0.01))
+    assert type(bn1d[1]) is torch.nn.BatchNorm1d and len(bn1d) == 3
+
+
+def test_lidar_teacher_builds_from_the_kitti_configs(pkg):
+    ref_configs = '/root/reference/configs/dfm'
+    cfgs = [LIDAR_MODEL]
+    if os.path.isdir(ref_configs):   # where the reference checkout is present, its own dicts as well
+        for name in KITTI_CONFIGS:
+            scope = {}
+            exec(compile(open(os.path.join(ref_configs, name)).read(), name, 'exec'), scope)
+            assert scope['model']['lidar_model'] == LIDAR_MODEL or \
+                {k: v for k, v in scope['model']['lidar_model'].items() if k != 'init_cfg'} == \
+                {k: v for k, v in LIDAR_MODEL.items() if k != 'init_cfg'}
+            cfgs.append(scope['model']['lidar_model'])
+    for cfg in cfgs:
+        t = pkg.LidarTeacher(cfg)
+        assert not t.training and not any(p.requires_grad for p in t.parameters())
+        t.train()
+        assert not any(m.training for m in t.modules())            # eval only, as dfm.py:111-116 forces it
+        assert type(t.voxel_layer) is pkg.Voxelization and t.voxel_layer.max_voxels == (40000, 40000)
+        assert t.voxel_layer.grid_size.tolist() == [1152, 1216, 40]
+        assert type(t.voxel_encoder) is pkg.HardSimpleVFE and t.voxel_encoder.num_features == 3
+        assert type(t.middle_encoder) is pkg.CustomSparseEncoder and t.middle_encoder.sparse_shape == [41, 1216, 1152]
+        keys = list(t.state_dict())
+        assert 'middle_encoder.conv_input.0.weight' in keys and 'backbone.compress_conv.bn.running_mean' in keys
+        assert tuple(t.state_dict()['backbone.compress_conv.conv.weight'].shape) == (64, 160, 3, 3)
+    with pytest.raises(KeyError, match='VoxelNet'):
+        pkg.LidarTeacher(dict(LIDAR_MODEL, type='PointPillars'))
+
+
+def test_hard_simple_vfe_divides_on_live_rows_only(pkg):
+    vfe = pkg.HardSimpleVFE(num_features=3)
+    voxels = torch.zeros(4, 5, 4)
+    voxels[0, :2] = torch.tensor([[1., 2., 3., 9.], [3., 4., 5., 9.]])
+    voxels[2, :5] = torch.arange(20.).view(5, 4)
+    num = torch.tensor([2, 0, 5, 0], dtype=torch.int32)
+    out = vfe(voxels, num, None)
+    assert tuple(out.shape) == (4, 3) and torch.equal(out[0], torch.tensor([2., 3., 4.]))
+    assert torch.equal(out[2], voxels[2, :, :3].sum(0) / 5) and not out[1].any() and not out[3].any()
+    assert torch.isfinite(out).all()                               # 0 / 0 never happens on a padding row
+
+
+def test_cpu_tensors_training_mode_and_grad_inputs_are_refused(pkg):
+    with pytest.raises(RuntimeError, match='no CPU path'):
+        pkg.hard_voxelize(torch.zeros(10, 4), [0.1, 0.1, 0.1], [0, 0, 0, 1, 1, 1], 5, 10)
+    with pytest.raises(RuntimeError, match='no CPU path'):
+        pkg.Voxelization([0.1, 0.1, 0.1], [0, 0, 0, 1, 1, 1], 5, (10, 10))(torch.zeros(10, 4))
+    x = pkg.SparseConvTensor(torch.zeros(4, 16), torch.zeros(4, 4, dtype=torch.int32), [4, 4, 4], 1)
+    conv = pkg.SubMConv3d(16, 16, 3, bias=False, indice_key='a').eval()
+    with pytest.raises(RuntimeError, match='no CPU path'):
+        conv(x)
+    with pytest.raises(RuntimeError, match='no CPU path'):
+        x.dense()
+    gen = ref.generator()
+    enc = pkg.CustomSparseEncoder(sparse_shape=[9, 24, 20], **gen.ENCODER_CFG).eval()
+    with pytest.raises(RuntimeError, match='no CPU path'):
+        enc(torch.zeros(4, 3), torch.zeros(4, 4, dtype=torch.int32), 1)
+    t = pkg.LidarTeacher(LIDAR_MODEL)
+    with pytest.raises(RuntimeError, match='no CPU path'):
+        t([torch.zeros(10, 4)])
+
+    # the settings the kernels do not cover: MfmaPathError naming the setting, under every policy -- there is no torch
+    # path behind these classes.  (A meta tensor stands in for a GPU tensor: the checks come before any launch.)
+    class OnGpu(torch.Tensor):
+        is_cuda = True
+
+    def fake(*shape, dtype=torch.float32):
+        return torch.zeros(*shape, dtype=dtype).as_subclass(OnGpu)
+
+    xg = pkg.SparseConvTensor(fake(4, 16), fake(4, 4, dtype=torch.int32), [4, 4, 4], 1)
+    for policy in ('warn', 'raise', 'silent'):
+        prev = pkg.set_fallback_policy(policy)
+        try:
+            with pytest.raises(pkg.MfmaPathError, match='training mode'):
+                pkg.SubMConv3d(16, 16, 3, bias=False).train()(xg)
+            grad = pkg.SparseConvTensor(fake(4, 16).requires_grad_(), fake(4, 4, dtype=torch.int32), [4, 4, 4], 1)
+            with pytest.raises(pkg.MfmaPathError, match='requires grad'):
+                conv(grad)
+            with pytest.raises(pkg.MfmaPathError, match='channels 24->24'):
+                pkg.SparseConv3d(24, 24, 3, bias=False).eval()(
+                    pkg.SparseConvTensor(fake(4, 24), fake(4, 4, dtype=torch.int32), [4, 4, 4], 1))
+            with pytest.raises(pkg.MfmaPathError, match='dtype'):
+                conv(pkg.SparseConvTensor(fake(4, 16, dtype=torch.bfloat16), fake(4, 4, dtype=torch.int32), [4, 4, 4], 1))
+            with pytest.raises(pkg.MfmaPathError, match='basicblock'):
+                pkg.CustomSparseEncoder(3, [9, 24, 20], block_type='basicblock')
+            seq = pkg.make_sparse_convmodule(16, 16, 3, 'k', norm_cfg=dict(type='BN1d', eps=1e-3, momentum=0.01))
+            seq[0].eval()
+            with pytest.raises(pkg.MfmaPathError, match='training mode'):
+                seq(xg)                                            # the BatchNorm is still in training mode
+        finally:
+            pkg.set_fallback_policy(prev)
+    with pytest.raises(NotImplementedError, match='dynamic'):
+        pkg.Voxelization([0.1, 0.1, 0.1], [0, 0, 0, 1, 1, 1], -1, (10, 10))
+
+
+def test_patch_rebinds_stub_modules_and_touches_nothing_when_absent(pkg):
+    integ = importlib.import_module('depth-from-motion_amd.integration')
+    sc = importlib.import_module('depth-from-motion_amd.sparse_conv')
+    chain = ('mmcv', 'mmcv.ops', 'mmcv.cnn', 'mmdet3d', 'mmdet3d.ops', 'mmdet3d.models',
+             'mmdet3d.models.middle_encoders', 'mmdet3d.models.middle_encoders.sparse_encoder',
+             'mmdet3d.models.detectors', 'mmdet3d.models.detectors.dfm')
+    before = {k: sys.modules.get(k) for k in chain}
+    kept = dict(sc._REFERENCE)
+    try:
+        for k in chain:
+            sys.modules.pop(k, None)
+        sc._REFERENCE.clear()
+        assert integ._patch_lidar_teacher() == ([], [], []) and not any(k in sys.modules for k in chain)
+        assert sc._REFERENCE == {}
+
+        class Registry:
+            def __init__(self):
+                self.table = {}
+
+            def get(self, key):
+                return self.table.get(key)
+
+            def register_module(self, name=None, force=False, module=None):
+                assert force or name not in self.table
+                self.table[name] = module
+
+        class MmcvVoxelization:
+            pass
+
+        class MmcvSubM:
+            pass
+
+        def ref_make(*a, **k):
+            raise AssertionError('not replaced')
+
+        class DfM:
+            def extract_lidar_model_feat(self, points):
+                return 'reference'
+
+        ref_method = DfM.extract_lidar_model_feat
+        reg = Registry()
+        reg.table['SubMConv3d'] = MmcvSubM
+        reg.table['Conv2d'] = torch.nn.Conv2d
+        for k in chain:
+            sys.modules[k] = types.ModuleType(k)
+        sys.modules['mmcv.ops'].Voxelization = MmcvVoxelization
+        sys.modules['mmcv.ops'].SubMConv3d = MmcvSubM
+        sys.modules['mmcv.ops'].nms = other = object()
+        sys.modules['mmcv.cnn'].CONV_LAYERS = reg
+        sys.modules['mmdet3d.ops'].make_sparse_convmodule = ref_make
+        sys.modules['mmdet3d.models.middle_encoders.sparse_encoder'].make_sparse_convmodule = ref_make
+        sys.modules['mmdet3d.models.detectors.dfm'].DfM = DfM
+        functions, layers, methods = integ._patch_lidar_teacher()
+        assert functions == ['mmcv.ops.Voxelization', 'mmcv.ops.SubMConv3d', 'mmdet3d.ops.make_sparse_convmodule',
+                             'mmdet3d.models.middle_encoders.sparse_encoder.make_sparse_convmodule']
+        assert layers == ['SubMConv3d (mmcv CONV_LAYERS)', 'SparseConv3d (mmcv CONV_LAYERS)']
+        assert methods == ['DfM.extract_lidar_model_feat']
+        assert sys.modules['mmcv.ops'].Voxelization is pkg.Voxelization
+        assert sys.modules['mmcv.ops'].SubMConv3d is pkg.SubMConv3d and sys.modules['mmcv.ops'].nms is other
+        assert reg.table['SubMConv3d'] is pkg.SubMConv3d and reg.table['SparseConv3d'] is pkg.SparseConv3d
+        assert reg.table['Conv2d'] is torch.nn.Conv2d
+        assert sys.modules['mmdet3d.ops'].make_sparse_convmodule is pkg.make_sparse_convmodule
+        assert DfM.extract_lidar_model_feat is pkg.DfMLidarTeacherMixin.extract_lidar_model_feat
+        want = {'mmcv.ops.Voxelization': MmcvVoxelization, 'mmcv.ops.SubMConv3d': MmcvSubM,
+                'CONV_LAYERS.SubMConv3d': MmcvSubM, 'mmdet3d.ops.make_sparse_convmodule': ref_make,
+                'mmdet3d.models.middle_encoders.sparse_encoder.make_sparse_convmodule': ref_make,
+                'DfM.extract_lidar_model_feat': ref_method}
+        assert sc._REFERENCE == want                                # what was replaced is kept
+        # a second call changes nothing and loses nothing
+        assert integ._patch_lidar_teacher() == (functions, layers, methods) and sc._REFERENCE == want
+        # a teacher built from classes that are not this package's keeps the reference's method
+        det = DfM()
+        det.lidar_model = types.SimpleNamespace(voxel_layer=MmcvVoxelization())
+        assert det.extract_lidar_model_feat([]) == 'reference'
+    finally:
+        for k, v in before.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
+        sc._REFERENCE.clear()
+        sc._REFERENCE.update(kept)
+
+
+def test_the_fixture_is_small_and_whole(pkg):
+    z = ref.fixture()
+    assert os.path.getsize(os.path.join(ROOT, 'tests', 'golden', 'lidar_teacher.npz')) <= 1 << 20
+    gen = ref.generator()
+    for name in gen.LAYERS:
+        sd = ref.state_dict(f'layer.{name}')                       # regenerated weights match the stored digests
+        assert tuple(sd['0.weight'].shape)[3:] == gen.LAYERS[name][1:3]
+        assert 0 < float(z[f'layer.{name}.stage.err']) < 2e-6
+    for name in ('faces', 'nan', 'crowded', 'cut', 'empty', 'outside', 'ndim5', 'ndim3'):
+        v, c, n = (z[f'vox.{name}.{q}'] for q in ('voxels', 'coors', 'num_points'))
+        assert v.shape[0] == c.shape[0] == n.shape[0] <= int(z[f'vox.{name}.max_voxels'])
+        assert v.shape[1:] == (5, z[f'vox.{name}.points'].shape[1]) and c.shape[1:] == (3, )
+    assert int(z['vox.crowded.num_points'].max()) == 5 and len(z['vox.cut.coors']) == 37
+    assert len(z['vox.empty.coors']) == 0 and len(z['vox.outside.coors']) == 0
+    assert np.isnan(z['vox.nan.points'][:, :3]).any() and not np.isnan(z['vox.nan.voxels'][:, :, :3]).any()
+    assert (z['vox.batch.coors'][:, 0] != 1).all() and set(z['vox.batch.coors'][:, 0]) == {0, 2}
