@@ -451,6 +451,26 @@ SPARSE_CONV_SIGNATURES = _sparse_conv_signatures()
 SPARSE_CONV_EXPORTS = tuple(SPARSE_CONV_SIGNATURES)
 
 
+KITTI_SAMPLE_POINTS, KITTI_LDS_DETS = 41, 128  # DFM_KITTI_SAMPLE_POINTS, DFM_KITTI_LDS_DETS
+
+
+def _kitti_eval_signatures():
+    """the same for include/dfm_hip_kitti_eval.h: the KITTI evaluation's same-frame overlaps and its matching
+    (tests/test_kitti_eval.py checks this table against that header and the built library)"""
+    vp = fp = ctypes.c_void_p
+    ci, i32, i64, sz = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
+    return {
+        'dfm_kitti_overlaps': (ci, [i64, i64, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]),
+        'dfm_kitti_eval_workspace_bytes': (sz, [i64, i32, i64, i32]),
+        'dfm_kitti_match': (ci, [i32, i32, i32, i64, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, i64,
+                                 i64, fp, fp, fp, fp, fp, fp, i64, vp, sz, vp]),
+    }
+
+
+KITTI_EVAL_SIGNATURES = _kitti_eval_signatures()
+KITTI_EVAL_EXPORTS = tuple(KITTI_EVAL_SIGNATURES)
+
+
 _lib = None
 
 
@@ -467,7 +487,7 @@ def lib():
     h = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in (*SIGNATURES.items(), *BBOX_DECODE_SIGNATURES.items(),
                                       *ATSS_TARGET_SIGNATURES.items(), *DEFORM_CONV_SIGNATURES.items(),
-                                      *SPARSE_CONV_SIGNATURES.items()):
+                                      *SPARSE_CONV_SIGNATURES.items(), *KITTI_EVAL_SIGNATURES.items()):
         fn = getattr(h, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = h

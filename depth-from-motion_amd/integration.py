@@ -50,6 +50,7 @@ from .deform_conv import ModulatedDeformConv2dPack, modulated_deform_conv2d
 from . import sparse_conv as _sparse_conv
 from .sparse_conv import SparseConv3d, SparseConvTensor, SparseSequential, SubMConv3d
 from .voxelize import Voxelization
+from . import kitti_eval as _kitti_eval
 from .geometry import prepare_coordinates_3d, prepare_depth
 from .conv3d import MfmaConv3dTo1
 from .graphs import GraphedCallable
@@ -621,6 +622,27 @@ def _patch_lidar_teacher():
     return functions, layers, methods
 
 
+# the KITTI evaluation: ``kitti_eval`` in every module that holds it by name, and ``rotate_iou_gpu_eval`` (numba.cuda in
+# the reference) where it is defined.  The datasets import ``kitti_eval`` from ``mmdet3d.core.evaluation`` at call time,
+# so rebinding the names is enough.  Only where those modules are already imported, as above: eval.py imports numba.
+_KITTI_EVAL_MODULES = ('mmdet3d.core.evaluation.kitti_utils.eval', 'mmdet3d.core.evaluation.kitti_utils',
+                       'mmdet3d.core.evaluation', 'mmdet3d.core')
+_ROTATE_IOU_MODULES = ('mmdet3d.core.evaluation.kitti_utils.rotate_iou',)
+
+
+def _patch_kitti_eval():
+    """-> functions rebound"""
+    done = []
+    for modules, attr, fn in ((_KITTI_EVAL_MODULES, 'kitti_eval', _kitti_eval.kitti_eval),
+                              (_ROTATE_IOU_MODULES, 'rotate_iou_gpu_eval', _kitti_eval.rotate_iou_eval)):
+        for mod_name in modules:
+            mod = sys.modules.get(mod_name)
+            if mod is not None and hasattr(mod, attr):
+                setattr(mod, attr, fn)
+                done.append(f'{mod_name}.{attr}')
+    return done
+
+
 def patch_reference(precision=None, strict=False):
     """Route a real mmdet3d (the reference fork) to the HIP path.  Call once after
     ``import mmdet3d`` and before building the model from ``configs/dfm/*``.  Returns a report
@@ -645,6 +667,7 @@ def patch_reference(precision=None, strict=False):
             report['functions'].append(f'{mod_name}.{attr}')
     report['functions'] += _patch_nms_functions()
     report['functions'] += _patch_iou_functions()
+    report['functions'] += _patch_kitti_eval()
     functions, methods = _patch_anchor_target()
     report['functions'] += functions
     report['methods'] += methods

@@ -1376,6 +1376,8 @@ DFM_API int dfm_spp_tail_fwd(const dfm_spp_desc *desc, const void *const *pooled
 #include "dfm_hip_deform_conv.h"
 /* the LiDAR teacher: hard voxelization (dfm_voxel_*) and sparse 3-D convolutions (dfm_sparse_*): likewise */
 #include "dfm_hip_sparse_conv.h"
+/* KITTI evaluation: same-frame overlaps and the AP / AOS matching (dfm_kitti_*): likewise */
+#include "dfm_hip_kitti_eval.h"
 
 #ifdef __cplusplus
 }

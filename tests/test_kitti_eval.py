@@ -1,0 +1,422 @@
+"""CPU: the KITTI evaluation above the kernels -- the fixture's own consistency (shapes, flags, the guards re-checked
+from the stored numbers), the new header against its binding table and the library, the vectorised clean_data against
+the recorded flags, get_thresholds / get_mAP11 / get_mAP40 and the result text against the recorded ones, the two
+deliberate deviations from the reference, the refusal of bad offset tables, the no-CPU-path error and the rebinding of
+stub mmdet3d modules.
+
+Fixture numbers (tests/golden/kitti_eval.npz, generator tests/golden/make_golden_kitti_eval.py): the reference's own
+rotated-overlap algorithm differs between fp64 and fp32 arithmetic by at most ``fp32_iou_error`` = 1.27e-4 over the
+stored pairs (the 70 and 130 near-duplicate detections of the ``edge`` scene set it; the 24-frame scene alone stays
+below 1e-5); ``GUARD_BAND`` = 4 x that = 5.1e-4.  The GPU tests read both."""
+import ctypes
+import importlib
+import os
+import re
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from tests import kitti_eval_util as ku
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ('dfm_kitti_overlaps', 'dfm_kitti_eval_workspace_bytes', 'dfm_kitti_match')
+NAMES = ('rotate_iou_eval', 'bev_box_overlap', 'd3_box_overlap', 'image_box_overlap', 'calculate_iou_partly',
+         'eval_class', 'get_mAP11', 'get_mAP40', 'do_eval', 'kitti_eval')
+
+
+@pytest.fixture(scope='module')
+def pkg():
+    importlib.import_module('depth-from-motion_amd.build').build_hip()
+    return importlib.import_module('depth-from-motion_amd')
+
+
+@pytest.fixture(scope='module')
+def ke(pkg):
+    return importlib.import_module('depth-from-motion_amd.kitti_eval')
+
+
+@pytest.fixture(scope='module')
+def z():
+    return ku.fixture()
+
+
+def blocks(z, scene, key):
+    """per-frame (n_dt, n_gt) blocks of a stored flat overlap array"""
+    nd, ng = z[f'{scene}/dt_num'], z[f'{scene}/gt_num']
+    off = np.concatenate([[0], np.cumsum(nd * ng)])
+    return [z[f'{scene}/{key}'][off[f]:off[f + 1]].reshape(nd[f], ng[f]) for f in range(len(nd))]
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the fixture
+# ---------------------------------------------------------------------------------------------------------
+def test_fixture_figures_and_size(z):
+    err, guard = float(z['fp32_iou_error']), float(z['GUARD_BAND'])
+    assert 0 < err <= 1.3e-4 and guard == 4 * err                            # the docstring's figure
+    assert 0 < float(z['crit/fp32_error']) < 1e-4
+    assert os.path.getsize(ku.PATH) < 1024 * 1024
+    assert z['crit/boxes'].shape == (40, 5) and z['crit/query_boxes'].shape == (30, 5)
+    for crit in (-1, 0, 1, 2):
+        assert z[f'crit/iou_{crit}'].shape == (40, 30) and (z[f'crit/iou_{crit}'] > 0).sum() >= 10
+    # criterion 0 divides by the QUERY's area, 1 by the box's (the kernel's argument order), 2 is the area itself
+    area_b = (z['crit/boxes'][:, 2] * z['crit/boxes'][:, 3]).astype(np.float32).astype(np.float64)[:, None]
+    area_q = (z['crit/query_boxes'][:, 2] * z['crit/query_boxes'][:, 3]).astype(np.float32).astype(np.float64)[None]
+    inter = z['crit/iou_2']
+    assert np.allclose(z['crit/iou_0'], inter / area_q, rtol=1e-6) and np.allclose(z['crit/iou_1'], inter / area_b,
+                                                                                  rtol=1e-6)
+    assert np.allclose(z['crit/iou_-1'], inter / (area_b + area_q - inter), rtol=1e-6)
+
+
+def test_scene_shapes(z):
+    assert len(z['val24/gt_num']) == 24 and z['val24/gt_num'].min() >= 2 and z['val24/gt_num'].max() <= 9
+    assert set(z['val24/gt_name'].tolist()) == {'Car', 'Pedestrian', 'Cyclist', 'Van', 'Person_sitting', 'DontCare'}
+    assert z['edge/gt_num'].tolist()[1:5] == [0, 9, 0, 1] and z['edge/gt_num'][0] > 0 and z['edge/gt_num'][5] == 9
+    assert z['edge/dt_num'].tolist()[1:] == [0, 0, 7, 70, 130] and z['edge/dt_num'][0] > 0
+    assert z['single/gt_num'].tolist() == [1] and z['single/dt_num'].tolist() == [1]
+    h = z['val24/gt_bbox'][:, 3] - z['val24/gt_bbox'][:, 1]
+    hd = z['val24/dt_bbox'][:, 3] - z['val24/dt_bbox'][:, 1]
+    for heights in (h, hd):                                                  # both sides of 25 px and of 40 px
+        assert (heights < 25).any() and ((heights > 25) & (heights < 40)).any() and (heights > 40).any()
+    assert len(set(z['val24/gt_occluded'].tolist())) >= 4 and len(set(z['val24/gt_truncated'].tolist())) >= 4
+    for scene in ku.SCENES:
+        total_gt, total_dt = int(z[f'{scene}/gt_num'].sum()), int(z[f'{scene}/dt_num'].sum())
+        pairs = int((z[f'{scene}/gt_num'] * z[f'{scene}/dt_num']).sum())
+        for k in ku.GT_KEYS:
+            assert z[f'{scene}/gt_{k}'].shape[0] == total_gt, (scene, k)
+        for k in ku.DT_KEYS:
+            assert z[f'{scene}/dt_{k}'].shape[0] == total_dt, (scene, k)
+        for m in range(3):
+            assert z[f'{scene}/overlaps{m}'].shape == (pairs,) and z[f'{scene}/overlaps{m}'].dtype == np.float64
+        assert z[f'{scene}/ignored_gt'].shape == (3, 3, total_gt) and z[f'{scene}/ignored_dt'].shape == (3, 3, total_dt)
+        assert set(np.unique(z[f'{scene}/ignored_gt']).tolist()) <= {-1, 0, 1}
+        assert np.array_equal(z[f'{scene}/num_valid_gt'], (z[f'{scene}/ignored_gt'] == 0).sum(-1))
+    # some detections sit inside DontCare boxes
+    assert (z['val24/dc_overlaps'] > 0.7).any()
+
+
+@pytest.mark.parametrize('scene', ku.SCENES)
+def test_guards_hold_in_the_stored_numbers(z, scene):
+    guard = float(z['GUARD_BAND'])
+    for m in range(3):
+        ov = z[f'{scene}/overlaps{m}']
+        for t in ku.MIN_OVERLAPS[m]:
+            assert np.all(np.abs(ov - t) > guard), (m, t)
+        if m:
+            assert np.all(ov < 1 - 1e-9)                                     # no coincident boxes
+        low = min(ku.MIN_OVERLAPS[m])
+        for block in blocks(z, scene, f'overlaps{m}'):
+            for i in range(block.shape[1]):
+                col = np.sort(block[block[:, i] > low - guard, i])
+                assert np.all(np.diff(col) > guard), (m, i)
+    for t in ku.MIN_OVERLAPS[0]:
+        assert np.all(np.abs(z[f'{scene}/dc_overlaps'] - t) > guard)
+    off = np.concatenate([[0], np.cumsum(z[f'{scene}/dt_num'])])
+    for f in range(len(off) - 1):
+        s = z[f'{scene}/dt_score'][off[f]:off[f + 1]]
+        assert len(set(s.tolist())) == len(s)                                 # distinct within a frame
+
+
+def test_val24_has_every_outcome_and_no_printed_value_on_a_rounding_boundary(z):
+    for m in range(3):
+        pr, nthr = z[f'val24/all/m{m}/pr'], z[f'val24/all/m{m}/num_thresholds']
+        for c in range(3):                                                   # strict overlap, hard: tp, fp, fn >= 1
+            last = pr[c, 2, 0, nthr[c, 2, 0] - 1]
+            assert nthr[c, 2, 0] > 0 and np.all(last[:3] >= 1), (m, c, last)
+        prec = z[f'val24/all/m{m}/precision']
+        assert 0 < prec.max() <= 1 and prec.min() == 0 and not np.all((prec == 0) | (prec == 1))
+    for key, variant in ku.VARIANTS:
+        for v in z[f'{key}/{variant}/ret_values']:
+            assert abs((float(v) * 1e4) % 1.0 - 0.5) * 1e-4 > 1e-6
+    assert z['val24/all/m0/orientation'].max() > 0 and z['val24/noaos/m0/orientation'].max() == 0
+    assert not any('Overall' in k for k in z['val24/car/ret_keys']) and 'aos' not in str(z['val24/noaos/result'])
+    # the reference appended 'aos' to the list it was given (the first deviation)
+    assert z['val24/all/eval_types_after'].tolist() == ['bbox', 'bev', '3d', 'aos', 'aos']
+    assert z['val24/noaos/eval_types_after'].tolist() == ['bbox', 'bev', '3d']
+
+
+# ---------------------------------------------------------------------------------------------------------
+# header, binding, library
+# ---------------------------------------------------------------------------------------------------------
+def test_names_are_exported(pkg, ke):
+    for name in NAMES:
+        assert callable(getattr(pkg, name)) and name in pkg.__all__ and name in ke.__all__, name
+
+
+def test_header_binding_and_library_agree_on_the_new_symbols(pkg):
+    main = open(os.path.join(ROOT, 'include', 'dfm_hip.h')).read()
+    assert '#include "dfm_hip_kitti_eval.h"' in main
+    text = open(os.path.join(ROOT, 'include', 'dfm_hip_kitti_eval.h')).read()
+    code = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    decls = {}
+    for m in re.finditer(r'^DFM_API\s+([\w\s\*]+?)\b(dfm_\w+)\s*\(([^)]*)\)\s*;', code, flags=re.M):
+        decls[m.group(2)] = (' '.join(m.group(1).split()), m.group(3).count(',') + 1)
+    capi = pkg._capi
+    assert sorted(decls) == sorted(NEW) == sorted(capi.KITTI_EVAL_SIGNATURES)
+    assert capi.KITTI_EVAL_EXPORTS == tuple(capi.KITTI_EVAL_SIGNATURES)
+    for other in (capi.EXPORTS, capi.BBOX_DECODE_EXPORTS, capi.ATSS_TARGET_EXPORTS, capi.DEFORM_CONV_EXPORTS,
+                  capi.SPARSE_CONV_EXPORTS):
+        assert not set(NEW) & set(other)
+    assert len(capi.EXPORTS) == 114                               # the main header keeps its declarations
+    restypes = {'int': ctypes.c_int, 'size_t': ctypes.c_size_t}
+    h, lib = ctypes.CDLL(capi.LIB_PATH), capi.lib()
+    for name, (ret, nparams) in decls.items():
+        restype, argtypes = capi.KITTI_EVAL_SIGNATURES[name]
+        assert len(argtypes) == nparams and restype is restypes[ret], name
+        assert hasattr(h, name), f'{name} not exported by the library'
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    for phrase in ('row-major (n_dt, n_gt)', 'ONE LANE PER PAIR', 'no +1', 'ROUNDED TO FP32', 'reflection',
+                   'COINCIDENT BOXES', '1/3', 'ONE WAVE PER (combination, frame)', 'NO_DETECTION = -10000000',
+                   'assigned_ignored_det', 'score < thresh', 'DontCare pass for metric 0 only',
+                   '(1 + cos(alpha_gt - alpha_dt)) / 2', 'No floating atomics', 'THE CALLER', 'there is no cap'):
+        assert phrase in text, phrase                             # the semantics are stated in the header
+    for name, value in (('DFM_KITTI_SAMPLE_POINTS', capi.KITTI_SAMPLE_POINTS), ('DFM_KITTI_LDS_DETS', capi.KITTI_LDS_DETS)):
+        assert int(re.search(rf'#define {name} (\d+)', text).group(1)) == value
+    assert (capi.KITTI_SAMPLE_POINTS, capi.KITTI_LDS_DETS) == (41, 128)
+
+
+def test_bad_arguments_are_rejected_without_touching_the_gpu(pkg):
+    lib = pkg._capi.lib()
+    buf = ctypes.create_string_buffer(4096 + 16)
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)      # aligned host memory, never dereferenced
+    ov = lib.dfm_kitti_overlaps
+    tail = (p,) * 11
+    assert ov(-1, 4, -1, *tail, p, p, p, None) == -1
+    assert ov(2, 4, -1, *tail, None, None, None, None) == -1 and b'no metric' in lib.dfm_last_error()
+    assert ov(0, 0, -1, *(None,) * 11, p, None, None, None) == 0            # nothing to do: a valid no-op
+    assert ov(2, 4, -1, *(None,) * 11, p, None, None, None) == -1 and b'offset table' in lib.dfm_last_error()
+    assert ov(2, 4, -1, None, p, p, p, p, None, p, p, p, p, p, p, None, None, None) == -1 and \
+        b'bbox' in lib.dfm_last_error()
+    assert ov(2, 4, -1, p, None, p, p, p, p, p, p, p, p, p, None, p, None, None) == -1 and \
+        b'location' in lib.dfm_last_error()
+    size = lib.dfm_kitti_eval_workspace_bytes
+    assert size(-1, 18, 10, 0) == 0 and size(10, -1, 10, 0) == 0 and size(10, 18, -1, 0) == 0
+    assert size(10, 18, 128, 0) == 16                             # the masks fit the LDS: nothing but the pad
+    assert size(10, 18, 129, 0) == 16 + 180 * 3 * 64 * 8          # 3 words per lane, one slot per wave
+    assert size(10, 18, 128, 1) == 16 + 10 * 18 * 41 * 8          # the similarity partials
+    assert size(4000, 18, 129, 0) == 16 + 16384 * 3 * 64 * 8      # at most DFM_KITTI_MATCH_MAX_GRID waves
+    mt = lib.dfm_kitti_match
+
+    def call(metric=0, second=1, aos=0, frames=2, c=3, l=3, k=2, ptrs=(p,) * 12, total_gt=4, total_dt=4, mo=p, thr=p,
+             nthr=p, tp=p, counts=p, sim=p, max_dt=4, ws=p, ws_bytes=4096):
+        return mt(metric, second, aos, frames, c, l, k, *ptrs, total_gt, total_dt, mo, thr, nthr, tp, counts, sim,
+                  max_dt, ws, ws_bytes, None)
+    assert call(metric=3) == -1 and b'metric' in lib.dfm_last_error()
+    assert call(frames=-1) == -1 and call(total_gt=-1) == -1 and call(max_dt=-1) == -1
+    assert call(counts=None) == -1 and b'counts' in lib.dfm_last_error()
+    assert call(aos=1, sim=None) == -1 and b'similarity' in lib.dfm_last_error()
+    assert call(second=0, tp=None) == -1 and b'tp_scores' in lib.dfm_last_error()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# host pieces
+# ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('scene', ku.SCENES)
+def test_vectorised_clean_data_equals_the_recorded_flags(z, ke, scene):
+    for m in range(3):
+        for l in range(3):
+            ig, idt = ke.clean_data_flags(z[f'{scene}/gt_name'], z[f'{scene}/gt_bbox'], z[f'{scene}/gt_occluded'],
+                                          z[f'{scene}/gt_truncated'], z[f'{scene}/dt_name'], z[f'{scene}/dt_bbox'],
+                                          m, l)
+            assert ig.dtype == np.int8 and idt.dtype == np.int8
+            assert np.array_equal(ig, z[f'{scene}/ignored_gt'][m, l]), (m, l)
+            assert np.array_equal(idt, z[f'{scene}/ignored_dt'][m, l]), (m, l)
+
+
+def test_clean_data_string_rules(ke):
+    names = np.array(['CAR', 'van', 'Person_sitting', 'pedestrian', 'DontCare', 'Cyclist', 'Car', 'Car'])
+    bbox = np.array([[0, 0, 50, 41]] * 6 + [[0, 0, 50, 40], [0, 0, 50, 40.5]], dtype=np.float64)
+    occ, trunc = np.zeros(8), np.zeros(8)
+    ig, idt = ke.clean_data_flags(names, bbox, occ, trunc, names, bbox, 0, 0)
+    assert ig.tolist() == [0, 1, -1, -1, -1, -1, 1, 0]             # height <= 40 ignores a ground truth ...
+    assert idt.tolist() == [0, -1, -1, -1, -1, -1, 0, 0]           # ... and only height < 40 a detection
+    ig, _ = ke.clean_data_flags(names, bbox, occ, trunc, names, bbox, 1, 0)
+    assert ig.tolist() == [-1, -1, 1, 0, -1, -1, -1, -1]
+    ig, _ = ke.clean_data_flags(names, bbox, np.array([1.0] + [0] * 7), np.array([0, 0, 0, 0, 0, 0, 0, 0.2]), names, bbox,
+                                0, 0)
+    assert ig[0] == 1 and ig[7] == 1                               # occlusion 1 > 0, truncation 0.2 > 0.15
+    with pytest.raises(ValueError, match='Car'):
+        ke.clean_data_flags(names, bbox, occ, trunc, names, bbox, 3, 0)
+
+
+@pytest.mark.parametrize('key', sorted(ku.VARIANTS))
+def test_host_get_thresholds_equals_the_recorded_ones(z, ke, key):
+    scene, variant = key
+    for m in range(3):
+        p = f'{scene}/{variant}/m{m}'
+        counts = z[f'{p}/first_counts']
+        off = np.concatenate([[0], np.cumsum(counts)])
+        thr, nthr = z[f'{p}/thresholds'].reshape(-1, 41), z[f'{p}/num_thresholds'].reshape(-1)
+        assert len(counts) == len(nthr)
+        for c in range(len(counts)):
+            got = ke.get_thresholds(z[f'{p}/first_scores'][off[c]:off[c + 1]], int(z[f'{p}/first_num_gt'][c]))
+            assert len(got) == nthr[c] <= 41 and np.array_equal(np.array(got), thr[c, :nthr[c]]), (m, c)
+
+
+def test_get_thresholds_walk_by_hand(ke):
+    # 4 ground truths, 3 matched scores: recalls 0.25, 0.5, 0.75; the sample points 0, 0.025, ... are taken by the
+    # first score until the midpoint rule lets the walk move on
+    t = ke.get_thresholds(np.array([0.2, 0.9, 0.5]), 4)
+    assert t[0] == 0.9 and t[-1] == 0.2 and sorted(set(t), reverse=True) == [0.9, 0.5, 0.2] and len(t) == 3
+    assert ke.get_thresholds(np.zeros(0), 4) == []
+    one = ke.get_thresholds(np.array([0.3]), 1)
+    assert one == [0.3]
+
+
+@pytest.mark.parametrize('key', sorted(ku.VARIANTS))
+def test_map_and_result_text_from_the_recorded_curves(z, ke, key):
+    scene, variant = key
+    classes, eval_types, alpha = ku.VARIANTS[key]
+    ints = [ku.CLASSES.index(c) for c in classes]
+    maps11, maps40 = {}, {}
+    for kind, m in (('bbox', 0), ('bev', 1), ('3d', 2)):
+        prec = z[f'{scene}/{variant}/m{m}/precision']
+        assert prec.shape == (len(classes), 3, 2, 41)
+        maps11[kind], maps40[kind] = ke.get_mAP11(prec), ke.get_mAP40(prec)
+    aos = alpha is None
+    if aos:
+        maps11['aos'] = ke.get_mAP11(z[f'{scene}/{variant}/m0/orientation'])
+        maps40['aos'] = ke.get_mAP40(z[f'{scene}/{variant}/m0/orientation'])
+    for tag, maps in (('mAP11', maps11), ('mAP40', maps40)):
+        for kind, got in maps.items():
+            assert np.array_equal(got, z[f'{scene}/{variant}/{tag}_{kind}']), (tag, kind)
+        assert (f'{scene}/{variant}/{tag}_aos' in z) == aos
+    text, ret = ke.format_results(ints, ku.kitti_min_overlaps()[:, :, ints], maps11, maps40, aos)
+    assert text == str(z[f'{scene}/{variant}/result'])
+    assert list(ret) == z[f'{scene}/{variant}/ret_keys'].tolist()
+    assert np.array_equal(np.array([float(v) for v in ret.values()]), z[f'{scene}/{variant}/ret_values'])
+
+
+def test_map_sums_the_reference_sample_points(ke):
+    prec = np.arange(41, dtype=np.float64)[None] / 100
+    assert np.isclose(ke.get_mAP11(prec)[0], sum(range(0, 41, 4)) / 11)
+    assert np.isclose(ke.get_mAP40(prec)[0], sum(range(1, 41)) / 40)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the two deviations, the kept error
+# ---------------------------------------------------------------------------------------------------------
+def fake_eval(ke, monkeypatch):
+    seen = []
+
+    def do_eval(gt_annos, dt_annos, current_classes, min_overlaps, eval_types):
+        seen.append(list(eval_types))
+        full = np.full((len(current_classes), 3, 2), 12.5)
+        have = {k: (full if k in eval_types else None) for k in ('bbox', 'bev', '3d', 'aos')}
+        return tuple(have[k] for k in ('bbox', 'bev', '3d', 'aos')) * 2
+    monkeypatch.setattr(ke, 'do_eval', do_eval)
+    monkeypatch.setattr(ke, '_device', lambda: None)
+    return seen
+
+
+def test_the_callers_eval_types_are_not_appended_to(ke, monkeypatch):
+    seen = fake_eval(ke, monkeypatch)
+    gt, dt = ku.annos('single')
+    mine = ['bbox', 'bev', '3d']
+    text, ret = ke.kitti_eval(gt, dt, ['Car'], mine)
+    assert mine == ['bbox', 'bev', '3d'] and seen == [['bbox', 'bev', '3d', 'aos']]
+    assert 'aos  AP11:12.50, 12.50, 12.50' in text
+    ke.kitti_eval(gt, dt, ['Car'])                                   # the default is no shared mutable list either
+    ke.kitti_eval(gt, dt, ['Car'])
+    assert seen[1] == seen[2] == ['bbox', 'bev', '3d', 'aos']
+
+
+def test_aos_is_evaluated_only_together_with_bbox(ke, monkeypatch):
+    seen = fake_eval(ke, monkeypatch)
+    gt, dt = ku.annos('single')
+    text, ret = ke.kitti_eval(gt, dt, ['Car', 'Cyclist'], ['bev', '3d'])    # a TypeError in the reference
+    assert seen == [['bev', '3d']] and 'aos' not in text and 'bbox' not in text
+    assert 'bev  AP40:12.5000' in text and 'KITTI/Overall_BEV_AP11_easy' in ret and 'KITTI/Car_2D_AP11_easy_strict' not in ret
+    with pytest.raises(AssertionError, match='bbox'):
+        ke.kitti_eval(gt, dt, ['Car'], ['bev', 'aos'])
+    with pytest.raises(AssertionError, match='at least one'):
+        ke.kitti_eval(gt, dt, ['Car'], [])
+
+
+def test_an_empty_first_ground_truth_frame_is_a_value_error(ke, monkeypatch):
+    fake_eval(ke, monkeypatch)
+    gt, dt = ku.annos('edge')
+    with pytest.raises(ValueError, match='empty'):
+        ke.kitti_eval(gt[1:], dt[1:], ['Car'])                       # frame 1 of the scene has no ground truth
+    for a in gt:
+        if len(a['alpha']):
+            a['alpha'][0] = -10                                      # invalid alphas first: the walk reaches frame 1
+    with pytest.raises(ValueError, match='IndexError in the reference'):
+        ke.kitti_eval(gt, dt, ['Car'])
+
+
+# ---------------------------------------------------------------------------------------------------------
+# offset tables, no CPU path, rebinding
+# ---------------------------------------------------------------------------------------------------------
+def test_bad_offset_tables_are_python_errors(ke, monkeypatch):
+    assert ke.check_offsets('t', [0, 2, 2, 5], 3, 5).dtype == np.int64
+    for table, frames, length, what in (([0, 2, 5], 3, 5, 'entries'), ([1, 2, 5], 2, 5, 'starts at 0'),
+                                        ([0, 3, 2, 5], 3, 5, 'monotone'), ([0, 2, 4], 2, 5, 'array length'),
+                                        ([0, 2, 6], 2, 5, 'array length'), ([0.0, 2.0, 5.0], 2, 5, 'integers'),
+                                        ([[0, 5]], 1, 5, 'entries')):
+        with pytest.raises(ValueError, match=what):
+            ke.check_offsets('t', table, frames, length)
+    # before any launch, and before the GPU is even looked for
+    monkeypatch.setattr(ke, '_device', lambda: pytest.fail('the GPU was asked for before the tables were checked'))
+    side = ke._side(bbox=np.zeros((5, 4)), n=5)
+    for dt_off, gt_off in (([0, 6], [0, 5]), ([0, 5], [0, 4]), ([0, 3, 2, 5], [0, 1, 2, 5]), ([0, 5], [0, 2, 5])):
+        with pytest.raises(ValueError):
+            ke._overlaps_concatenated(side, side, np.array(dt_off), np.array(gt_off), [0])
+    short = ke._side(bbox=np.zeros((4, 4)), n=5)
+    with pytest.raises(ValueError, match='rows'):
+        ke._overlaps_concatenated(short, side, np.array([0, 5]), np.array([0, 5]), [0])
+
+
+def test_there_is_no_cpu_path(ke, pkg, monkeypatch):
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
+    gt, dt = ku.annos('single')
+    boxes = np.array([[0.0, 10.0, 2.0, 4.0, 0.3]])
+    for call in (lambda: pkg.kitti_eval(gt, dt, ['Car']),
+                 lambda: pkg.rotate_iou_eval(boxes, boxes),
+                 lambda: pkg.image_box_overlap(np.array([[0.0, 0, 4, 4]]), np.array([[1.0, 1, 5, 5]])),
+                 lambda: pkg.d3_box_overlap(np.ones((1, 7)), np.ones((1, 7))),
+                 lambda: pkg.calculate_iou_partly(dt, gt, 1),
+                 lambda: pkg.eval_class(gt, dt, [0], [0, 1, 2], 0, ku.kitti_min_overlaps(1)),
+                 lambda: pkg.do_eval(gt, dt, [0], ku.kitti_min_overlaps(1), ['bbox'])):
+        with pytest.raises(RuntimeError, match='no CPU path'):
+            call()
+    assert pkg.rotate_iou_eval(np.zeros((0, 5)), boxes).shape == (0, 1)      # nothing to compute: no device needed
+    assert pkg.rotate_iou_eval(boxes, np.zeros((0, 5))).dtype == np.float32
+
+
+def test_patch_reference_rebinds_only_loaded_modules(pkg, ke):
+    integ = importlib.import_module('depth-from-motion_amd.integration')
+    names = ('mmdet3d', 'mmdet3d.core', 'mmdet3d.core.evaluation', 'mmdet3d.core.evaluation.kitti_utils',
+             'mmdet3d.core.evaluation.kitti_utils.eval', 'mmdet3d.core.evaluation.kitti_utils.rotate_iou')
+    before = {k: sys.modules.get(k) for k in names}
+    old = lambda *a, **k: 'reference'                                         # noqa: E731
+    try:
+        for k in names:
+            sys.modules.pop(k, None)
+        assert integ._patch_kitti_eval() == [] and not any(k in sys.modules for k in names)
+        for k in names:
+            m = types.ModuleType(k)
+            m.__path__ = []
+            sys.modules[k] = m
+        del sys.modules['mmdet3d.core']                                       # one holder that is NOT loaded
+        for k in names[2:5]:
+            sys.modules[k].kitti_eval = old
+        sys.modules[names[4]].kitti_eval_coco_style = old
+        sys.modules[names[5]].rotate_iou_gpu_eval = old
+        done = integ._patch_kitti_eval()
+        assert done == [f'{k}.kitti_eval' for k in (names[4], names[3], names[2])] + [f'{names[5]}.rotate_iou_gpu_eval']
+        for k in names[2:5]:
+            assert sys.modules[k].kitti_eval is pkg.kitti_eval
+        assert sys.modules[names[5]].rotate_iou_gpu_eval is pkg.rotate_iou_eval
+        assert sys.modules[names[4]].kitti_eval_coco_style is old and 'mmdet3d.core' not in sys.modules
+        assert not hasattr(sys.modules[names[5]], 'kitti_eval')
+        assert integ._patch_kitti_eval() == done                              # twice: the same report
+    finally:
+        for k, v in before.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
