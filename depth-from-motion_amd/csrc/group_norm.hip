@@ -163,18 +163,21 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T *__restrict__ x, 
             float f[VEC];
             load16<T>(xg + i, f);
             const int c = c0 + (int)(i / spatial);  // a vector never straddles channels
-            const float a = rstd * gamma[c], b = beta[c] - mean * a;
+            // gn_apply_cl_kernel's expression: two fused operations, one rounding each.  (beta - mean * a with the
+            // product rounded on its own is off by 2^-24 |mean a| -- where beta and mean * a cancel, more than the
+            // whole of x a + b is worth)
+            const float a = rstd * gamma[c], b = __builtin_fmaf(-mean, a, beta[c]);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
-                float v = f[k] * a + b;
+                float v = __builtin_fmaf(f[k], a, b);
                 f[k] = relu ? fmaxf(v, 0.0f) : v;
             }
             store16<T>(yg + i, f);
         } else {
             for (long long k = i; k < min(i + VEC, hi); ++k) {
                 const int c = c0 + (int)(k / spatial);
-                const float a = rstd * gamma[c], b = beta[c] - mean * a;
-                float v = elem<T>::load(xg[k]) * a + b;
+                const float a = rstd * gamma[c], b = __builtin_fmaf(-mean, a, beta[c]);
+                float v = __builtin_fmaf(elem<T>::load(xg[k]), a, b);
                 yg[k] = elem<T>::store(relu ? fmaxf(v, 0.0f) : v);
             }
         }

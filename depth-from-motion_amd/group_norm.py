@@ -66,8 +66,12 @@ class _GroupNormFn(torch.autograd.Function):
         else:
             launch('dfm_group_norm_fwd', n, c, spatial, groups, eps, DTYPES[x.dtype], int(relu and residual is None),
                    x, w32, b32, y, mean, rstd, WS, STREAM, ws_bytes=nbytes)
-        if residual is not None and not fused_res:
-            # a layout the kernel does not fuse (NCDHW, mismatched strides): plain torch ops
+        unfused = residual is not None and not fused_res
+        if unfused:
+            # a residual the kernel does not fuse (NCDHW, mismatched strides, another dtype, a broadcast one): plain
+            # torch ops behind the kernel, which ran without ReLU.  Their result may have another dtype (an fp32
+            # residual promotes a bf16 y) or layout than x, so it is never handed to a kernel as a ReLU mask: the
+            # backward applies the mask in torch as well and calls the kernel without ReLU
             y = y + residual
             if relu:
                 y = torch.relu_(y)
@@ -75,7 +79,7 @@ class _GroupNormFn(torch.autograd.Function):
         # (dfm_group_norm_bwd_channels_last_xmask) -- y is not kept for it, one activation less per layer in the graph
         xmask = bool(relu) and cl and residual is None and _XMASK
         ctx.save_for_backward(x, y if (relu and not xmask) else x, mean, rstd, w32, b32)
-        ctx.cfg = (groups, bool(relu), weight.dtype, bias.dtype, cl, residual is not None, xmask)
+        ctx.cfg = (groups, bool(relu), weight.dtype, bias.dtype, cl, residual is not None, xmask, unfused)
         if stats_out is not None:  # (mean, rstd) per (sample, group): HipBatchNorm3d's running statistics
             stats_out.append((mean, rstd))
         return y
@@ -83,12 +87,21 @@ class _GroupNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, y, mean, rstd, w32, b32 = ctx.saved_tensors
-        groups, relu, wdt, bdt, cl, has_res, xmask = ctx.cfg
+        groups, relu, wdt, bdt, cl, has_res, xmask, unfused = ctx.cfg
         lib = _capi.lib()
         device = x.device
         n, c = x.shape[:2]
         spatial = x.numel() // (n * c)
         want_res = has_res and ctx.needs_input_grad[7]
+        gres = None
+        if unfused:
+            # y = relu?(gn(x) + residual) in torch ops: the mask of that y (its own dtype and layout) in torch; what is
+            # left is the backward of a GroupNorm without ReLU.  The residual's gradient is the masked incoming one as
+            # it is (autograd sums it over a broadcast residual's extent and casts it to the residual's dtype)
+            if relu:
+                gy = gy * (y > 0).to(gy.dtype)
+                relu = False
+            gres = gy if want_res else None
         # (the channels-last kernels overwrite the parameter gradients: no zero fill -- 2 launches per layer saved)
         gw = (torch.empty if cl else torch.zeros)(c, dtype=torch.float32, device=device)
         gb = (torch.empty if cl else torch.zeros)(c, dtype=torch.float32, device=device)
@@ -99,24 +112,22 @@ class _GroupNormFn(torch.autograd.Function):
             fmt = torch.channels_last_3d if x.dim() == 5 else torch.channels_last
             gy = gy.to(x.dtype).contiguous(memory_format=fmt)
             gx = torch.empty_like(x)
-            gres = torch.empty_like(x) if want_res and relu else None
+            if want_res and relu:
+                gres = torch.empty_like(x)
             if xmask:
                 launch('dfm_group_norm_bwd_channels_last_xmask', n, c, spatial, groups, DTYPES[x.dtype], gy, x, mean,
                        rstd, w32, b32, gx, gw, gb, WS, STREAM, ws_bytes=nbytes)
                 return gx, gw.to(wdt), gb.to(bdt), None, None, None, None, None, None
-            launch('dfm_group_norm_bwd_channels_last', n, c, spatial, groups, DTYPES[x.dtype], int(relu), gy, x, y,
-                   mean, rstd, w32, gx, gres, gw, gb, WS, STREAM, ws_bytes=nbytes)
-            if want_res and not relu:
+            launch('dfm_group_norm_bwd_channels_last', n, c, spatial, groups, DTYPES[x.dtype], int(relu), gy, x,
+                   y if relu else None, mean, rstd, w32, gx, gres if relu else None, gw, gb, WS, STREAM,
+                   ws_bytes=nbytes)
+            if want_res and not relu and not unfused:
                 gres = gy
             return gx, gw.to(wdt), gb.to(bdt), None, None, None, None, gres, None
-        # y = relu?(gn(x) + residual): the residual's gradient is the incoming one behind the ReLU mask
-        gres = None
-        if want_res:
-            gres = gy * (y > 0).to(gy.dtype) if relu else gy
         gy = gy.contiguous().to(x.dtype)
         gx = torch.empty_like(x)
-        launch('dfm_group_norm_bwd', n, c, spatial, groups, DTYPES[x.dtype], int(relu), gy, x, y, mean, rstd, w32,
-               gx, gw, gb, WS, STREAM, ws_bytes=nbytes)
+        launch('dfm_group_norm_bwd', n, c, spatial, groups, DTYPES[x.dtype], int(relu), gy, x, y if relu else None,
+               mean, rstd, w32, gx, gw, gb, WS, STREAM, ws_bytes=nbytes)
         return gx, gw.to(wdt), gb.to(bdt), None, None, None, None, gres, None
 
 
