@@ -37,6 +37,7 @@ from .deform_conv import (ModulatedDeformConv2d, ModulatedDeformConv2dPack, defo
 from .voxelize import HardSimpleVFE, Voxelization, hard_voxelize, hard_voxelize_batch  # noqa: F401
 from .sparse_conv import (CustomSparseEncoder, SparseConv3d, SparseConvTensor, SparseSequential,  # noqa: F401
                           SubMConv3d, make_sparse_convmodule, sparse_conv_plan)
+from .sparse_train import enable_sparse_training  # noqa: F401
 from .kitti_eval import (bev_box_overlap, calculate_iou_partly, d3_box_overlap, do_eval, eval_class,  # noqa: F401
                          get_mAP11, get_mAP40, image_box_overlap, kitti_eval, rotate_iou_eval)
 from .data_geometry import (fold_ref_frame_matrices, select_ref_frames, stage_geometry,  # noqa: F401
@@ -59,6 +60,6 @@ __all__ = ['build_dfm_cost', 'plane_sweep_grid', 'point_sample', 'mv_feature_tra
            'HipATSSTargetMixin', 'deform_sample', 'modulated_deform_conv2d', 'ModulatedDeformConv2d',
            'ModulatedDeformConv2dPack', 'hard_voxelize', 'hard_voxelize_batch', 'Voxelization', 'HardSimpleVFE',
            'SparseConvTensor', 'SubMConv3d', 'SparseConv3d', 'SparseSequential', 'make_sparse_convmodule',
-           'CustomSparseEncoder', 'sparse_conv_plan', 'LidarTeacher', 'DfMLidarTeacherMixin', 'rotate_iou_eval',
+           'CustomSparseEncoder', 'sparse_conv_plan', 'enable_sparse_training', 'LidarTeacher', 'DfMLidarTeacherMixin', 'rotate_iou_eval',
            'bev_box_overlap', 'd3_box_overlap', 'image_box_overlap', 'calculate_iou_partly', 'eval_class', 'get_mAP11',
            'get_mAP40', 'do_eval', 'kitti_eval']

@@ -451,6 +451,33 @@ SPARSE_CONV_SIGNATURES = _sparse_conv_signatures()
 SPARSE_CONV_EXPORTS = tuple(SPARSE_CONV_SIGNATURES)
 
 
+SPARSE_WGRAD_CHUNK, SPARSE_BN_CHUNK = 256, 256  # DFM_SPARSE_WGRAD_CHUNK, DFM_SPARSE_BN_CHUNK
+
+
+def _sparse_train_signatures():
+    """the same for include/dfm_hip_sparse_train.h: the backward of the sparse convolutions and the BatchNorm over
+    live rows (tests/test_sparse_train.py checks this table against that header and the built library)"""
+    vp = fp = ctypes.c_void_p
+    ci, i32, i64, sz, f32 = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
+    s3 = ctypes.POINTER(ctypes.c_int32)
+    return {
+        'dfm_sparse_inverse_table': (ci, [fp, i32, i64, i64, fp, vp]),
+        'dfm_sparse_conv_wgrad_workspace_bytes': (sz, [i32, i32, i32, i64]),
+        'dfm_sparse_conv_wgrad': (ci, [i32, i32, i32, fp, i64, fp, fp, i64, fp, fp, vp, sz, fp, vp]),
+        'dfm_sparse_bn_workspace_bytes': (sz, [i64, i32]),
+        'dfm_sparse_bn_stats': (ci, [fp, fp, i64, i32, fp, vp, sz, fp, vp]),
+        'dfm_sparse_bn_apply': (ci, [fp, fp, i64, i32, fp, fp, fp, f32, i32, fp, vp]),
+        'dfm_sparse_bn_bwd_reduce': (ci, [fp, fp, fp, i64, i32, fp, fp, fp, f32, i32, fp, vp, sz, fp, vp]),
+        'dfm_sparse_bn_bwd_apply': (ci, [fp, fp, fp, i64, i32, fp, fp, fp, fp, f32, i32, fp, vp]),
+        'dfm_sparse_bn_running': (ci, [fp, i32, f32, fp, fp, vp]),
+        'dfm_sparse_dense_bwd': (ci, [fp, fp, i64, i32, i32, s3, fp, vp]),
+    }
+
+
+SPARSE_TRAIN_SIGNATURES = _sparse_train_signatures()
+SPARSE_TRAIN_EXPORTS = tuple(SPARSE_TRAIN_SIGNATURES)
+
+
 KITTI_SAMPLE_POINTS, KITTI_LDS_DETS = 41, 128  # DFM_KITTI_SAMPLE_POINTS, DFM_KITTI_LDS_DETS
 
 
@@ -487,7 +514,8 @@ def lib():
     h = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in (*SIGNATURES.items(), *BBOX_DECODE_SIGNATURES.items(),
                                       *ATSS_TARGET_SIGNATURES.items(), *DEFORM_CONV_SIGNATURES.items(),
-                                      *SPARSE_CONV_SIGNATURES.items(), *KITTI_EVAL_SIGNATURES.items()):
+                                      *SPARSE_CONV_SIGNATURES.items(), *SPARSE_TRAIN_SIGNATURES.items(),
+                                      *KITTI_EVAL_SIGNATURES.items()):
         fn = getattr(h, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = h

@@ -18,6 +18,10 @@ There is no torch path behind these classes: a setting the kernels do not cover 
 requires grad, ``block_type='basicblock'``, channel counts outside Cin in {3, 4, 8, ..., 64} / Cout in {16, 32, 64},
 a dtype other than fp32) raises ``MfmaPathError`` naming the setting under every fallback policy.  CPU tensors raise
 the package's "no CPU path" error.
+
+Training is opt-in: ``enable_sparse_training(module)`` (sparse_train.py) marks the layers of a tree, and a marked layer
+in training mode runs under autograd -- the convolution without an epilogue, a BatchNorm over the live rows, ``dense()``
+with a gathering backward.  Unmarked layers, and marked ones in eval mode under ``torch.no_grad()``, run as above.
 """
 import ctypes
 
@@ -86,6 +90,8 @@ class SparseConvTensor:
         self.num_rows = None    # a strided layer's output: its live row count, one int32 ON THE DEVICE
         self._status = None     # one int32 on the device, shared along a chain of layers
         self._table = None      # (keys, rows, capacity): the hash table over ``indices``, built once
+        self._train = False     # computed by a layer that enable_sparse_training marked, in training mode
+        self._live_rows = None  # one int32 on the device: every row at or past it has b < 0 (a sorted strided output)
 
     @property
     def spatial_size(self):
@@ -116,10 +122,11 @@ class SparseConvTensor:
             self._table = (keys, vals, capacity)
         return self._table
 
-    def _like(self, features):
+    def _like(self, features, train=False):
         """the same row set with new features: shares the tables and the status word"""
         out = SparseConvTensor(features, self.indices, self.spatial_shape, self.batch_size, self.grid)
         out.indice_dict, out._status, out._table = self.indice_dict, self.status(), self._table
+        out._train, out._live_rows = self._train or bool(train), self._live_rows
         return out
 
     def dense(self, channels_first=True):
@@ -127,6 +134,10 @@ class SparseConvTensor:
         ``(B, D, H, W, C)``).  No host wait."""
         require_gpu(self.features, 'features')
         c = self.features.shape[1]
+        if self._train and self.features.requires_grad and torch.is_grad_enabled():
+            from . import sparse_train
+            out = sparse_train.dense_rows(self)   # the same launch under autograd: the backward gathers the live rows
+            return out if channels_first else out.permute(0, 2, 3, 4, 1)
         out = torch.empty((self.batch_size, c, *self.spatial_shape), dtype=torch.float32, device=self.features.device)
         launch('dfm_sparse_dense', self.features, self.indices, self.features.shape[0], c, self.batch_size,
                _size3(self.spatial_shape), out, STREAM)
@@ -153,6 +164,7 @@ class _SparseConvBase(nn.Module):
     """parameters and checks shared by SubMConv3d and SparseConv3d: ``weight (kD, kH, kW, Cin, Cout)``, mmcv 1.x's
     layout, and an optional ``bias`` (the encoder builds none; a bias is folded into the epilogue's shift)"""
     subm = False
+    sparse_training = False   # enable_sparse_training(module) sets it: training mode runs under autograd
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
                  indice_key=None):
@@ -199,9 +211,14 @@ class _SparseConvBase(nn.Module):
         require_gpu(x.features, 'features')
         require_gpu(x.indices, 'indices')
         why = self.config_why_not()
-        if why is None and self.training:
+        if self.sparse_training:
+            if why is None and not self.training and torch.is_grad_enabled() and (
+                    x.features.requires_grad or any(p.requires_grad for p in self.parameters())):
+                why = ('eval mode with an input or a weight that needs a gradient (frozen-BN fine-tuning): '
+                       'enable_sparse_training covers training mode; evaluate under torch.no_grad()')
+        elif why is None and self.training:
             why = 'module in training mode (the sparse convolutions are forward only, eval only: call .eval())'
-        if why is None and (x.features.requires_grad and torch.is_grad_enabled()):
+        elif why is None and (x.features.requires_grad and torch.is_grad_enabled()):
             why = 'input that requires grad (there is no backward)'
         if why is None and x.features.dtype != torch.float32:
             why = f'feature dtype {x.features.dtype} (the kernels are fp32)'
@@ -227,7 +244,17 @@ class _SparseConvBase(nn.Module):
             shift = shift + self.bias.detach().float() * scale
         return scale, shift
 
-    def _run(self, x, nbr, out_indices, norm, relu):
+    def _run(self, x, nbr, out_indices, norm, relu, inverse=None, live_rows=None):
+        """the output rows: today's fused launch, or -- a layer marked by ``enable_sparse_training``, in training
+        mode -- the convolution under autograd, without an epilogue (``inverse()``: the inverse table, built when the
+        input needs a gradient; ``live_rows``: the device count the output's live rows are the first of, or None)"""
+        if self.sparse_training and self.training:
+            if norm is not None or relu:
+                raise MfmaPathError(f'{type(self).__name__}({self.in_channels}->{self.out_channels}): a fused '
+                                    'BatchNorm / ReLU epilogue in training mode -- enable_sparse_training must mark '
+                                    'the SparseSequential around the convolution as well (call it on the whole tree)')
+            from . import sparse_train
+            return sparse_train.conv_rows(self, x, nbr, out_indices, inverse, live_rows)
         scale, shift = self._epilogue(norm)
         taps = self.kernel_size[0] * self.kernel_size[1] * self.kernel_size[2]
         out_rows = out_indices.shape[0]
@@ -260,10 +287,17 @@ class SubMConv3d(_SparseConvBase):
             nbr = torch.empty((27, rows), dtype=torch.int32, device=x.indices.device)
             launch('dfm_sparse_subm_neighbours', x.indices, rows, x.batch_size, _size3(x.spatial_shape), keys, vals,
                    capacity, nbr, STREAM)
-            entry = (x.indices, nbr)
+            entry = [x.indices, nbr, None]   # the third: the inverse table, made by the first backward-capable call
             if self.indice_key is not None:
                 x.indice_dict[self.indice_key] = entry
-        return x._like(self._run(x, entry[1], x.indices, norm, relu))
+
+        def inverse():   # inv[k] = nbr[26 - k]: no kernel
+            if entry[2] is None:
+                entry[2] = entry[1].flip(0)
+            return entry[2]
+
+        return x._like(self._run(x, entry[1], x.indices, norm, relu, inverse, x._live_rows),
+                       self.sparse_training and self.training)
 
 
 @register_module(on_path=False)
@@ -275,21 +309,41 @@ class SparseConv3d(_SparseConvBase):
     def forward_fused(self, x, norm=None, relu=False):
         self._check(x)
         if self.conv1x1:
-            return x._like(self._run(x, None, x.indices, norm, relu))
+            return x._like(self._run(x, None, x.indices, norm, relu, None, x._live_rows),
+                           self.sparse_training and self.training)
         rows, device = x.indices.shape[0], x.indices.device
         d = _conv_desc(x.batch_size, x.spatial_shape, self.kernel_size, self.stride, self.padding, False)
         plan = _capi.SparseConvPlan()
         _capi.check(_capi.lib().dfm_sparse_conv_out_shape(ctypes.byref(d), rows, ctypes.byref(plan)))
         keys, vals, capacity = x.table()
         assert capacity == plan.in_capacity
+        sorted_count = None
         out_keys = torch.full((plan.out_capacity,), -1, dtype=torch.int64, device=device)
         out_indices = torch.full((plan.out_rows, 4), -1, dtype=torch.int32, device=device)
         count = torch.zeros((1,), dtype=torch.int32, device=device)
         launch('dfm_sparse_conv_out_rows', d, x.indices, rows, out_keys, out_indices, count, x.status(), STREAM)
+        if self.sparse_training and self.training:
+            # the atomic counter numbers the rows in arrival order; the sums over rows of the training kernels (batch
+            # statistics, weight gradient) are bit-reproducible only over a fixed order: ascending (b, z, y, x), the
+            # rows that do not exist last (a device sort, as the voxelization's; no host wait)
+            i = out_indices.long()
+            key = ((i[:, 0] * plan.out_size[0] + i[:, 1]) * plan.out_size[1] + i[:, 2]) * plan.out_size[2] + i[:, 3]
+            key = torch.where(i[:, 0] >= 0, key, torch.full_like(key, torch.iinfo(torch.int64).max))
+            out_indices = out_indices[torch.argsort(key)].contiguous()
+            sorted_count = count
         nbr = torch.empty((plan.taps, plan.out_rows), dtype=torch.int32, device=device)
         launch('dfm_sparse_conv_neighbours', d, out_indices, rows, keys, vals, nbr, STREAM)
-        out = SparseConvTensor(self._run(x, nbr, out_indices, norm, relu), out_indices, list(plan.out_size),
-                               x.batch_size, x.grid)
+
+        def inverse():   # kept beside the forward table under the layer's indice_key
+            inv = torch.full((plan.taps, rows), -1, dtype=torch.int32, device=device)
+            launch('dfm_sparse_inverse_table', nbr, plan.taps, plan.out_rows, rows, inv, STREAM)
+            if self.indice_key is not None:
+                x.indice_dict[self.indice_key] = [x.indices, nbr, inv]
+            return inv
+
+        out = SparseConvTensor(self._run(x, nbr, out_indices, norm, relu, inverse, sorted_count), out_indices,
+                               list(plan.out_size), x.batch_size, x.grid)
+        out._train, out._live_rows = x._train or (self.sparse_training and self.training), sorted_count
         out.indice_dict, out._status = x.indice_dict, x.status()
         out.num_rows = count
         return out
@@ -300,12 +354,26 @@ class SparseSequential(nn.Sequential):
     convolution followed by an eval-mode ``BatchNorm1d`` and / or a ``ReLU`` runs as ONE launch: both are the
     convolution's epilogue, on active rows only."""
 
+    sparse_training = False   # enable_sparse_training(module) sets it
+
     def forward(self, input):
         mods = list(self)
         i = 0
         while i < len(mods):
             m = mods[i]
-            if isinstance(m, _SparseConvBase):
+            if isinstance(m, _SparseConvBase) and self.sparse_training and m.sparse_training and m.training:
+                # a marked chain in training mode: the convolution without an epilogue, then the BatchNorm over the
+                # live rows with the ReLU that follows it, all three under autograd (sparse_train.py)
+                from . import sparse_train
+                input, i = m.forward_fused(input, None, False), i + 1
+                if i < len(mods) and isinstance(mods[i], (nn.BatchNorm1d, nn.SyncBatchNorm)):
+                    norm, i = mods[i], i + 1
+                    relu = i < len(mods) and isinstance(mods[i], nn.ReLU)
+                    i += int(relu)
+                    out = input._like(sparse_train.batch_norm_rows(input.features, input.indices, norm, relu,
+                                                                   input._live_rows), True)
+                    out.num_rows, input = input.num_rows, out
+            elif isinstance(m, _SparseConvBase):
                 norm, relu, j = None, False, i + 1
                 if j < len(mods) and isinstance(mods[j], nn.BatchNorm1d):
                     norm, j = mods[j], j + 1
@@ -328,7 +396,9 @@ def _build_norm_1d(norm_cfg, num_features):
     cfg.pop('requires_grad', None)
     if kind not in ('BN1d', 'SyncBN', 'BN'):
         raise MfmaPathError(f'norm_cfg type {kind!r}: the sparse encoder builds BatchNorm1d (BN1d | SyncBN), eval only')
-    return nn.BatchNorm1d(num_features, **cfg)   # SyncBN in eval mode is a BatchNorm1d
+    bn = nn.BatchNorm1d(num_features, **cfg)   # SyncBN in eval mode is a BatchNorm1d
+    bn.cross_rank = kind == 'SyncBN'   # training (sparse_train.py) refuses it in a group of more than one rank
+    return bn
 
 
 _CONV_TYPES = dict(SubMConv3d=SubMConv3d, SparseConv3d=SparseConv3d)
@@ -359,7 +429,8 @@ class CustomSparseEncoder(nn.Module):
     """The reference's ``CustomSparseEncoder`` (middle_encoders/sparse_encoder.py:217-440): same constructor, same
     state-dict keys (``conv_input.0.weight``, ``conv_input.1.*``, ``encoder_layers.encoder_layer2.0.0.weight``, ...,
     ``conv_out.0.weight``), ``forward(voxel_features, coors, batch_size)`` -> ``spatial_features (B, C * D, H, W)`` or,
-    with ``output_volume_feat``, ``(spatial_features, volume_features (B, C, D, H, W))``.  Forward only, eval only; no
+    with ``output_volume_feat``, ``(spatial_features, volume_features (B, C, D, H, W))``.  Forward only, eval only
+    (under autograd, with the same return values, once ``enable_sparse_training`` has marked it: sparse_train.py); no
     host wait.  ``coors`` may carry rows with batch index -1 (``hard_voxelize_batch``'s padding): they do not exist."""
 
     def __init__(self, in_channels, sparse_shape, order=('conv', 'norm', 'act'),

@@ -1376,6 +1376,9 @@ DFM_API int dfm_spp_tail_fwd(const dfm_spp_desc *desc, const void *const *pooled
 #include "dfm_hip_deform_conv.h"
 /* the LiDAR teacher: hard voxelization (dfm_voxel_*) and sparse 3-D convolutions (dfm_sparse_*): likewise */
 #include "dfm_hip_sparse_conv.h"
+/* training the teacher's sparse encoder: inverse tables, the weight gradient, BatchNorm over live rows, dense()
+ * backward (dfm_sparse_inverse_table, dfm_sparse_conv_wgrad, dfm_sparse_bn_*, dfm_sparse_dense_bwd): likewise */
+#include "dfm_hip_sparse_train.h"
 /* KITTI evaluation: same-frame overlaps and the AP / AOS matching (dfm_kitti_*): likewise */
 #include "dfm_hip_kitti_eval.h"
 
