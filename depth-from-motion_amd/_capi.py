@@ -1,4 +1,9 @@
-"""ctypes binding of lib/libdfm_hip.so (C ABI: include/dfm_hip.h).
+"""ctypes binding of lib/libdfm_hip.so (C ABI: include/dfm_hip.h and the headers it includes).
+
+One hand-written table, ``_BINDING``, keyed by header file like the declarations it mirrors; ``STRUCTS`` names the
+ctypes class of every descriptor struct.  Nothing is parsed here: tests/test_capi_binding.py parses the headers and
+holds this module against them -- names, return types, every parameter's type, struct layouts, constants -- and
+against the built library.
 
 Loud by design: a missing library is an ImportError with the build command,
 never a silent fallback.
@@ -220,10 +225,22 @@ class SparseConvPlan(ctypes.Structure):
                 ('in_capacity', ctypes.c_int64), ('out_capacity', ctypes.c_int64)]
 
 
+# C struct name -> its ctypes mirror: every descriptor struct the headers define
+STRUCTS = {
+    'dfm_sweep_desc': SweepDesc, 'dfm_sweep_opts': SweepOpts, 'dfm_mv_desc': MvDesc, 'dfm_f2v_desc': F2vDesc,
+    'dfm_spp_desc': SppDesc, 'dfm_vs_desc': VsDesc, 'dfm_vs_mv_desc': VsMvDesc,
+    'dfm_depth_loss_desc': DepthLossDesc, 'dfm_imitation_desc': ImitationDesc, 'dfm_conv3d_desc': Conv3dDesc,
+    'dfm_conv3d_wgrad_desc': Conv3dWgradDesc, 'dfm_anchor_target_desc': AnchorTargetDesc,
+    'dfm_anchor_head_desc': AnchorHeadDesc, 'dfm_atss_target_desc': AtssTargetDesc, 'dfm_deform_desc': DeformDesc,
+    'dfm_voxel_desc': VoxelDesc, 'dfm_sparse_conv_desc': SparseConvDesc, 'dfm_sparse_conv_plan': SparseConvPlan,
+}
+
 # DFM_SPARSE_STATUS_*: bits of the device status word of the sparse-convolution index kernels
 SPARSE_STATUS = {1: 'a hash-table probe loop ran out of slots', 2: 'two input rows share one coordinate (duplicate)',
                  4: 'more output rows than the row bound', 8: 'a coordinate outside the grid or the batch'}
 SPARSE_MAX_TAPS = 27  # DFM_SPARSE_MAX_TAPS
+SPARSE_WGRAD_CHUNK, SPARSE_BN_CHUNK = 256, 256  # DFM_SPARSE_WGRAD_CHUNK, DFM_SPARSE_BN_CHUNK
+KITTI_SAMPLE_POINTS, KITTI_LDS_DETS = 41, 128  # DFM_KITTI_SAMPLE_POINTS, DFM_KITTI_LDS_DETS
 
 DFM_ERR_UNSUPPORTED = -2  # include/dfm_hip.h
 BOX_NMS_MAX_N = 16384  # DFM_BOX_NMS_MAX_N
@@ -233,270 +250,228 @@ class DfmHipError(RuntimeError):
     pass
 
 
-def _signatures():
-    """name -> (restype, argtypes) of every symbol include/dfm_hip.h declares: the whole binding (tests/
-    test_capi_symbols.py and tests/test_launch.py check it against the header -- names, parameter counts, void
-    returns -- and against the built library).  vp: a ``void *`` of the header (dtype-dependent memory, the stream),
-    fp: a typed pointer (``float *``, ``int32_t *``, ...); both are c_void_p here."""
+def _table(*rows):
+    """(name, restype, argtypes) rows of one header -> {name: (restype, argtypes)}; a name bound twice raises (a dict
+    literal would keep the last one and say nothing)"""
+    table = {}
+    for name, restype, argtypes in rows:
+        if name in table:
+            raise ValueError(f'{name} is bound twice in one header')
+        table[name] = (restype, argtypes)
+    return table
+
+
+def _binding():
+    """header file -> name -> (restype, argtypes) of every symbol that header declares: the whole binding, written by
+    hand in the headers' order.  vp: a ``void *`` of the header (dtype-dependent memory, the stream), fp: a typed
+    pointer (``float *``, ``int32_t *``, ...); both are c_void_p here.  A pointer to a descriptor struct is a
+    POINTER to its class in STRUCTS."""
     P = ctypes.POINTER
     vp = fp = ctypes.c_void_p
     ci, i32, i64, sz, f32, f64 = (ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float,
                                   ctypes.c_double)
     dp, op, mp, f2p, spp, pp = P(SweepDesc), P(SweepOpts), P(MvDesc), P(F2vDesc), P(SppDesc), P(vp)
     vsp, vmp, cp, wp, lp = P(VsDesc), P(VsMvDesc), P(Conv3dDesc), P(Conv3dWgradDesc), P(DepthLossDesc)
-    ip, atp = P(ImitationDesc), P(AnchorTargetDesc)
+    ip, atp, ahp, adp, ddp = P(ImitationDesc), P(AnchorTargetDesc), P(AnchorHeadDesc), P(AtssTargetDesc), P(DeformDesc)
+    vdp, sdp, plp, i32p, i64p = P(VoxelDesc), P(SparseConvDesc), P(SparseConvPlan), P(i32), P(i64)
     return {
-        'dfm_version': (ci, []),
-        'dfm_last_error': (ctypes.c_char_p, []),
-        'dfm_profile_begin': (ci, [ci]),
-        'dfm_profile_end': (ci, [P(f64), P(ci)]),
-        'dfm_camera_prepare': (ci, [fp, i32, i32, i32, fp, fp, vp]),
-        'dfm_plane_sweep_workspace_bytes': (sz, [dp]),
-        'dfm_plane_sweep_fwd': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
-        'dfm_plane_sweep_cl_workspace_bytes': (sz, [dp]),
-        'dfm_plane_sweep_fwd_channels_last': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
-        'dfm_plane_sweep_fwd_nhwc': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
-        'dfm_plane_sweep_fwd_from_nhwc': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
-        'dfm_plane_sweep_bwd': (ci, [dp, vp, fp, fp, fp, fp, fp, fp, vp]),
-        'dfm_plane_sweep_grid': (ci, [dp, i32, fp, fp, fp, fp, fp, fp, vp]),
-        'dfm_plane_sweep_last_kernel': (ci, []),
-        'dfm_plane_sweep_bwd_last_kernel': (ci, []),
-        'dfm_plane_sweep_fwd_opts': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp, op]),
-        'dfm_plane_sweep_bwd_opts': (ci, [dp, vp, fp, fp, fp, fp, fp, fp, vp, op]),
-        'dfm_plane_sweep_bwd_channels_last': (ci, [dp, vp, fp, fp, fp, fp, fp, fp, vp, sz, vp]),
-        'dfm_plane_sweep_bwd_cur_nhwc': (ci, [dp, vp, fp, fp, fp, fp, fp, vp]),
-        'dfm_plane_sweep_bwd_prev_gather_workspace_bytes': (sz, [dp]),
-        'dfm_plane_sweep_bwd_prev_gather': (ci, [dp, vp, fp, fp, fp, fp, fp, vp, sz, vp]),
-        'dfm_plane_sweep_bwd_gather': (ci, [dp, i32, vp, i32, fp, fp, fp, fp, fp, i32, vp, sz, vp]),
-        'dfm_plane_sweep_autotune': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp, op]),
-        'dfm_plane_sweep_tuning': (ci, [dp, op]),
-        'dfm_plane_sweep_reset_tuning': (None, []),
-        'dfm_store_probe': (ci, [vp, i32, i32, i64, i32, i32, vp]),
-        'dfm_clock_probe': (ci, [vp, i32, vp]),
-        'dfm_point_sample_mv_workspace_bytes': (sz, [mp]),
-        'dfm_point_sample_mv_fwd': (ci, [mp, vp, fp, fp, fp, vp, vp, vp, sz, vp]),
-        'dfm_frustum_to_voxel_workspace_bytes': (sz, [f2p]),
-        'dfm_frustum_to_voxel_fwd': (ci, [f2p, vp, vp, vp, fp, fp, vp, vp, sz, vp]),
-        'dfm_depth_head_fwd': (ci, [i32, i32, i32, i32, i32, i32, vp, fp, vp, vp, vp, vp]),
-        'dfm_depth_head_stats_fwd': (ci, [i32, i32, i32, i32, i32, i32, vp, fp, fp, fp, vp, vp]),
-        'dfm_frustum_to_voxel_fused_fwd': (ci, [f2p, vp, vp, fp, fp, i32, vp, fp, fp, vp, vp, sz, vp]),
-        'dfm_frustum_to_voxel_bwd_workspace_bytes': (sz, [f2p]),
-        'dfm_frustum_to_voxel_bwd': (ci, [f2p, vp, vp, fp, fp, fp, fp, vp, sz, vp]),
-        'dfm_frustum_to_voxel_fused_bwd': (ci, [f2p, vp, vp, fp, fp, i32, fp, fp, fp, fp, vp, sz, vp]),
-        'dfm_frustum_to_voxel_bwd_gather_workspace_bytes': (sz, [f2p]),
-        'dfm_frustum_to_voxel_bwd_gather': (ci, [f2p, vp, vp, vp, fp, fp, i32, fp, P(f32), fp, fp, fp, vp, sz, vp]),
-        'dfm_frustum_to_voxel_bwd_gather_cl': (ci, [f2p, vp, vp, vp, fp, fp, i32, fp, P(f32), fp, vp, fp, vp, sz, vp]),
-        'dfm_point_sample_mv_fwd_batched': (ci, [vp, i32, vp, fp, i32, fp, fp, vp, vp, vp]),
-        'dfm_point_sample_mv_bwd_workspace_bytes': (sz, [mp]),
-        'dfm_point_sample_mv_bwd': (ci, [mp, vp, fp, fp, fp, fp, vp, sz, vp]),
-        'dfm_depth_head_bwd': (ci, [i32, i32, i32, i32, i32, i32, vp, fp, vp, vp, vp, fp, vp]),
-        'dfm_sweep_conv_weight_bytes': (sz, []),
-        'dfm_sweep_conv_pack_weights': (ci, [vp, vp, i32, vp, vp]),
-        'dfm_sweep_conv_stats_splits': (ci, [dp, i32]),
-        'dfm_sweep_conv_fwd': (ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, vp, fp, fp, i32, vp]),
-        'dfm_cost_gate_weight_bytes': (sz, [i32]),
-        'dfm_cost_gate_pack_weights': (ci, [vp, i32, i32, vp, vp]),
-        'dfm_cost_gate_fwd': (ci, [i32, i32, i64, i32, vp, vp, vp, vp, vp]),
-        'dfm_conv3d_k3_c32_weight_bytes': (sz, []),
-        'dfm_conv3d_k3_c32_pack_weights': (ci, [vp, i32, i32, i32, i32, vp, vp]),
-        'dfm_conv3d_k3_c32_stats_splits': (ci, [i32, i32, i32, i32, i32]),
-        'dfm_conv3d_k3_c32_fwd': (ci, [i32, i32, i32, i32, vp, vp, fp, vp, i32, i32, i32, fp, vp]),
-        'dfm_conv3d_k3_c32_fwd_strided': (ci, [i32, i32, i32, i32, vp, i32, vp, fp, vp, i32, i32, i32, fp, vp]),
-        'dfm_conv3d_k3_c32_fwd_slices': (ci, [i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp]),
-        'dfm_conv3d_k3_c32_to1_fwd': (ci, [i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]),
-        'dfm_group_norm_coefficients': (ci, [i32, i32, i32, f32, vp, i32, vp, vp, vp, vp]),
-        'dfm_conv3d_to1_norm_fwd': (ci, [i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp]),
-        'dfm_conv3d_to1_bwd_data': (ci, [i32, i32, i32, i32, vp, vp, i32, vp, vp]),
-        'dfm_conv3d_to1_wgrad_workspace_bytes': (sz, []),
-        'dfm_conv3d_to1_wgrad': (ci, [i32, i32, i32, i32, vp, vp, vp, i32, vp, sz, vp]),
-        'dfm_bilinear_resize_bwd_nhwc': (ci, [i32, i32, i32, i32, i32, i32, i32, vp, vp, fp, i32, vp, fp, i32, vp, vp]),
-        'dfm_depth_pool_fwd': (ci, [i64, i32, i64, i32, vp, vp, vp]),
-        'dfm_depth_pool_bwd': (ci, [i64, i32, i64, i32, vp, vp, vp]),
-        'dfm_cost_gate_mfma_weight_bytes': (sz, [i32]),
-        'dfm_cost_gate_mfma_pack_weights': (ci, [vp, i32, i32, vp, vp]),
-        'dfm_cost_gate_mfma_fwd': (ci, [i32, i32, i64, vp, vp, vp, vp, vp]),
-        'dfm_conv3d_g_weight_bytes': (sz, [i32, i32]),
-        'dfm_conv3d_g_pack_weights': (ci, [vp, i32, i32, i32, i32, i32, vp, vp]),
-        'dfm_conv3d_g_pack_weights_2d': (ci, [vp, i32, i32, i32, i32, i32, vp, vp]),
-        'dfm_conv3d_g_fwd': (ci, [cp, vp, vp, fp, fp, vp, vp, vp]),
-        'dfm_conv3d_g_fwd_f32': (ci, [cp, vp, vp, vp, vp, vp]),
-        'dfm_conv3d_g_plan': (ci, [cp, P(i64)]),
-        'dfm_conv3d_wgrad_workspace_bytes': (sz, [wp]),
-        'dfm_conv3d_wgrad': (ci, [wp, vp, vp, fp, vp, sz, vp]),
-        'dfm_conv3d_wgrad_to': (ci, [wp, vp, vp, vp, i32, vp, sz, vp]),
-        'dfm_depth_loss_fwd': (ci, [lp, vp, fp, fp, fp, vp, vp]),
-        'dfm_depth_loss_bwd': (ci, [lp, vp, fp, fp, fp, vp, vp]),
-        'dfm_depth_loss_fused_fwd': (ci, [lp, vp, i32, fp, fp, fp, vp, vp]),
-        'dfm_depth_loss_fused_bwd': (ci, [lp, vp, i32, fp, fp, fp, fp, vp]),
-        'dfm_voxel_sample_fwd': (ci, [vsp, vp, fp, vp, vp]),
-        'dfm_voxel_sample_bwd': (ci, [vsp, vp, fp, fp, vp]),
-        'dfm_voxel_sample_mv_fwd': (ci, [vmp, fp, vp, fp, vp, vp]),
-        'dfm_voxel_sample_mv_bwd': (ci, [vmp, fp, vp, fp, fp, vp]),
-        'dfm_spp_tail_workspace_bytes': (sz, [spp]),
-        'dfm_spp_tail_fwd': (ci, [spp, pp, pp, pp, pp, pp, vp, vp, sz, vp]),
-        'dfm_group_norm_workspace_bytes': (sz, [i32, i32, i64, i32]),
-        'dfm_group_norm_fwd': (ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, fp, vp, sz, vp]),
-        'dfm_group_norm_fwd_channels_last': (ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, fp, vp, sz,
-            vp]),
-        'dfm_group_norm_apply_channels_last': (ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, fp, fp, i32,
-            vp, sz, vp]),
-        'dfm_group_norm_fwd_channels_last_res': (ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, vp, fp, fp, vp,
-            sz, vp]),
-        'dfm_group_norm_apply_channels_last_res': (ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, vp, fp, fp,
-            fp, i32, vp, sz, vp]),
-        'dfm_group_norm_bwd': (ci, [i32, i32, i64, i32, i32, i32, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp, sz, vp]),
-        'dfm_group_norm_bwd_channels_last': (ci, [i32, i32, i64, i32, i32, i32, vp, vp, vp, fp, fp, fp, vp, vp, fp, fp,
-            vp, sz, vp]),
-        'dfm_group_norm_bwd_channels_last_xmask': (ci, [i32, i32, i64, i32, i32, vp, vp, fp, fp, fp, fp, vp, fp, fp, vp,
-            sz, vp]),
-        'dfm_batch_norm_workspace_bytes': (sz, [i32, i64]),
-        'dfm_batch_norm_stats_channels_last': (ci, [i32, i64, i32, vp, fp, vp, sz, vp]),
-        'dfm_batch_norm_apply_gathered_channels_last': (ci, [i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, vp, fp,
-            fp, fp, vp]),
-        'dfm_batch_norm_bwd_reduce_channels_last': (ci, [i32, i64, i32, i32, vp, vp, vp, fp, fp, fp, fp, fp, vp, sz,
-            vp]),
-        'dfm_batch_norm_bwd_apply_channels_last': (ci, [i32, i64, i32, i32, vp, vp, vp, fp, fp, fp, fp, fp, fp, vp, vp,
-            vp, sz, vp]),
-        'dfm_imitation_loss_workspace_bytes': (sz, [ip]),
-        'dfm_imitation_loss_fwd': (ci, [ip, vp, vp, fp, fp, fp, fp, fp, vp, vp, vp, sz, vp]),
-        'dfm_imitation_loss_bwd': (ci, [ip, vp, vp, vp, fp, fp, fp, vp, vp]),
-        'dfm_box_nms_workspace_bytes': (sz, [i32, i32]),
-        'dfm_box_nms_rotated': (ci, [fp, i32, i32, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp]),
-        'dfm_box_nms_aligned': (ci, [fp, i32, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp]),
-        'dfm_box_iou_rotated': (ci, [fp, i32, fp, i32, i32, fp, vp]),
-        'dfm_diff_iou_rotated': (ci, [fp, fp, i32, i32, fp, fp, fp, vp]),
-        'dfm_iou3d_loss_from_deltas': (ci, [fp, fp, fp, vp, i32, i32, i32, fp, fp, vp]),
-        'dfm_nearest_bev_overlaps': (ci, [fp, i32, fp, i32, i32, i32, i32, fp, vp]),
-        'dfm_anchor_target_workspace_bytes': (sz, [i32, i32]),
-        'dfm_anchor_target_3d': (ci, [atp, fp, fp, vp, P(i32), vp, fp, fp, fp, vp, fp, vp, vp, sz, vp]),
+        'dfm_hip.h': _table(
+            ('dfm_version', ci, []),
+            ('dfm_last_error', ctypes.c_char_p, []),
+            ('dfm_profile_begin', ci, [ci]),
+            ('dfm_profile_end', ci, [P(f64), P(ci)]),
+            ('dfm_camera_prepare', ci, [fp, i32, i32, i32, fp, fp, vp]),
+            ('dfm_plane_sweep_workspace_bytes', sz, [dp]),
+            ('dfm_plane_sweep_fwd', ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
+            ('dfm_plane_sweep_cl_workspace_bytes', sz, [dp]),
+            ('dfm_plane_sweep_fwd_channels_last', ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
+            ('dfm_plane_sweep_fwd_nhwc', ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
+            ('dfm_plane_sweep_fwd_from_nhwc', ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
+            ('dfm_plane_sweep_bwd', ci, [dp, vp, fp, fp, fp, fp, fp, fp, vp]),
+            ('dfm_plane_sweep_grid', ci, [dp, i32, fp, fp, fp, fp, fp, fp, vp]),
+            ('dfm_plane_sweep_last_kernel', ci, []),
+            ('dfm_plane_sweep_bwd_last_kernel', ci, []),
+            ('dfm_plane_sweep_fwd_opts', ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp, op]),
+            ('dfm_plane_sweep_bwd_opts', ci, [dp, vp, fp, fp, fp, fp, fp, fp, vp, op]),
+            ('dfm_plane_sweep_bwd_channels_last', ci, [dp, vp, fp, fp, fp, fp, fp, fp, vp, sz, vp]),
+            ('dfm_plane_sweep_bwd_cur_nhwc', ci, [dp, vp, fp, fp, fp, fp, fp, vp]),
+            ('dfm_plane_sweep_bwd_prev_gather_workspace_bytes', sz, [dp]),
+            ('dfm_plane_sweep_bwd_prev_gather', ci, [dp, vp, fp, fp, fp, fp, fp, vp, sz, vp]),
+            ('dfm_plane_sweep_bwd_gather', ci, [dp, i32, vp, i32, fp, fp, fp, fp, fp, i32, vp, sz, vp]),
+            ('dfm_plane_sweep_autotune', ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, sz, vp, op]),
+            ('dfm_plane_sweep_tuning', ci, [dp, op]),
+            ('dfm_plane_sweep_reset_tuning', None, []),
+            ('dfm_store_probe', ci, [vp, i32, i32, i64, i32, i32, vp]),
+            ('dfm_clock_probe', ci, [vp, i32, vp]),
+            ('dfm_point_sample_mv_workspace_bytes', sz, [mp]),
+            ('dfm_point_sample_mv_fwd', ci, [mp, vp, fp, fp, fp, vp, vp, vp, sz, vp]),
+            ('dfm_frustum_to_voxel_workspace_bytes', sz, [f2p]),
+            ('dfm_frustum_to_voxel_fwd', ci, [f2p, vp, vp, vp, fp, fp, vp, vp, sz, vp]),
+            ('dfm_depth_head_fwd', ci, [i32, i32, i32, i32, i32, i32, vp, fp, vp, vp, vp, vp]),
+            ('dfm_depth_head_stats_fwd', ci, [i32, i32, i32, i32, i32, i32, vp, fp, fp, fp, vp, vp]),
+            ('dfm_frustum_to_voxel_fused_fwd', ci, [f2p, vp, vp, fp, fp, i32, vp, fp, fp, vp, vp, sz, vp]),
+            ('dfm_frustum_to_voxel_bwd_workspace_bytes', sz, [f2p]),
+            ('dfm_frustum_to_voxel_bwd', ci, [f2p, vp, vp, fp, fp, fp, fp, vp, sz, vp]),
+            ('dfm_frustum_to_voxel_fused_bwd', ci, [f2p, vp, vp, fp, fp, i32, fp, fp, fp, fp, vp, sz, vp]),
+            ('dfm_frustum_to_voxel_bwd_gather_workspace_bytes', sz, [f2p]),
+            ('dfm_frustum_to_voxel_bwd_gather', ci, [f2p, vp, vp, vp, fp, fp, i32, fp, P(f32), fp, fp, fp, vp, sz,
+                                                     vp]),
+            ('dfm_frustum_to_voxel_bwd_gather_cl', ci, [f2p, vp, vp, vp, fp, fp, i32, fp, P(f32), fp, vp, fp, vp, sz,
+                                                        vp]),
+            ('dfm_point_sample_mv_fwd_batched', ci, [vp, i32, vp, fp, i32, fp, fp, vp, vp, vp]),
+            ('dfm_point_sample_mv_bwd_workspace_bytes', sz, [mp]),
+            ('dfm_point_sample_mv_bwd', ci, [mp, vp, fp, fp, fp, fp, vp, sz, vp]),
+            ('dfm_depth_head_bwd', ci, [i32, i32, i32, i32, i32, i32, vp, fp, vp, vp, vp, fp, vp]),
+            ('dfm_sweep_conv_weight_bytes', sz, []),
+            ('dfm_sweep_conv_pack_weights', ci, [vp, vp, i32, vp, vp]),
+            ('dfm_sweep_conv_stats_splits', ci, [dp, i32]),
+            ('dfm_sweep_conv_fwd', ci, [dp, vp, vp, fp, fp, fp, fp, vp, vp, vp, fp, fp, i32, vp]),
+            ('dfm_cost_gate_weight_bytes', sz, [i32]),
+            ('dfm_cost_gate_pack_weights', ci, [vp, i32, i32, vp, vp]),
+            ('dfm_cost_gate_fwd', ci, [i32, i32, i64, i32, vp, vp, vp, vp, vp]),
+            ('dfm_conv3d_k3_c32_weight_bytes', sz, []),
+            ('dfm_conv3d_k3_c32_pack_weights', ci, [vp, i32, i32, i32, i32, vp, vp]),
+            ('dfm_conv3d_k3_c32_stats_splits', ci, [i32, i32, i32, i32, i32]),
+            ('dfm_conv3d_k3_c32_fwd', ci, [i32, i32, i32, i32, vp, vp, fp, vp, i32, i32, i32, fp, vp]),
+            ('dfm_conv3d_k3_c32_fwd_strided', ci, [i32, i32, i32, i32, vp, i32, vp, fp, vp, i32, i32, i32, fp, vp]),
+            ('dfm_conv3d_k3_c32_fwd_slices', ci, [i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp]),
+            ('dfm_conv3d_k3_c32_to1_fwd', ci, [i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]),
+            ('dfm_group_norm_coefficients', ci, [i32, i32, i32, f32, vp, i32, vp, vp, vp, vp]),
+            ('dfm_conv3d_to1_norm_fwd', ci, [i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp]),
+            ('dfm_conv3d_to1_bwd_data', ci, [i32, i32, i32, i32, vp, vp, i32, vp, vp]),
+            ('dfm_conv3d_to1_wgrad_workspace_bytes', sz, []),
+            ('dfm_conv3d_to1_wgrad', ci, [i32, i32, i32, i32, vp, vp, vp, i32, vp, sz, vp]),
+            ('dfm_bilinear_resize_bwd_nhwc', ci, [i32, i32, i32, i32, i32, i32, i32, vp, vp, fp, i32, vp, fp, i32, vp,
+                                                  vp]),
+            ('dfm_depth_pool_fwd', ci, [i64, i32, i64, i32, vp, vp, vp]),
+            ('dfm_depth_pool_bwd', ci, [i64, i32, i64, i32, vp, vp, vp]),
+            ('dfm_cost_gate_mfma_weight_bytes', sz, [i32]),
+            ('dfm_cost_gate_mfma_pack_weights', ci, [vp, i32, i32, vp, vp]),
+            ('dfm_cost_gate_mfma_fwd', ci, [i32, i32, i64, vp, vp, vp, vp, vp]),
+            ('dfm_conv3d_g_weight_bytes', sz, [i32, i32]),
+            ('dfm_conv3d_g_pack_weights', ci, [vp, i32, i32, i32, i32, i32, vp, vp]),
+            ('dfm_conv3d_g_pack_weights_2d', ci, [vp, i32, i32, i32, i32, i32, vp, vp]),
+            ('dfm_conv3d_g_fwd', ci, [cp, vp, vp, fp, fp, vp, vp, vp]),
+            ('dfm_conv3d_g_fwd_f32', ci, [cp, vp, vp, vp, vp, vp]),
+            ('dfm_conv3d_g_plan', ci, [cp, i64p]),
+            ('dfm_conv3d_wgrad_workspace_bytes', sz, [wp]),
+            ('dfm_conv3d_wgrad', ci, [wp, vp, vp, fp, vp, sz, vp]),
+            ('dfm_conv3d_wgrad_to', ci, [wp, vp, vp, vp, i32, vp, sz, vp]),
+            ('dfm_depth_loss_fwd', ci, [lp, vp, fp, fp, fp, vp, vp]),
+            ('dfm_depth_loss_bwd', ci, [lp, vp, fp, fp, fp, vp, vp]),
+            ('dfm_depth_loss_fused_fwd', ci, [lp, vp, i32, fp, fp, fp, vp, vp]),
+            ('dfm_depth_loss_fused_bwd', ci, [lp, vp, i32, fp, fp, fp, fp, vp]),
+            ('dfm_voxel_sample_fwd', ci, [vsp, vp, fp, vp, vp]),
+            ('dfm_voxel_sample_bwd', ci, [vsp, vp, fp, fp, vp]),
+            ('dfm_voxel_sample_mv_fwd', ci, [vmp, fp, vp, fp, vp, vp]),
+            ('dfm_voxel_sample_mv_bwd', ci, [vmp, fp, vp, fp, fp, vp]),
+            ('dfm_spp_tail_workspace_bytes', sz, [spp]),
+            ('dfm_spp_tail_fwd', ci, [spp, pp, pp, pp, pp, pp, vp, vp, sz, vp]),
+            ('dfm_group_norm_workspace_bytes', sz, [i32, i32, i64, i32]),
+            ('dfm_group_norm_fwd', ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, fp, vp, sz, vp]),
+            ('dfm_group_norm_fwd_channels_last', ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, fp, vp, sz,
+                                                      vp]),
+            ('dfm_group_norm_apply_channels_last', ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, fp, fp,
+                                                        i32, vp, sz, vp]),
+            ('dfm_group_norm_fwd_channels_last_res', ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, vp, fp, fp,
+                                                          vp, sz, vp]),
+            ('dfm_group_norm_apply_channels_last_res', ci, [i32, i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, vp, fp,
+                                                            fp, fp, i32, vp, sz, vp]),
+            ('dfm_group_norm_bwd', ci, [i32, i32, i64, i32, i32, i32, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp, sz, vp]),
+            ('dfm_group_norm_bwd_channels_last', ci, [i32, i32, i64, i32, i32, i32, vp, vp, vp, fp, fp, fp, vp, vp, fp,
+                                                      fp, vp, sz, vp]),
+            ('dfm_group_norm_bwd_channels_last_xmask', ci, [i32, i32, i64, i32, i32, vp, vp, fp, fp, fp, fp, vp, fp, fp,
+                                                            vp, sz, vp]),
+            ('dfm_batch_norm_workspace_bytes', sz, [i32, i64]),
+            ('dfm_batch_norm_stats_channels_last', ci, [i32, i64, i32, vp, fp, vp, sz, vp]),
+            ('dfm_batch_norm_apply_gathered_channels_last', ci, [i32, i64, i32, f32, i32, i32, vp, fp, fp, vp, fp, vp,
+                                                                 fp, fp, fp, vp]),
+            ('dfm_batch_norm_bwd_reduce_channels_last', ci, [i32, i64, i32, i32, vp, vp, vp, fp, fp, fp, fp, fp, vp, sz,
+                                                             vp]),
+            ('dfm_batch_norm_bwd_apply_channels_last', ci, [i32, i64, i32, i32, vp, vp, vp, fp, fp, fp, fp, fp, fp, vp,
+                                                            vp, vp, sz, vp]),
+            ('dfm_imitation_loss_workspace_bytes', sz, [ip]),
+            ('dfm_imitation_loss_fwd', ci, [ip, vp, vp, fp, fp, fp, fp, fp, vp, vp, vp, sz, vp]),
+            ('dfm_imitation_loss_bwd', ci, [ip, vp, vp, vp, fp, fp, fp, vp, vp]),
+            ('dfm_box_nms_workspace_bytes', sz, [i32, i32]),
+            ('dfm_box_nms_rotated', ci, [fp, i32, i32, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp]),
+            ('dfm_box_nms_aligned', ci, [fp, i32, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp]),
+            ('dfm_box_iou_rotated', ci, [fp, i32, fp, i32, i32, fp, vp]),
+            ('dfm_diff_iou_rotated', ci, [fp, fp, i32, i32, fp, fp, fp, vp]),
+            ('dfm_iou3d_loss_from_deltas', ci, [fp, fp, fp, vp, i32, i32, i32, fp, fp, vp]),
+            ('dfm_nearest_bev_overlaps', ci, [fp, i32, fp, i32, i32, i32, i32, fp, vp]),
+            ('dfm_anchor_target_workspace_bytes', sz, [i32, i32]),
+            ('dfm_anchor_target_3d', ci, [atp, fp, fp, vp, i32p, vp, fp, fp, fp, vp, fp, vp, vp, sz, vp]),
+        ),
+        # the anchor head's maps -> boxes
+        'dfm_hip_bbox_decode.h': _table(
+            ('dfm_anchor_head_candidates_workspace_bytes', sz, [ahp]),
+            ('dfm_anchor_head_candidates', ci, [ahp, vp, vp, vp, fp, fp, fp, fp, vp, vp, vp, sz, vp]),
+            ('dfm_delta_xyzwlhr_decode', ci, [fp, fp, i32, i32, fp, vp]),
+        ),
+        # 2-D box overlaps and the 2-D ATSS head's training targets
+        'dfm_hip_atss_target.h': _table(
+            ('dfm_bbox_overlaps_2d', ci, [fp, i32, fp, i32, i32, i32, fp, vp]),
+            ('dfm_atss_target_workspace_bytes', sz, [adp, i32]),
+            ('dfm_atss_target_2d', ci, [adp, fp, i32p, vp, fp, i32p, vp, vp, fp, fp, fp, vp, vp, vp, sz, vp]),
+        ),
+        # the columns of the modulated deformable convolution and their backward
+        'dfm_hip_deform_conv.h': _table(
+            ('dfm_deform_sample_fwd', ci, [ddp, vp, vp, vp, vp, vp]),
+            ('dfm_deform_conv_bwd_cols', ci, [ddp, vp, vp, vp, vp, fp, i64p, fp, i64p, fp, vp]),
+        ),
+        # hard voxelization and the sparse 3-D convolutions of the LiDAR teacher
+        'dfm_hip_sparse_conv.h': _table(
+            ('dfm_voxel_keys', ci, [vdp, fp, fp, vp]),
+            ('dfm_voxel_heads', ci, [vdp, fp, fp, fp, fp, vp]),
+            ('dfm_voxel_keep', ci, [vdp, fp, fp, fp, vp]),
+            ('dfm_voxel_fill', ci, [vdp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]),
+            ('dfm_sparse_conv_out_shape', ci, [sdp, i64, plp]),
+            ('dfm_sparse_conv_workspace_bytes', sz, [sdp, i64]),
+            ('dfm_sparse_index_build', ci, [fp, i64, i32, i32p, fp, fp, i64, fp, vp]),
+            ('dfm_sparse_subm_neighbours', ci, [fp, i64, i32, i32p, fp, fp, i64, fp, vp]),
+            ('dfm_sparse_conv_out_rows', ci, [sdp, fp, i64, fp, fp, fp, fp, vp]),
+            ('dfm_sparse_conv_neighbours', ci, [sdp, fp, i64, fp, fp, fp, vp]),
+            ('dfm_sparse_conv_fwd', ci, [i32, i32, i32, fp, i64, fp, fp, i64, fp, fp, fp, i32, fp, vp]),
+            ('dfm_sparse_dense', ci, [fp, fp, i64, i32, i32, i32p, fp, vp]),
+        ),
+        # the backward of the sparse convolutions and the BatchNorm over live rows
+        'dfm_hip_sparse_train.h': _table(
+            ('dfm_sparse_inverse_table', ci, [fp, i32, i64, i64, fp, vp]),
+            ('dfm_sparse_conv_wgrad_workspace_bytes', sz, [i32, i32, i32, i64]),
+            ('dfm_sparse_conv_wgrad', ci, [i32, i32, i32, fp, i64, fp, fp, i64, fp, fp, vp, sz, fp, vp]),
+            ('dfm_sparse_bn_workspace_bytes', sz, [i64, i32]),
+            ('dfm_sparse_bn_stats', ci, [fp, fp, i64, i32, fp, vp, sz, fp, vp]),
+            ('dfm_sparse_bn_apply', ci, [fp, fp, i64, i32, fp, fp, fp, f32, i32, fp, vp]),
+            ('dfm_sparse_bn_bwd_reduce', ci, [fp, fp, fp, i64, i32, fp, fp, fp, f32, i32, fp, vp, sz, fp, vp]),
+            ('dfm_sparse_bn_bwd_apply', ci, [fp, fp, fp, i64, i32, fp, fp, fp, fp, f32, i32, fp, vp]),
+            ('dfm_sparse_bn_running', ci, [fp, i32, f32, fp, fp, vp]),
+            ('dfm_sparse_dense_bwd', ci, [fp, fp, i64, i32, i32, i32p, fp, vp]),
+        ),
+        # the KITTI evaluation's same-frame overlaps and its matching
+        'dfm_hip_kitti_eval.h': _table(
+            ('dfm_kitti_overlaps', ci, [i64, i64, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]),
+            ('dfm_kitti_eval_workspace_bytes', sz, [i64, i32, i64, i32]),
+            ('dfm_kitti_match', ci, [i32, i32, i32, i64, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp,
+                                     i64, i64, fp, fp, fp, fp, fp, fp, i64, vp, sz, vp]),
+        ),
     }
 
 
-SIGNATURES = _signatures()
+def _flatten(binding):
+    """{header: {name: signature}} -> {name: signature}; a name bound under two headers raises"""
+    flat, where = {}, {}
+    for header, table in binding.items():
+        for name, signature in table.items():
+            if name in flat:
+                raise ValueError(f'{name} is bound twice: under {where[name]} and under {header}')
+            flat[name], where[name] = signature, header
+    return flat
+
+
+_BINDING = _binding()
+SIGNATURES = _flatten(_BINDING)
 EXPORTS = tuple(SIGNATURES)
-
-
-def _bbox_decode_signatures():
-    """the same for include/dfm_hip_bbox_decode.h, the header dfm_hip.h includes for the anchor head's maps -> boxes
-    entry points (tests/test_bbox_decode.py checks this table against that header and the built library)"""
-    vp = fp = ctypes.c_void_p
-    ci, i32, sz, ahp = ctypes.c_int, ctypes.c_int32, ctypes.c_size_t, ctypes.POINTER(AnchorHeadDesc)
-    return {
-        'dfm_anchor_head_candidates_workspace_bytes': (sz, [ahp]),
-        'dfm_anchor_head_candidates': (ci, [ahp, vp, vp, vp, fp, fp, fp, fp, vp, vp, vp, sz, vp]),
-        'dfm_delta_xyzwlhr_decode': (ci, [fp, fp, i32, i32, fp, vp]),
-    }
-
-
-BBOX_DECODE_SIGNATURES = _bbox_decode_signatures()
-BBOX_DECODE_EXPORTS = tuple(BBOX_DECODE_SIGNATURES)
-
-
-def _atss_target_signatures():
-    """the same for include/dfm_hip_atss_target.h: 2-D box overlaps and the 2-D ATSS head's training targets
-    (tests/test_atss_target.py checks this table against that header and the built library)"""
-    vp = fp = ctypes.c_void_p
-    ci, i32, sz, adp = ctypes.c_int, ctypes.c_int32, ctypes.c_size_t, ctypes.POINTER(AtssTargetDesc)
-    return {
-        'dfm_bbox_overlaps_2d': (ci, [fp, i32, fp, i32, i32, i32, fp, vp]),
-        'dfm_atss_target_workspace_bytes': (sz, [adp, i32]),
-        'dfm_atss_target_2d': (ci, [adp, fp, ctypes.POINTER(i32), vp, fp, ctypes.POINTER(i32), vp, vp, fp, fp, fp, vp,
-                                    vp, vp, sz, vp]),
-    }
-
-
-ATSS_TARGET_SIGNATURES = _atss_target_signatures()
-ATSS_TARGET_EXPORTS = tuple(ATSS_TARGET_SIGNATURES)
-
-
-def _deform_conv_signatures():
-    """the same for include/dfm_hip_deform_conv.h: the columns of the modulated deformable convolution and their
-    backward (tests/test_deform_conv.py checks this table against that header and the built library)"""
-    vp = fp = ctypes.c_void_p
-    ci, ddp, i64p = ctypes.c_int, ctypes.POINTER(DeformDesc), ctypes.POINTER(ctypes.c_int64)
-    return {
-        'dfm_deform_sample_fwd': (ci, [ddp, vp, vp, vp, vp, vp]),
-        'dfm_deform_conv_bwd_cols': (ci, [ddp, vp, vp, vp, vp, fp, i64p, fp, i64p, fp, vp]),
-    }
-
-
-DEFORM_CONV_SIGNATURES = _deform_conv_signatures()
-DEFORM_CONV_EXPORTS = tuple(DEFORM_CONV_SIGNATURES)
-
-
-def _sparse_conv_signatures():
-    """the same for include/dfm_hip_sparse_conv.h: hard voxelization and the sparse 3-D convolutions of the LiDAR
-    teacher (tests/test_lidar_teacher.py checks this table against that header and the built library)"""
-    vp = fp = ctypes.c_void_p
-    ci, i32, i64, sz = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
-    vdp, sdp, spp, s3 = (ctypes.POINTER(VoxelDesc), ctypes.POINTER(SparseConvDesc), ctypes.POINTER(SparseConvPlan),
-                         ctypes.POINTER(i32))
-    return {
-        'dfm_voxel_keys': (ci, [vdp, fp, fp, vp]),
-        'dfm_voxel_heads': (ci, [vdp, fp, fp, fp, fp, vp]),
-        'dfm_voxel_keep': (ci, [vdp, fp, fp, fp, vp]),
-        'dfm_voxel_fill': (ci, [vdp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]),
-        'dfm_sparse_conv_out_shape': (ci, [sdp, i64, spp]),
-        'dfm_sparse_conv_workspace_bytes': (sz, [sdp, i64]),
-        'dfm_sparse_index_build': (ci, [fp, i64, i32, s3, fp, fp, i64, fp, vp]),
-        'dfm_sparse_subm_neighbours': (ci, [fp, i64, i32, s3, fp, fp, i64, fp, vp]),
-        'dfm_sparse_conv_out_rows': (ci, [sdp, fp, i64, fp, fp, fp, fp, vp]),
-        'dfm_sparse_conv_neighbours': (ci, [sdp, fp, i64, fp, fp, fp, vp]),
-        'dfm_sparse_conv_fwd': (ci, [i32, i32, i32, fp, i64, fp, fp, i64, fp, fp, fp, i32, fp, vp]),
-        'dfm_sparse_dense': (ci, [fp, fp, i64, i32, i32, s3, fp, vp]),
-    }
-
-
-SPARSE_CONV_SIGNATURES = _sparse_conv_signatures()
-SPARSE_CONV_EXPORTS = tuple(SPARSE_CONV_SIGNATURES)
-
-
-SPARSE_WGRAD_CHUNK, SPARSE_BN_CHUNK = 256, 256  # DFM_SPARSE_WGRAD_CHUNK, DFM_SPARSE_BN_CHUNK
-
-
-def _sparse_train_signatures():
-    """the same for include/dfm_hip_sparse_train.h: the backward of the sparse convolutions and the BatchNorm over
-    live rows (tests/test_sparse_train.py checks this table against that header and the built library)"""
-    vp = fp = ctypes.c_void_p
-    ci, i32, i64, sz, f32 = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
-    s3 = ctypes.POINTER(ctypes.c_int32)
-    return {
-        'dfm_sparse_inverse_table': (ci, [fp, i32, i64, i64, fp, vp]),
-        'dfm_sparse_conv_wgrad_workspace_bytes': (sz, [i32, i32, i32, i64]),
-        'dfm_sparse_conv_wgrad': (ci, [i32, i32, i32, fp, i64, fp, fp, i64, fp, fp, vp, sz, fp, vp]),
-        'dfm_sparse_bn_workspace_bytes': (sz, [i64, i32]),
-        'dfm_sparse_bn_stats': (ci, [fp, fp, i64, i32, fp, vp, sz, fp, vp]),
-        'dfm_sparse_bn_apply': (ci, [fp, fp, i64, i32, fp, fp, fp, f32, i32, fp, vp]),
-        'dfm_sparse_bn_bwd_reduce': (ci, [fp, fp, fp, i64, i32, fp, fp, fp, f32, i32, fp, vp, sz, fp, vp]),
-        'dfm_sparse_bn_bwd_apply': (ci, [fp, fp, fp, i64, i32, fp, fp, fp, fp, f32, i32, fp, vp]),
-        'dfm_sparse_bn_running': (ci, [fp, i32, f32, fp, fp, vp]),
-        'dfm_sparse_dense_bwd': (ci, [fp, fp, i64, i32, i32, s3, fp, vp]),
-    }
-
-
-SPARSE_TRAIN_SIGNATURES = _sparse_train_signatures()
-SPARSE_TRAIN_EXPORTS = tuple(SPARSE_TRAIN_SIGNATURES)
-
-
-KITTI_SAMPLE_POINTS, KITTI_LDS_DETS = 41, 128  # DFM_KITTI_SAMPLE_POINTS, DFM_KITTI_LDS_DETS
-
-
-def _kitti_eval_signatures():
-    """the same for include/dfm_hip_kitti_eval.h: the KITTI evaluation's same-frame overlaps and its matching
-    (tests/test_kitti_eval.py checks this table against that header and the built library)"""
-    vp = fp = ctypes.c_void_p
-    ci, i32, i64, sz = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
-    return {
-        'dfm_kitti_overlaps': (ci, [i64, i64, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]),
-        'dfm_kitti_eval_workspace_bytes': (sz, [i64, i32, i64, i32]),
-        'dfm_kitti_match': (ci, [i32, i32, i32, i64, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, i64,
-                                 i64, fp, fp, fp, fp, fp, fp, i64, vp, sz, vp]),
-    }
-
-
-KITTI_EVAL_SIGNATURES = _kitti_eval_signatures()
-KITTI_EVAL_EXPORTS = tuple(KITTI_EVAL_SIGNATURES)
-
 
 _lib = None
 
@@ -512,10 +487,7 @@ def lib():
             '`python -c "import __graft_entry__ as g; g.build()"` '
             '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
     h = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in (*SIGNATURES.items(), *BBOX_DECODE_SIGNATURES.items(),
-                                      *ATSS_TARGET_SIGNATURES.items(), *DEFORM_CONV_SIGNATURES.items(),
-                                      *SPARSE_CONV_SIGNATURES.items(), *SPARSE_TRAIN_SIGNATURES.items(),
-                                      *KITTI_EVAL_SIGNATURES.items()):
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(h, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = h

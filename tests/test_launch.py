@@ -1,17 +1,14 @@
 """CPU: the launch helper (depth-from-motion_amd/_launch.py) without a GPU -- how Python arguments become C
 arguments (against recording stand-ins), the device checks, how a status becomes True / False / an exception
-(real rejecting calls on the built library: no kernel is launched), and the signature table of _capi.py against
-include/dfm_hip.h."""
+(real rejecting calls on the built library: no kernel is launched).  The signature table of _capi.py is held against
+the headers by tests/test_capi_binding.py."""
 import ctypes
 import importlib
-import os
-import re
 import types
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STREAM_HANDLE, SCRATCH = 0x5151, 0x7000
 
 
@@ -157,53 +154,3 @@ def test_status_mapping_on_the_built_library(pkg, L):
     assert L.try_launch('dfm_plane_sweep_fwd', desc, *tail) is False
     with pytest.raises(err, match='libdfm_hip error -2'):
         L.launch('dfm_plane_sweep_fwd', desc, *tail)
-
-
-# ---------------------------------------------------------------------------
-# the signature table against the header
-# ---------------------------------------------------------------------------
-def header_declarations():
-    """{name: (return type text, parameter count)} of every DFM_API function of include/dfm_hip.h"""
-    text = open(os.path.join(ROOT, 'include', 'dfm_hip.h')).read()
-    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
-    text = re.sub(r'//[^\n]*', ' ', text)
-    decls = {}
-    for m in re.finditer(r'^DFM_API\s+([\w\s\*]+?)\b(dfm_\w+)\s*\(', text, flags=re.M):
-        i, depth, commas = m.end(), 1, 0
-        while depth:
-            ch = text[i]
-            depth += (ch == '(') - (ch == ')')
-            commas += ch == ',' and depth == 1
-            i += 1
-        params = text[m.end():i - 1].strip()
-        assert text[i:].lstrip().startswith(';'), m.group(2)
-        decls[m.group(2)] = (' '.join(m.group(1).split()), 0 if params in ('void', '') else commas + 1)
-    return decls
-
-
-def test_header_parser_on_known_declarations():
-    d = header_declarations()
-    assert d['dfm_version'] == ('int', 0) and d['dfm_last_error'] == ('const char *', 0)
-    assert d['dfm_plane_sweep_reset_tuning'] == ('void', 0)
-    assert d['dfm_profile_end'] == ('int', 2) and d['dfm_camera_prepare'] == ('int', 7)
-    assert d['dfm_plane_sweep_workspace_bytes'] == ('size_t', 1)
-
-
-def test_signature_table_matches_the_header(pkg):
-    capi = pkg._capi
-    decls = header_declarations()
-    assert len(decls) == 114
-    assert sorted(decls) == sorted(capi.SIGNATURES) and capi.EXPORTS == tuple(capi.SIGNATURES)
-    restypes = {'int': ctypes.c_int, 'size_t': ctypes.c_size_t, 'const char *': ctypes.c_char_p, 'void': None}
-    for name, (ret, nparams) in decls.items():
-        restype, argtypes = capi.SIGNATURES[name]
-        assert isinstance(argtypes, list) and len(argtypes) == nparams, \
-            f'{name}: {len(argtypes)} argtypes, the header declares {nparams} parameters'
-        assert restype is restypes[ret], f'{name}: restype {restype}, the header returns {ret}'
-
-
-def test_lib_applies_the_whole_table(pkg):
-    lib = pkg._capi.lib()
-    for name, (restype, argtypes) in pkg._capi.SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, name

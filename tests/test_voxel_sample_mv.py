@@ -52,22 +52,6 @@ def test_function_and_entry_points_are_public(pkg):
     assert pair == pkg._capi.VS_PAIR_FLOATS
 
 
-def test_descriptor_matches_the_header(pkg):
-    """struct dfm_vs_mv_desc, field by field in order, against the ctypes mirror"""
-    header = open(os.path.join(ROOT, 'include', 'dfm_hip.h')).read()
-    body = re.search(r'typedef struct dfm_vs_mv_desc \{(.*?)\} dfm_vs_mv_desc;', header, re.S).group(1)
-    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
-    fields = []
-    for ctype, names in re.findall(r'(int32_t|float)\s+([^;]+);', body):
-        for n in names.split(','):
-            m = re.match(r'\s*(\w+)(?:\[(\d+)\])?\s*$', n)
-            fields.append((m.group(1), ctype, int(m.group(2) or 1)))
-    names = {ctypes.c_float: 'float', ctypes.c_int32: 'int32_t'}
-    mirror = [(n, names[t._type_ if hasattr(t, '_length_') else t], getattr(t, '_length_', 1))
-              for n, t in pkg._capi.VsMvDesc._fields_]
-    assert fields == mirror
-
-
 def test_invalid_calls_are_rejected_without_touching_the_gpu(pkg):
     lib = pkg._capi.lib()
     desc = pkg._capi.VsMvDesc()   # all zero
