@@ -17,7 +17,8 @@ from .depth_head import LazyDepthDistribution, depth_head_forward, depth_head_st
 from .group_norm import HipGroupNorm, group_norm  # noqa: F401
 from .geometry import prepare_coordinates_3d, prepare_depth  # noqa: F401
 from .frustum_to_voxel import frustum_to_voxel_sample  # noqa: F401
-from .integration import (DfMImitationMixin, DfMLidarTeacherMixin, DfMStereoPath, LidarTeacher,  # noqa: F401
+from .integration import (DfMDepthTargetMixin, DfMImitationMixin, DfMLidarTeacherMixin, DfMStereoPath,  # noqa: F401
+                          LidarTeacher,
                           MultiViewDfMMixin, MultiViewVoxelPath, enable_fast_path, inject_detector_attributes,
                           patch_reference)
 from .conv3d import MfmaPathError, fallback_policy, set_fallback_policy, set_fp32_mode  # noqa: F401
@@ -40,6 +41,8 @@ from .sparse_conv import (CustomSparseEncoder, SparseConv3d, SparseConvTensor, S
 from .sparse_train import enable_sparse_training  # noqa: F401
 from .kitti_eval import (bev_box_overlap, calculate_iou_partly, d3_box_overlap, do_eval, eval_class,  # noqa: F401
                          get_mAP11, get_mAP40, image_box_overlap, kitti_eval, rotate_iou_eval)
+from .depth_targets import (GenerateDepthMap, depth_map_in_boxes, generate_depth_map,  # noqa: F401
+                            generate_depth_targets, points_in_boxes_all, points_in_boxes_idmap, points_in_boxes_part)
 from .data_geometry import (fold_ref_frame_matrices, select_ref_frames, stage_geometry,  # noqa: F401
                             video_cur2prevs)
 from .point_sample import (mv_feature_transformation, point_sample, voxel_centers,  # noqa: F401
@@ -62,4 +65,5 @@ __all__ = ['build_dfm_cost', 'plane_sweep_grid', 'point_sample', 'mv_feature_tra
            'SparseConvTensor', 'SubMConv3d', 'SparseConv3d', 'SparseSequential', 'make_sparse_convmodule',
            'CustomSparseEncoder', 'sparse_conv_plan', 'enable_sparse_training', 'LidarTeacher', 'DfMLidarTeacherMixin', 'rotate_iou_eval',
            'bev_box_overlap', 'd3_box_overlap', 'image_box_overlap', 'calculate_iou_partly', 'eval_class', 'get_mAP11',
-           'get_mAP40', 'do_eval', 'kitti_eval']
+           'get_mAP40', 'do_eval', 'kitti_eval', 'generate_depth_map', 'depth_map_in_boxes', 'generate_depth_targets',
+           'points_in_boxes_part', 'points_in_boxes_all', 'points_in_boxes_idmap', 'GenerateDepthMap', 'DfMDepthTargetMixin']

@@ -225,6 +225,17 @@ class SparseConvPlan(ctypes.Structure):
                 ('in_capacity', ctypes.c_int64), ('out_capacity', ctypes.c_int64)]
 
 
+DEPTH_MAX_BATCH, DEPTH_CAM_DOUBLES = 64, 28  # DFM_DEPTH_MAX_BATCH, DFM_DEPTH_CAM_DOUBLES
+PIB_PART, PIB_ALL, PIB_IDMAP = 0, 1, 2  # DFM_PIB_*
+
+
+class DepthTargetsDesc(ctypes.Structure):
+    """struct dfm_depth_targets_desc"""
+    _fields_ = [(n, ctypes.c_int32) for n in ('batch', 'pad_h', 'pad_w', 'point_stride')] + \
+        [('img_h', ctypes.c_int32 * DEPTH_MAX_BATCH), ('img_w', ctypes.c_int32 * DEPTH_MAX_BATCH),
+         ('point_off', ctypes.c_int64 * (DEPTH_MAX_BATCH + 1)), ('box_off', ctypes.c_int64 * (DEPTH_MAX_BATCH + 1))]
+
+
 # C struct name -> its ctypes mirror: every descriptor struct the headers define
 STRUCTS = {
     'dfm_sweep_desc': SweepDesc, 'dfm_sweep_opts': SweepOpts, 'dfm_mv_desc': MvDesc, 'dfm_f2v_desc': F2vDesc,
@@ -233,6 +244,7 @@ STRUCTS = {
     'dfm_conv3d_wgrad_desc': Conv3dWgradDesc, 'dfm_anchor_target_desc': AnchorTargetDesc,
     'dfm_anchor_head_desc': AnchorHeadDesc, 'dfm_atss_target_desc': AtssTargetDesc, 'dfm_deform_desc': DeformDesc,
     'dfm_voxel_desc': VoxelDesc, 'dfm_sparse_conv_desc': SparseConvDesc, 'dfm_sparse_conv_plan': SparseConvPlan,
+    'dfm_depth_targets_desc': DepthTargetsDesc,
 }
 
 # DFM_SPARSE_STATUS_*: bits of the device status word of the sparse-convolution index kernels
@@ -274,6 +286,7 @@ def _binding():
     vsp, vmp, cp, wp, lp = P(VsDesc), P(VsMvDesc), P(Conv3dDesc), P(Conv3dWgradDesc), P(DepthLossDesc)
     ip, atp, ahp, adp, ddp = P(ImitationDesc), P(AnchorTargetDesc), P(AnchorHeadDesc), P(AtssTargetDesc), P(DeformDesc)
     vdp, sdp, plp, i32p, i64p = P(VoxelDesc), P(SparseConvDesc), P(SparseConvPlan), P(i32), P(i64)
+    dtp = P(DepthTargetsDesc)
     return {
         'dfm_hip.h': _table(
             ('dfm_version', ci, []),
@@ -454,6 +467,13 @@ def _binding():
             ('dfm_kitti_eval_workspace_bytes', sz, [i64, i32, i64, i32]),
             ('dfm_kitti_match', ci, [i32, i32, i32, i64, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp,
                                      i64, i64, fp, fp, fp, fp, fp, fp, i64, vp, sz, vp]),
+        ),
+        # the depth loss's targets (LiDAR depth map, box-id mask) and box membership
+        'dfm_hip_depth_targets.h': _table(
+            ('dfm_depth_targets_workspace_bytes', sz, [dtp]),
+            ('dfm_depth_scatter', ci, [dtp, fp, fp, vp, sz, vp]),
+            ('dfm_depth_resolve', ci, [dtp, vp, fp, fp, fp, f32, f32, fp, fp, vp]),
+            ('dfm_points_in_boxes', ci, [i32, i32, i64, i32, fp, fp, fp, vp]),
         ),
     }
 

@@ -19,6 +19,7 @@
 //             two centering NormalizeLayer types measure their scale on the centred values).
 //   backward: grad_pred = coef (pred - t') at positives, 0 elsewhere, one dense pass over grad_pred in
 //             pred's own layout, 16 bytes per lane; coef is read from device memory.
+#include "box_membership.h"
 #include "dfm_common.h"
 
 using namespace dfm;
@@ -40,33 +41,6 @@ struct ImiGeom {
     int32_t wg_per_b, W, ns;  // workgroups per sample, in all; floats per partial row
     int64_t p_sb, p_sc, p_sz, p_sp, t_sb, t_sc, t_sz, t_sp;  // element strides: sample, channel, z, cell
 };
-
-struct ImiBox { float x, y, cz, hx, hy, hz, ca, sa; };
-
-// mmcv 1.6 `points_in_boxes_part` (check_pt_in_box3d + lidar_to_local_coords of
-// mmcv/ops/csrc/common/cuda/points_in_boxes_cuda_kernel.cuh), as the maintainers state its semantics, fp32:
-//   cz = z + z_size/2; reject if |pz - cz| > z_size/2;  a = -yaw;
-//   lx = dx cos(a) - dy sin(a), ly = dx sin(a) + dy cos(a);  inside iff |lx| < x_size/2 and |ly| < y_size/2, strict.
-// A zero-size box contains nothing.
-__device__ __forceinline__ ImiBox imi_box(const float *b7, bool flat)
-{
-    ImiBox o;
-    const float z = flat ? 0.0f : b7[2];  // dfm.py:486: gt_boxes[..., 2] = 0
-    o.x = b7[0]; o.y = b7[1];
-    o.hx = b7[3] / 2.0f; o.hy = b7[4] / 2.0f; o.hz = b7[5] / 2.0f;
-    o.cz = z + o.hz;
-    const float a = -b7[6];
-    o.ca = cosf(a); o.sa = sinf(a);
-    return o;
-}
-__device__ __forceinline__ bool imi_point_in_box(float px, float py, float pz, const ImiBox &b)
-{
-    if (fabsf(pz - b.cz) > b.hz) return false;
-    const float dx = px - b.x, dy = py - b.y;
-    const float lx = dx * b.ca - dy * b.sa;
-    const float ly = dx * b.sa + dy * b.ca;
-    return (lx > -b.hx) & (lx < b.hx) & (ly > -b.hy) & (ly < b.hy);
-}
 
 __device__ __forceinline__ float imi_wave_sum(float v)
 {
@@ -99,7 +73,7 @@ __global__ __launch_bounds__(IMI_THREADS) void imitation_fwd_kernel(
     const float *__restrict__ new_center, unsigned char *__restrict__ mask, double *__restrict__ stats,
     unsigned int *__restrict__ ticket, int *__restrict__ ws_count, float *__restrict__ ws_part)
 {
-    __shared__ ImiBox s_box[IMI_BOX_CHUNK];
+    __shared__ PtBox s_box[IMI_BOX_CHUNK];
     __shared__ int s_list[IMI_CELLS];
     __shared__ int s_cnt[IMI_CPT * IMI_WAVES];
     __shared__ float s_S[IMI_WAVES];
@@ -129,13 +103,13 @@ __global__ __launch_bounds__(IMI_THREADS) void imitation_fwd_kernel(
             for (int t0 = 0; t0 < g.T; t0 += IMI_BOX_CHUNK) {
                 const int nb = min(IMI_BOX_CHUNK, g.T - t0);
                 __syncthreads();
-                if (tid < nb) s_box[tid] = imi_box(boxes + ((size_t)b * g.T + t0 + tid) * 7, true);
+                if (tid < nb) s_box[tid] = pt_box(boxes + ((size_t)b * g.T + t0 + tid) * 7, true);
                 __syncthreads();
                 for (int t = 0; t < nb; ++t) {
-                    const ImiBox bx = s_box[t];
+                    const PtBox bx = s_box[t];
 #pragma unroll
                     for (int k = 0; k < IMI_CPT; ++k)
-                        in[k] = in[k] | imi_point_in_box(px[k], py[k], 0.0f, bx);  // dfm.py:485: point z = 0
+                        in[k] = in[k] | pt_in_box(px[k], py[k], 0.0f, bx);  // dfm.py:485: point z = 0
                 }
             }
         }

@@ -21,7 +21,9 @@ Three ways to use this package from there, all routed to the HIP kernels:
    ``modulated_deform_conv2d`` is rebound and ``ModulatedDeformConv2dPack`` registered as ``'DCNv2'`` in mmcv's
    ``CONV_LAYERS``; likewise ``Voxelization``, ``SparseConvTensor``, ``SparseSequential`` and the layer types
    ``SubMConv3d`` / ``SparseConv3d`` of the LiDAR teacher (``LidarTeacher`` below), and
-   ``DfM.extract_lidar_model_feat``.
+   ``DfM.extract_lidar_model_feat``; and ``depth_map_in_boxes_cpu`` / ``points_in_boxes_part`` / ``points_in_boxes_all``
+   where the pipeline, the box structures and the detector hold them (``DfMDepthTargetMixin`` makes the depth loss's
+   two target maps on the device when the loader did not supply them).
 2. ``DfMStereoPath`` -- the KITTI student's path (neck -> backbone_stereo -> depth_head ->
    feature_transformation -> height compression -> backbone_3d) built from the ``model`` dict of
    ``configs/dfm/dfm_r34_1x8_kitti-3d-3class.py`` with the detector's attribute injection;
@@ -51,6 +53,8 @@ from . import sparse_conv as _sparse_conv
 from .sparse_conv import SparseConv3d, SparseConvTensor, SparseSequential, SubMConv3d
 from .voxelize import Voxelization
 from . import kitti_eval as _kitti_eval
+from . import depth_targets as _depth_targets
+from ._launch import upload
 from .geometry import prepare_coordinates_3d, prepare_depth
 from .conv3d import MfmaConv3dTo1
 from .graphs import GraphedCallable
@@ -207,6 +211,66 @@ class DfMStereoPath(nn.Module):
                                     out['upsample_costs'].flatten(start_dim=0, end_dim=1),
                                     depth_img.flatten(start_dim=0, end_dim=1),
                                     depth_fgmask_img=depth_fgmask_img)
+
+    def depth_targets(self, points, gt_bboxes_3d, img_metas, projs=None):
+        """``(depth_img, depth_fgmask_img)``, (B, 1, H, W) float32 and int32, of a batch -- what the pipeline step
+        ``GenerateDepthMap(generate_fgmask=True)`` hands to ``forward_train``, made on the device from what reaches it
+        anyway: ``points`` (the list of clouds the LiDAR teacher voxelizes: the pipeline's point filters keep
+        ``rect_points`` in step with it, transforms_3d.py:1038-1039), ``gt_bboxes_3d`` (a list of box sets or objects
+        with a ``.tensor``; on the host, where the loader leaves them, or on the device) and the metas' ``cam2img``,
+        ``img_shape`` and ``pad_shape``.  ``projs``: the 3x4 projection of each sample, default ``cam2img[:3]`` --
+        the reference projects with ``calib.P2``, a second copy of that
+        matrix which the augmentations keep equal to it.  One memset and two launches of this package's kernels, no
+        host wait (``depth_targets.counters()``)."""
+        return depth_targets_from_metas(points, gt_bboxes_3d, img_metas, projs)
+
+
+def _boxes_beside(boxes, device):
+    """the first 7 columns of one sample's boxes as float32 on ``device``.  The loader leaves ``gt_bboxes_3d`` on the
+    host (``DefaultFormatBundle3D`` wraps box objects ``cpu_only``) and the reference moves them itself where it needs
+    them (dfm.py:480-483); here the copy is pinned and non-blocking, so the host does not wait for the stream"""
+    t = getattr(boxes, 'tensor', boxes)
+    if not torch.is_tensor(t):
+        t = torch.as_tensor(np.asarray(t))
+    t = t[:, :7]
+    if t.device == device:
+        return t
+    if t.shape[0] == 0:
+        return torch.empty((0, 7), dtype=t.dtype, device=device)
+    return upload(t, device)
+
+
+def depth_targets_from_metas(points, gt_bboxes_3d, img_metas, projs=None):
+    """the arguments of ``generate_depth_targets`` read from ``img_metas``; every sample shares one ``pad_shape``.  With
+    the clouds on a GPU, box sets that are still on the host are copied beside them"""
+    points, boxes = list(points), list(gt_bboxes_3d)
+    if points and torch.is_tensor(points[0]) and points[0].is_cuda:
+        boxes = [_boxes_beside(b, points[0].device) for b in boxes]
+    cam2imgs = [_depth_targets._host_matrix(meta['cam2img'], 'cam2img') for meta in img_metas]
+    pads = {tuple(int(v) for v in tuple(meta['pad_shape'])[:2]) for meta in img_metas}
+    if len(pads) != 1:
+        raise ValueError(f'the samples of a batch share one pad_shape, got {sorted(pads)}')
+    if projs is None:
+        projs = cam2imgs
+    return _depth_targets.generate_depth_targets(points, boxes, projs, cam2imgs,
+                                                 [meta['img_shape'] for meta in img_metas], pads.pop())
+
+
+class DfMDepthTargetMixin:
+    """``forward_train`` of ``DfM`` (dfm.py:300-310) that makes ``depth_img`` / ``depth_fgmask_img`` on the device from
+    ``points`` when the loader did not supply them (a train pipeline without ``GenerateDepthMap``, whose mask half needs
+    mmcv's compiled ``points_in_boxes_cpu``), then defers to the host class:
+    ``class FastDfM(DfMDepthTargetMixin, DfM)``.  What the loader supplied is left as it is."""
+
+    def forward_train(self, img, img_metas, gt_bboxes_3d, gt_labels_3d, gt_bboxes=None, depth_img=None,
+                      depth_fgmask_img=None, points=None, centers2d=None, **kwargs):
+        if depth_img is None and points is not None and getattr(self, 'with_depth_head', True):
+            depth_img, mask = depth_targets_from_metas(points, gt_bboxes_3d, img_metas)
+            if depth_fgmask_img is None:
+                depth_fgmask_img = mask
+        return super().forward_train(img, img_metas, gt_bboxes_3d, gt_labels_3d, gt_bboxes=gt_bboxes,
+                                     depth_img=depth_img, depth_fgmask_img=depth_fgmask_img, points=points,
+                                     centers2d=centers2d, **kwargs)
 
 
 class MultiViewDfMMixin:
@@ -643,6 +707,28 @@ def _patch_kitti_eval():
     return done
 
 
+# the depth loss's targets: ``depth_map_in_boxes_cpu`` where the pipeline holds it by name (its body calls mmcv's
+# compiled ``points_in_boxes_cpu``), and mmcv's ``points_in_boxes_part`` / ``_all`` where the box structures and the
+# detector imported them.  Only where those modules are already imported, as above.
+_DEPTH_MAP_MODULES = ('mmdet3d.datasets.utils', 'mmdet3d.datasets.pipelines.transforms_3d')
+_POINTS_IN_BOXES_MODULES = ('mmdet3d.core.bbox.structures.base_box3d', 'mmdet3d.models.detectors.dfm')
+
+
+def _patch_depth_targets():
+    """-> functions rebound; [] when none of the modules is imported"""
+    done = []
+    for modules, names in ((_DEPTH_MAP_MODULES, {'depth_map_in_boxes_cpu': _depth_targets.depth_map_in_boxes}),
+                           (_POINTS_IN_BOXES_MODULES, {'points_in_boxes_part': _depth_targets.points_in_boxes_part,
+                                                       'points_in_boxes_all': _depth_targets.points_in_boxes_all})):
+        for mod_name in modules:
+            mod = sys.modules.get(mod_name)
+            for attr, fn in names.items():
+                if mod is not None and hasattr(mod, attr):
+                    setattr(mod, attr, fn)
+                    done.append(f'{mod_name}.{attr}')
+    return done
+
+
 def patch_reference(precision=None, strict=False):
     """Route a real mmdet3d (the reference fork) to the HIP path.  Call once after
     ``import mmdet3d`` and before building the model from ``configs/dfm/*``.  Returns a report
@@ -668,6 +754,7 @@ def patch_reference(precision=None, strict=False):
     report['functions'] += _patch_nms_functions()
     report['functions'] += _patch_iou_functions()
     report['functions'] += _patch_kitti_eval()
+    report['functions'] += _patch_depth_targets()
     functions, methods = _patch_anchor_target()
     report['functions'] += functions
     report['methods'] += methods

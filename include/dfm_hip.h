@@ -1381,6 +1381,9 @@ DFM_API int dfm_spp_tail_fwd(const dfm_spp_desc *desc, const void *const *pooled
 #include "dfm_hip_sparse_train.h"
 /* KITTI evaluation: same-frame overlaps and the AP / AOS matching (dfm_kitti_*): likewise */
 #include "dfm_hip_kitti_eval.h"
+/* the depth loss's targets: LiDAR depth map and box-id mask, and the box-membership operators (dfm_depth_*,
+ * dfm_points_in_boxes): likewise */
+#include "dfm_hip_depth_targets.h"
 
 #ifdef __cplusplus
 }

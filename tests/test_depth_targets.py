@@ -1,0 +1,285 @@
+"""CPU: the depth loss's targets (depth-from-motion_amd/depth_targets.py) on their numpy path against
+tests/golden/depth_targets.npz, which holds what the reference's own GenerateDepthMap produced
+(tests/golden/make_golden_depth_targets.py).  The results are integers and copied floats: every comparison is
+bit-exact.  The kernels run the same cases in tests/test_depth_targets_gpu.py."""
+import ctypes
+import importlib
+import re
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from tests import capi_header as H
+from tests.depth_targets_util import BATCH, SINGLE, case, fixture, same_bits
+
+
+@pytest.fixture(scope='module')
+def pkg():
+    importlib.import_module('depth-from-motion_amd.build').build_hip()
+    return importlib.import_module('depth-from-motion_amd')
+
+
+@pytest.fixture(scope='module')
+def dt(pkg):
+    return importlib.import_module('depth-from-motion_amd.depth_targets')
+
+
+def run_single(dt, c, wrap=lambda a: a):
+    return dt.generate_depth_targets([wrap(c['points'])], [wrap(c['boxes'])], [c['P']], [c['cam2img']],
+                                     [c['img_shape']], c['pad_shape'])
+
+
+@pytest.mark.parametrize('key', SINGLE + BATCH)
+def test_numpy_path_reproduces_the_reference(dt, key):
+    c = case(key)
+    depth, mask = run_single(dt, c)
+    h, w = c['pad_shape'][:2]
+    assert (depth.dtype, mask.dtype) == (torch.float32, torch.int32) and depth.shape == mask.shape == (1, 1, h, w)
+    assert same_bits(depth[0, 0].numpy(), c['depth']) and np.array_equal(mask[0, 0].numpy(), c['mask'])
+    # the two halves on their own: numpy in, numpy out; a CPU tensor in, a CPU tensor out
+    alone = dt.generate_depth_map(c['points'], c['P'], c['img_shape'], c['pad_shape'])
+    assert isinstance(alone, np.ndarray) and same_bits(alone, c['depth'])
+    ids = dt.depth_map_in_boxes(c['depth'], c['boxes'], c['cam2img'], expand_ratio=1.0, expand_distance=0.)
+    assert isinstance(ids, np.ndarray) and ids.dtype == np.int32 and np.array_equal(ids, c['mask'])
+    ids = dt.depth_map_in_boxes(torch.from_numpy(c['depth']), torch.from_numpy(c['boxes']), c['cam2img'])
+    assert torch.is_tensor(ids) and ids.dtype == torch.int32 and np.array_equal(ids.numpy(), c['mask'])
+
+
+def test_exact_case_shows_what_it_is_there_for():
+    """read off the stored reference result: ties go to even, -0.5 is kept as column / row 0, w - 0.5 is dropped, the
+    highest index wins, a negative depth is written and gets no id, a point on a face is outside"""
+    c = case('exact')
+    d, m = c['depth'], c['mask']
+    assert d[3, 4] == 2 and d[3, 6] == 2 and d[3, 5] == 0 and d[5, 0] == 2 and d[2, 9] == 4 and d[4, 9] == 4
+    assert d[0, 11] == 4 and d[8, 24] == -2 and m[8, 24] == 0 and d[12, 20] == 4 and d[2, 26] == 2
+    assert (d[8, 16], m[8, 16]) == (4, 0) and (d[8, 17], m[8, 17]) == (4, 2)
+    assert (d[8, 12], m[8, 12]) == (1, 3) and (d[7, 12], m[7, 12]) == (1, 0)          # in / above the plane of dz = 0
+    assert c['points'].shape[0] == 5000 and np.array_equal(c['points'][50, :3], c['points'][4950, :3] * 4)
+
+
+def test_a_batch_equals_its_samples(dt):
+    cs = [case(k) for k in BATCH]
+    assert [c['points'].shape[0] for c in cs] == [0, 257, 5000] and [c['boxes'].shape[0] for c in cs] == [2, 0, 7]
+    depth, mask = dt.generate_depth_targets([torch.from_numpy(c['points']) for c in cs],
+                                            [types.SimpleNamespace(tensor=torch.from_numpy(c['boxes'])) for c in cs],
+                                            [c['P'] for c in cs], [c['cam2img'] for c in cs],
+                                            [c['img_shape'] for c in cs], cs[0]['pad_shape'])
+    assert depth.shape == mask.shape == (3, 1, 32, 64)
+    for b, c in enumerate(cs):
+        assert same_bits(depth[b, 0].numpy(), c['depth']) and np.array_equal(mask[b, 0].numpy(), c['mask'])
+    only, none = dt.generate_depth_targets([c['points'] for c in cs], None, [c['P'] for c in cs], None,
+                                           [c['img_shape'] for c in cs], cs[0]['pad_shape'], generate_fgmask=False)
+    assert none is None and same_bits(only.numpy(), depth.numpy())
+
+
+def test_expansion_is_ratio_then_distance_in_fp32(dt):
+    """utils.py:423-424: sizes * ratio, then + distance; against the same boxes expanded by hand in FP32"""
+    c = case('random')
+    grown = c['boxes'].copy()
+    grown[:, 3:6] *= np.float32(1.1)
+    grown[:, 3:6] += np.float32(0.25)
+    want = dt.depth_map_in_boxes(c['depth'], grown, c['cam2img'])
+    got = dt.depth_map_in_boxes(c['depth'], c['boxes'], c['cam2img'], expand_ratio=1.1, expand_distance=0.25)
+    assert np.array_equal(got, want) and (got != c['mask']).any()
+
+
+def test_membership_modes(dt):
+    z = fixture()
+    p, b = z['membership/points'], z['membership/boxes']
+    assert p.shape == (2, 515, 3) and b.shape == (2, 5, 7) and (z['membership/part'] != z['membership/idmap']).any()
+    for fn, key, shape in ((dt.points_in_boxes_part, 'part', (2, 515)), (dt.points_in_boxes_all, 'all', (2, 515, 5)),
+                           (dt.points_in_boxes_idmap, 'idmap', (2, 515))):
+        got = fn(torch.from_numpy(p), torch.from_numpy(b))
+        assert torch.is_tensor(got) and got.dtype == torch.int32 and tuple(got.shape) == shape
+        assert np.array_equal(got.numpy(), z[f'membership/{key}'])
+        assert np.array_equal(fn(p, b), z[f'membership/{key}'])
+    none = b[:, :0]
+    assert (dt.points_in_boxes_part(p, none) == -1).all() and dt.points_in_boxes_all(p, none).shape == (2, 515, 0)
+    assert dt.points_in_boxes_idmap(p[:, :0], b).shape == (2, 0)
+
+
+def test_pipeline_step_matches_the_reference_contract(pkg, dt):
+    c = case('random')
+    step = pkg.GenerateDepthMap()
+    assert repr(step) == str(fixture()['repr']) and step.generate_fgmask is True
+    calib = types.SimpleNamespace(P2=c['P'])
+    boxes = types.SimpleNamespace(tensor=torch.from_numpy(c['boxes']))
+    d = dict(cam2img=c['cam2img'], points=types.SimpleNamespace(tensor=torch.from_numpy(c['points'])), calib=calib,
+             pad_shape=c['pad_shape'], img_shape=c['img_shape'], gt_bboxes_3d=boxes)
+    out = step(d)
+    assert out is d and isinstance(out['depth_img'], np.ndarray) and isinstance(out['depth_fgmask_img'], np.ndarray)
+    assert out['depth_img'].dtype == np.float32 and out['depth_fgmask_img'].dtype == np.int32
+    assert same_bits(out['depth_img'], c['depth']) and np.array_equal(out['depth_fgmask_img'], c['mask'])
+    # rect_points, when the pipeline kept them, take precedence over points (transforms_3d.py:66-67)
+    p = c['points'].astype(np.float64)
+    d2 = dict(cam2img=c['cam2img'], rect_points=np.stack([-p[:, 1], -p[:, 2], p[:, 0]], 1), points=None, calib=calib,
+              pad_shape=c['pad_shape'], img_shape=c['img_shape'])
+    out = pkg.GenerateDepthMap(generate_fgmask=False)(d2)
+    assert same_bits(out['depth_img'], c['depth']) and 'depth_fgmask_img' not in out
+    assert repr(pkg.GenerateDepthMap(False)) == 'GenerateDepthMap(generate_fgmask=False.'
+
+
+def test_names_are_in_the_header_the_binding_and_the_package(pkg, dt):
+    header = 'dfm_hip_depth_targets.h'
+    names = ['dfm_depth_targets_workspace_bytes', 'dfm_depth_scatter', 'dfm_depth_resolve', 'dfm_points_in_boxes']
+    assert header in H.HEADERS and list(H.declarations(H.code(header))) == names
+    assert list(pkg._capi._BINDING[header]) == names and set(names) <= set(pkg._capi.EXPORTS)
+    assert re.search(r'#include "dfm_hip_depth_targets.h"', H.code('dfm_hip.h'))
+    assert pkg._capi.STRUCTS['dfm_depth_targets_desc'] is pkg._capi.DepthTargetsDesc
+    public = ['generate_depth_map', 'depth_map_in_boxes', 'generate_depth_targets', 'points_in_boxes_part',
+              'points_in_boxes_all', 'points_in_boxes_idmap', 'GenerateDepthMap']
+    assert set(public) | {'DfMDepthTargetMixin'} <= set(pkg.__all__) and set(public) | {'counters'} == set(dt.__all__)
+    for name in public:
+        assert getattr(pkg, name) is getattr(dt, name)
+    assert set(dt.counters()) == {'kernel_launches', 'memsets', 'host_waits'}
+    assert hasattr(pkg.DfMStereoPath, 'depth_targets')
+
+
+def test_patch_rebinds_only_loaded_modules(pkg, dt):
+    integ = importlib.import_module('depth-from-motion_amd.integration')
+    names = ('mmdet3d', 'mmdet3d.datasets', 'mmdet3d.datasets.utils', 'mmdet3d.datasets.pipelines',
+             'mmdet3d.datasets.pipelines.transforms_3d', 'mmdet3d.core', 'mmdet3d.core.bbox',
+             'mmdet3d.core.bbox.structures', 'mmdet3d.core.bbox.structures.base_box3d', 'mmdet3d.models',
+             'mmdet3d.models.detectors', 'mmdet3d.models.detectors.dfm')
+    before = {k: sys.modules.get(k) for k in names}
+    old = lambda *a, **k: 'reference'                                         # noqa: E731
+    try:
+        for k in names:
+            sys.modules.pop(k, None)
+        assert integ._patch_depth_targets() == [] and not any(k in sys.modules for k in names)
+        for k in names:
+            m = types.ModuleType(k)
+            m.__path__ = []
+            sys.modules[k] = m
+        del sys.modules['mmdet3d.datasets.utils']                              # one holder that is NOT loaded
+        sys.modules[names[4]].depth_map_in_boxes_cpu = old
+        sys.modules[names[8]].points_in_boxes_part = sys.modules[names[8]].points_in_boxes_all = old
+        sys.modules[names[8]].box_iou_rotated = old
+        sys.modules[names[11]].points_in_boxes_part = old
+        done = integ._patch_depth_targets()
+        assert done == [f'{names[4]}.depth_map_in_boxes_cpu', f'{names[8]}.points_in_boxes_part',
+                        f'{names[8]}.points_in_boxes_all', f'{names[11]}.points_in_boxes_part']
+        assert sys.modules[names[4]].depth_map_in_boxes_cpu is dt.depth_map_in_boxes
+        assert sys.modules[names[8]].points_in_boxes_part is dt.points_in_boxes_part
+        assert sys.modules[names[8]].points_in_boxes_all is dt.points_in_boxes_all
+        assert sys.modules[names[11]].points_in_boxes_part is dt.points_in_boxes_part
+        assert sys.modules[names[8]].box_iou_rotated is old
+        assert not hasattr(sys.modules[names[11]], 'points_in_boxes_all')
+        assert 'mmdet3d.datasets.utils' not in sys.modules and integ._patch_depth_targets() == done
+    finally:
+        for k, v in before.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
+
+
+def test_metas_and_mixin(pkg, dt):
+    """``depth_targets_from_metas`` reads cam2img / img_shape / pad_shape, projs default to cam2img[:3]; the mixin
+    fills what the loader left out and leaves what it supplied"""
+    integ = importlib.import_module('depth-from-motion_amd.integration')
+    c = case('random')
+    assert np.array_equal(c['cam2img'][:3], c['P'])
+    metas = [dict(cam2img=c['cam2img'].tolist(), img_shape=c['img_shape'], pad_shape=c['pad_shape'])]
+    points, boxes = [torch.from_numpy(c['points'])], [types.SimpleNamespace(tensor=torch.from_numpy(c['boxes']))]
+    depth, mask = integ.depth_targets_from_metas(points, boxes, metas)
+    assert same_bits(depth[0, 0].numpy(), c['depth']) and np.array_equal(mask[0, 0].numpy(), c['mask'])
+    with pytest.raises(ValueError, match='share one pad_shape'):
+        integ.depth_targets_from_metas(points * 2, boxes * 2, metas + [dict(metas[0], pad_shape=(40, 64, 3))])
+
+    class Host:
+        with_depth_head = True
+
+        def forward_train(self, img, img_metas, gt_bboxes_3d, gt_labels_3d, **kwargs):
+            return kwargs
+
+    class Fast(pkg.DfMDepthTargetMixin, Host):
+        pass
+    got = Fast().forward_train(None, metas, boxes, None, points=points)
+    assert same_bits(got['depth_img'][0, 0].numpy(), c['depth']) and got['points'] is points
+    assert np.array_equal(got['depth_fgmask_img'][0, 0].numpy(), c['mask'])
+    mine = torch.ones(1, 1, 32, 64)
+    got = Fast().forward_train(None, metas, boxes, None, points=points, depth_img=mine)
+    assert got['depth_img'] is mine and got['depth_fgmask_img'] is None
+    assert Fast().forward_train(None, metas, boxes, None)['depth_img'] is None                 # no points: nothing made
+
+
+def test_refusals(pkg, dt):
+    c = case('random')
+    args = ([c['P']], [c['cam2img']], [c['img_shape']], c['pad_shape'])
+    with pytest.raises(TypeError, match='points must be float32'):
+        dt.generate_depth_targets([c['points'].astype(np.float64)], [c['boxes']], *args)
+    with pytest.raises(TypeError, match='boxes must be float32'):
+        dt.generate_depth_targets([c['points']], [c['boxes'].astype(np.float64)], *args)
+    with pytest.raises(ValueError, match=r'points is \(N, >=3\)'):
+        dt.generate_depth_targets([c['points'][:, :2]], [c['boxes']], *args)
+    with pytest.raises(ValueError, match=r'boxes is \(M, >=7\)'):
+        dt.generate_depth_targets([c['points']], [c['boxes'][:, :6]], *args)
+    with pytest.raises(ValueError, match='one entry per sample'):
+        dt.generate_depth_targets([c['points']] * 2, [c['boxes']], *args)
+    with pytest.raises(ValueError, match='at most 64'):
+        dt.generate_depth_targets([c['points']] * 65, [c['boxes']] * 65, [c['P']] * 65, [c['cam2img']] * 65,
+                                  [c['img_shape']] * 65, c['pad_shape'])
+    with pytest.raises(ValueError, match='does not fit pad_shape'):
+        dt.generate_depth_targets([c['points']], [c['boxes']], [c['P']], [c['cam2img']], [(33, 64, 3)], c['pad_shape'])
+    with pytest.raises(ValueError, match='3x4 projection'):
+        dt.generate_depth_map(c['points'], c['P'][:, :3], c['img_shape'], c['pad_shape'])
+    with pytest.raises(ValueError, match='singular'):
+        dt.depth_map_in_boxes(c['depth'], c['boxes'], np.zeros((3, 3)))
+    with pytest.raises(TypeError, match='depth_img must be float32'):
+        dt.depth_map_in_boxes(c['depth'].astype(np.float64), c['boxes'], c['cam2img'])
+    z = fixture()
+    p, b = z['membership/points'], z['membership/boxes']
+    with pytest.raises(ValueError, match='same batch size'):
+        dt.points_in_boxes_part(p, b[:1])
+    with pytest.raises(ValueError, match=r'\(B, M, 7\)'):
+        dt.points_in_boxes_all(p, b[..., :6])
+    with pytest.raises(TypeError, match='float32'):
+        dt.points_in_boxes_idmap(p.astype(np.float64), b)
+    assert dt.MAX_POINTS == 2 ** 32 - 2 and dt.MAX_BOXES == 2 ** 31 - 2
+
+
+def test_the_library_refuses_before_it_touches_the_gpu(pkg):
+    """sizes beyond what the index words hold, an img_shape larger than the map, broken tables: answered on the host"""
+    capi, lib = pkg._capi, pkg._capi.lib()
+
+    def desc(**kw):
+        d = capi.DepthTargetsDesc()
+        d.batch, d.pad_h, d.pad_w, d.point_stride = 1, 32, 64, 4
+        d.img_h[0], d.img_w[0] = 30, 61
+        d.point_off[1], d.box_off[1] = 10, 2
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+    assert lib.dfm_depth_targets_workspace_bytes(ctypes.byref(desc())) == 32 * 64 * 8
+    assert lib.dfm_depth_targets_workspace_bytes(ctypes.byref(desc(batch=65))) == 0
+    for bad, rc, word in ((desc(batch=0), -1, 'batch'), (desc(point_stride=2), -1, 'point_stride'),
+                          (desc(pad_w=0), -1, 'pad'), (desc(pad_h=65536, pad_w=65536), -2, 'too large')):
+        assert lib.dfm_depth_scatter(ctypes.byref(bad), None, None, None, 0, None) == rc
+        assert word in lib.dfm_last_error().decode()
+    d = desc()
+    d.img_h[0] = 33
+    assert lib.dfm_depth_resolve(ctypes.byref(d), None, None, None, None, 1.0, 0.0, None, None, None) == -1
+    assert 'does not fit pad_shape' in lib.dfm_last_error().decode()
+    d = desc()
+    d.point_off[1] = 2 ** 32 - 1
+    assert lib.dfm_depth_scatter(ctypes.byref(d), None, None, None, 0, None) == -2
+    assert 'index word' in lib.dfm_last_error().decode()
+    d = desc()
+    d.box_off[1] = 2 ** 31 - 1
+    assert lib.dfm_depth_scatter(ctypes.byref(d), None, None, None, 0, None) == -2
+    d = desc()
+    d.point_off[1] = -1
+    assert lib.dfm_depth_scatter(ctypes.byref(d), None, None, None, 0, None) == -1
+    assert lib.dfm_depth_scatter(ctypes.byref(desc()), None, None, None, 0, None) == -3          # no key map
+    assert lib.dfm_depth_resolve(ctypes.byref(desc()), None, None, None, None, 1.0, 0.0, None, None, None) == -1
+    assert 'exactly one of keys and depth_in' in lib.dfm_last_error().decode()
+    assert lib.dfm_points_in_boxes(3, 1, 1, 1, None, None, None, None) == -1
+    assert lib.dfm_points_in_boxes(0, 1, 1, 2 ** 31 - 1, None, None, None, None) == -2
+    assert 'int32 index' in lib.dfm_last_error().decode()
+    assert lib.dfm_points_in_boxes(0, 65536, 1, 1, None, None, None, None) == -2
+    assert lib.dfm_points_in_boxes(1, 2, 0, 5, None, None, None, None) == 0                    # nothing to do
+    assert lib.dfm_points_in_boxes(0, 2, 5, 5, None, None, None, None) == -1                   # NULL pointers
