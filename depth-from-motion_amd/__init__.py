@@ -47,6 +47,7 @@ from .data_geometry import (fold_ref_frame_matrices, select_ref_frames, stage_ge
                             video_cur2prevs)
 from .point_sample import (mv_feature_transformation, point_sample, voxel_centers,  # noqa: F401
                            voxel_sample, voxel_sample_mv)
+from .optim import FusedAdamW, clip_grad_norm_  # noqa: F401
 
 __all__ = ['build_dfm_cost', 'plane_sweep_grid', 'point_sample', 'mv_feature_transformation',
            'voxel_centers', 'voxel_sample', 'voxel_sample_mv', 'frustum_to_voxel_sample', 'depth_head_forward', 'prepare_depth',
@@ -66,4 +67,5 @@ __all__ = ['build_dfm_cost', 'plane_sweep_grid', 'point_sample', 'mv_feature_tra
            'CustomSparseEncoder', 'sparse_conv_plan', 'enable_sparse_training', 'LidarTeacher', 'DfMLidarTeacherMixin', 'rotate_iou_eval',
            'bev_box_overlap', 'd3_box_overlap', 'image_box_overlap', 'calculate_iou_partly', 'eval_class', 'get_mAP11',
            'get_mAP40', 'do_eval', 'kitti_eval', 'generate_depth_map', 'depth_map_in_boxes', 'generate_depth_targets',
-           'points_in_boxes_part', 'points_in_boxes_all', 'points_in_boxes_idmap', 'GenerateDepthMap', 'DfMDepthTargetMixin']
+           'points_in_boxes_part', 'points_in_boxes_all', 'points_in_boxes_idmap', 'GenerateDepthMap', 'DfMDepthTargetMixin',
+           'FusedAdamW', 'clip_grad_norm_']

@@ -236,6 +236,17 @@ class DepthTargetsDesc(ctypes.Structure):
          ('point_off', ctypes.c_int64 * (DEPTH_MAX_BATCH + 1)), ('box_off', ctypes.c_int64 * (DEPTH_MAX_BATCH + 1))]
 
 
+OPTIM_THREADS, OPTIM_CHUNK, OPTIM_ZERO_GRADS = 256, 8192, 1  # DFM_OPTIM_*
+
+
+class OptimTensor(ctypes.Structure):
+    """struct dfm_optim_tensor: one row of the optimizer's multi-tensor table (the arrays are device addresses)"""
+    _fields_ = [(n, ctypes.c_int64) for n in ('param', 'grad', 'exp_avg', 'exp_avg_sq', 'master', 'numel')] + \
+        [('dtype', ctypes.c_int32), ('reserved', ctypes.c_int32)] + \
+        [(n, ctypes.c_float) for n in ('decay', 'step_size', 'bc2_sqrt', 'lerp_weight', 'beta2', 'one_minus_beta2',
+                                       'eps', 'reserved_f')]
+
+
 # C struct name -> its ctypes mirror: every descriptor struct the headers define
 STRUCTS = {
     'dfm_sweep_desc': SweepDesc, 'dfm_sweep_opts': SweepOpts, 'dfm_mv_desc': MvDesc, 'dfm_f2v_desc': F2vDesc,
@@ -244,7 +255,7 @@ STRUCTS = {
     'dfm_conv3d_wgrad_desc': Conv3dWgradDesc, 'dfm_anchor_target_desc': AnchorTargetDesc,
     'dfm_anchor_head_desc': AnchorHeadDesc, 'dfm_atss_target_desc': AtssTargetDesc, 'dfm_deform_desc': DeformDesc,
     'dfm_voxel_desc': VoxelDesc, 'dfm_sparse_conv_desc': SparseConvDesc, 'dfm_sparse_conv_plan': SparseConvPlan,
-    'dfm_depth_targets_desc': DepthTargetsDesc,
+    'dfm_depth_targets_desc': DepthTargetsDesc, 'dfm_optim_tensor': OptimTensor,
 }
 
 # DFM_SPARSE_STATUS_*: bits of the device status word of the sparse-convolution index kernels
@@ -474,6 +485,12 @@ def _binding():
             ('dfm_depth_scatter', ci, [dtp, fp, fp, vp, sz, vp]),
             ('dfm_depth_resolve', ci, [dtp, vp, fp, fp, fp, f32, f32, fp, fp, vp]),
             ('dfm_points_in_boxes', ci, [i32, i32, i64, i32, fp, fp, fp, vp]),
+        ),
+        # the optimizer step: the gradients' global norm, the clip and AdamW over one multi-tensor table
+        'dfm_hip_optim.h': _table(
+            ('dfm_grad_sqnorm', ci, [vp, i32, vp, i64, fp, vp]),
+            ('dfm_adamw_step', ci, [vp, i32, vp, i64, fp, f32, fp, i32, vp]),
+            ('dfm_grad_scale', ci, [vp, i32, vp, i64, fp, f32, fp, vp]),
         ),
     }
 

@@ -54,6 +54,7 @@ from .sparse_conv import SparseConv3d, SparseConvTensor, SparseSequential, SubMC
 from .voxelize import Voxelization
 from . import kitti_eval as _kitti_eval
 from . import depth_targets as _depth_targets
+from . import optim as _optim
 from ._launch import upload
 from .geometry import prepare_coordinates_3d, prepare_depth
 from .conv3d import MfmaConv3dTo1
@@ -729,6 +730,30 @@ def _patch_depth_targets():
     return done
 
 
+# the optimizer step: ``FusedAdamW`` into mmcv's OPTIMIZERS registry (a config names it ``type='FusedAdamW'``), and the
+# clip of ``OptimizerHook.clip_grads``.  The hook module holds torch's ``clip_grad`` MODULE and calls
+# ``clip_grad.clip_grad_norm_``: it gets a namespace of its own in that place, torch's module is left as it is.
+class _ClipGrad:
+    clip_grad_norm_ = staticmethod(_optim.clip_grad_norm_)
+
+
+def _patch_optimizer():
+    """-> (modules registered, functions rebound); ([], []) without mmcv"""
+    try:
+        registry_mod = importlib.import_module('mmcv.runner.optimizer')
+        hooks = importlib.import_module('mmcv.runner.hooks.optimizer')
+    except ImportError:
+        return [], []
+    modules, functions = [], []
+    if hasattr(registry_mod, 'OPTIMIZERS'):
+        registry_mod.OPTIMIZERS.register_module(name='FusedAdamW', force=True, module=_optim.FusedAdamW)
+        modules.append('FusedAdamW (mmcv OPTIMIZERS)')
+    if hasattr(hooks, 'clip_grad'):
+        hooks.clip_grad = _ClipGrad
+        functions.append('mmcv.runner.hooks.optimizer.clip_grad.clip_grad_norm_')
+    return modules, functions
+
+
 def patch_reference(precision=None, strict=False):
     """Route a real mmdet3d (the reference fork) to the HIP path.  Call once after
     ``import mmdet3d`` and before building the model from ``configs/dfm/*``.  Returns a report
@@ -755,6 +780,9 @@ def patch_reference(precision=None, strict=False):
     report['functions'] += _patch_iou_functions()
     report['functions'] += _patch_kitti_eval()
     report['functions'] += _patch_depth_targets()
+    layers, functions = _patch_optimizer()
+    report['modules'] += layers
+    report['functions'] += functions
     functions, methods = _patch_anchor_target()
     report['functions'] += functions
     report['methods'] += methods

@@ -1384,6 +1384,9 @@ DFM_API int dfm_spp_tail_fwd(const dfm_spp_desc *desc, const void *const *pooled
 /* the depth loss's targets: LiDAR depth map and box-id mask, and the box-membership operators (dfm_depth_*,
  * dfm_points_in_boxes): likewise */
 #include "dfm_hip_depth_targets.h"
+/* the optimizer step: the gradients' global norm, the clip and AdamW with fp32 masters over one multi-tensor table
+ * (dfm_grad_sqnorm, dfm_adamw_step, dfm_grad_scale): likewise */
+#include "dfm_hip_optim.h"
 
 #ifdef __cplusplus
 }
