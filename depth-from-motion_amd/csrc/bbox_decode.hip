@@ -427,7 +427,6 @@ extern "C" DFM_API int dfm_anchor_head_candidates(const dfm_anchor_head_desc *d,
     hd.reg.p = reg;
     hd.dir.p = dir;
     const bool cut = hd.k < hd.n;
-    const bool bf16 = d->dtype == DFM_BF16;
     hipStream_t s = (hipStream_t)stream;
     if (cut) {
         const size_t need = carve(nullptr, hd.batch, hd.n, hd.k).total_bytes;
@@ -443,10 +442,9 @@ extern "C" DFM_API int dfm_anchor_head_candidates(const dfm_anchor_head_desc *d,
         }
         HIP_TRY(hipMemsetAsync(workspace, 0, sc.zero_bytes, s));
         const dim3 grid((unsigned)(((long long)hd.n + SPAN - 1) / SPAN), (unsigned)hd.batch), block(BLOCK);
-        if (bf16)
-            hipLaunchKernelGGL(keys_kernel<bf16_t>, grid, block, 0, s, hd, sc.keys, sc.hist);
-        else
-            hipLaunchKernelGGL(keys_kernel<float>, grid, block, 0, s, hd, sc.keys, sc.hist);
+        by_dtype(d->dtype, [&](auto t) {
+            hipLaunchKernelGGL(keys_kernel<decltype(t)>, grid, block, 0, s, hd, sc.keys, sc.hist);
+        });
         HIP_TRY(hipGetLastError());
         for (int level = 1; level <= 2; ++level) {
             hipLaunchKernelGGL(refine_kernel, grid, block, 0, s, hd.n, hd.k, level, (const uint32_t *)sc.keys, sc.hist);
@@ -462,12 +460,10 @@ extern "C" DFM_API int dfm_anchor_head_candidates(const dfm_anchor_head_desc *d,
     }
     const long long rows = (long long)hd.batch * hd.k;
     const dim3 grid((unsigned)((rows + BLOCK - 1) / BLOCK)), block(BLOCK);
-    if (bf16)
-        hipLaunchKernelGGL(decode_rows_kernel<bf16_t>, grid, block, 0, s, hd, cut ? 0 : 1, anchors, bboxes,
+    by_dtype(d->dtype, [&](auto t) {
+        hipLaunchKernelGGL(decode_rows_kernel<decltype(t)>, grid, block, 0, s, hd, cut ? 0 : 1, anchors, bboxes,
                            bboxes_for_nms, scores, (long long *)dir_scores, (long long *)topk_inds);
-    else
-        hipLaunchKernelGGL(decode_rows_kernel<float>, grid, block, 0, s, hd, cut ? 0 : 1, anchors, bboxes,
-                           bboxes_for_nms, scores, (long long *)dir_scores, (long long *)topk_inds);
+    });
     HIP_TRY(hipGetLastError());
     return DFM_OK;
 }

@@ -69,7 +69,7 @@ extern "C" DFM_API int dfm_bilinear_resize_bwd_nhwc(int32_t n, int32_t c, int32_
 {
     if (n <= 0 || c <= 0 || h_in <= 0 || w_in <= 0 || h_out <= 0 || w_out <= 0 || kh <= 0 || kw <= 0)
         return set_error(DFM_ERR_INVALID_ARG, "non-positive size in dfm_bilinear_resize_bwd_nhwc");
-    if (dtype != DFM_F32 && dtype != DFM_BF16) return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(dtype)) return rc;
     if (!gy || !gx || !row_idx || !row_w || !col_idx || !col_w) return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     const int vec = dtype == DFM_BF16 ? 8 : 4;
     if (c % vec || ((uintptr_t)gy & 15) || ((uintptr_t)gx & 15))
@@ -78,13 +78,11 @@ extern "C" DFM_API int dfm_bilinear_resize_bwd_nhwc(int32_t n, int32_t c, int32_
     const long long blocks = (total + 255) / 256;
     if (blocks >= (1ll << 31)) return set_error(DFM_ERR_UNSUPPORTED, "map too large");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DFM_F32)
-        hipLaunchKernelGGL(bilinear_bwd_nhwc_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, c, h_in, w_in, h_out,
-                           w_out, (const float *)gy, row_idx, row_w, kh, col_idx, col_w, kw, (float *)gx, total);
-    else
-        hipLaunchKernelGGL(bilinear_bwd_nhwc_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, c, h_in, w_in, h_out,
-                           w_out, (const bf16_t *)gy, row_idx, row_w, kh, col_idx, col_w, kw, (bf16_t *)gx, total);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(bilinear_bwd_nhwc_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, c, h_in, w_in, h_out,
+                           w_out, (const T *)gy, row_idx, row_w, kh, col_idx, col_w, kw, (T *)gx, total);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }

@@ -403,16 +403,13 @@ extern "C" DFM_API int dfm_conv3d_k3_c32_pack_weights(const void *weight, int32_
     if (weight_dtype != DFM_F32 && weight_dtype != DFM_BF16)
         return set_error(DFM_ERR_UNSUPPORTED, "weight dtype must be DFM_F32 or DFM_BF16");
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e;
     // (the zero page behind the fragments is the pack kernel's)
-    if (weight_dtype == DFM_F32)
-        hipLaunchKernelGGL(conv3d_pack_weights_kernel<float>, dim3(CV_NFRAG), dim3(64), 0, st,
-                           (const float *)weight, cin_total, cin_offset, transposed, (bf16_t *)packed);
-    else
-        hipLaunchKernelGGL(conv3d_pack_weights_kernel<bf16_t>, dim3(CV_NFRAG), dim3(64), 0, st,
-                           (const bf16_t *)weight, cin_total, cin_offset, transposed, (bf16_t *)packed);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(weight_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(conv3d_pack_weights_kernel<T>, dim3(CV_NFRAG), dim3(64), 0, st, (const T *)weight,
+                           cin_total, cin_offset, transposed, (bf16_t *)packed);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -444,8 +441,7 @@ extern "C" DFM_API int dfm_conv3d_k3_c32_to1_fwd(int32_t n, int32_t d, int32_t h
     hipLaunchKernelGGL((conv3d_k3_c32_kernel<false, false, false, true>), dim3(g.tiles_w * g.tiles_h, nchunks, n),
                        dim3(256), lds, (hipStream_t)stream, g, (const bf16_t *)x, wfrag, (const float *)nullptr,
                        out, zero, (float *)nullptr CV_TRACE_ARG);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -519,8 +515,7 @@ static int conv_c32_impl(int32_t n, int32_t d, int32_t h, int32_t w, const void 
     else if (stats) { if (acc_in) CV_LAUNCH(false, true, true); else CV_LAUNCH(false, false, true); }
     else { if (acc_in) CV_LAUNCH(false, true, false); else CV_LAUNCH(false, false, false); }
 #undef CV_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 

@@ -790,18 +790,16 @@ static int g_pack_impl(const void *weight, int32_t weight_dtype, int32_t cin, in
     if (weight_dtype != DFM_F32 && weight_dtype != DFM_BF16)
         return set_error(DFM_ERR_UNSUPPORTED, "weight dtype must be DFM_F32 or DFM_BF16");
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e;   // (the zero page behind the cin * cout * 27 fragments' elements is the pack kernel's)
+    // (the zero page behind the cin * cout * 27 fragments' elements is the pack kernel's)
     const int cw = cout % 64 == 0 ? 2 : 1;
     const int cts = cout / (32 * cw), nchunk = cin / 32;
     dim3 grid(cts * nchunk * 27 * 2, cw);
-    if (weight_dtype == DFM_F32)
-        hipLaunchKernelGGL(conv3d_g_pack_kernel<float>, grid, dim3(64), 0, st, (const float *)weight, cout, cin,
-                           cw, swap, flip, (bf16_t *)packed, w2d);
-    else
-        hipLaunchKernelGGL(conv3d_g_pack_kernel<bf16_t>, grid, dim3(64), 0, st, (const bf16_t *)weight, cout,
-                           cin, cw, swap, flip, (bf16_t *)packed, w2d);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(weight_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(conv3d_g_pack_kernel<T>, grid, dim3(64), 0, st, (const T *)weight, cout, cin, cw, swap,
+                           flip, (bf16_t *)packed, w2d);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -865,22 +863,6 @@ static int conv3d_g_launch(const dfm_conv3d_desc *desc, const void *x, const voi
         else if (fast) G_LAUNCH1(CW_, PFW_, false, true);                                            \
         else G_LAUNCH1(CW_, PFW_, false, false);                                                     \
     } while (0)
-#define G_LAUNCH_OLD(CW_, PFW_)                                                                      \
-    do {                                                                                             \
-        if (f32) {                                                                                   \
-            const int rc_ = ensure_dynamic_lds((const void *)conv3d_g_kernel<CW_, PFW_, true>, 160 * 1024); \
-            if (rc_ != DFM_OK) return rc_;                                                           \
-            hipLaunchKernelGGL((conv3d_g_kernel<CW_, PFW_, true>), grid, dim3(256), lds, st, pl.g,   \
-                               (const bf16_t *)x, wfrag, scale, shift, (const bf16_t *)residual,     \
-                               (bf16_t *)out, zero);                                                 \
-        } else {                                                                                     \
-            const int rc_ = ensure_dynamic_lds((const void *)conv3d_g_kernel<CW_, PFW_>, 160 * 1024); \
-            if (rc_ != DFM_OK) return rc_;                                                           \
-            hipLaunchKernelGGL((conv3d_g_kernel<CW_, PFW_>), grid, dim3(256), lds, st, pl.g,         \
-                               (const bf16_t *)x, wfrag, scale, shift, (const bf16_t *)residual,     \
-                               (bf16_t *)out, zero);                                                 \
-        }                                                                                            \
-    } while (0)
     if (pl.cw == 2) {
         switch (pl.pfw) {
         case 1: G_LAUNCH(2, 1); break;
@@ -898,9 +880,7 @@ static int conv3d_g_launch(const dfm_conv3d_desc *desc, const void *x, const voi
     }
 #undef G_LAUNCH
 #undef G_LAUNCH1
-#undef G_LAUNCH_OLD
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 

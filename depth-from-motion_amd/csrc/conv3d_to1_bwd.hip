@@ -221,14 +221,12 @@ extern "C" DFM_API int dfm_conv3d_to1_bwd_data(int32_t n, int32_t d, int32_t h, 
     if ((uintptr_t)grad_x & 15) return set_error(DFM_ERR_INVALID_ARG, "grad_x must be 16-byte aligned");
     const int wgs = (int)std::min<long long>(2048, ((long long)g.nrows + 7) / 8);
     hipStream_t st = (hipStream_t)stream;
-    if (weight_dtype == DFM_F32)
-        hipLaunchKernelGGL(conv3d_to1_bwd_data_kernel<float>, dim3(wgs), dim3(256), 0, st, g, (const bf16_t *)grad_out,
-                           (const float *)weight, (bf16_t *)grad_x);
-    else
-        hipLaunchKernelGGL(conv3d_to1_bwd_data_kernel<bf16_t>, dim3(wgs), dim3(256), 0, st, g, (const bf16_t *)grad_out,
-                           (const bf16_t *)weight, (bf16_t *)grad_x);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(weight_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(conv3d_to1_bwd_data_kernel<T>, dim3(wgs), dim3(256), 0, st, g, (const bf16_t *)grad_out,
+                           (const T *)weight, (bf16_t *)grad_x);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -252,13 +250,11 @@ extern "C" DFM_API int dfm_conv3d_to1_wgrad(int32_t n, int32_t d, int32_t h, int
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(conv3d_to1_wgrad_kernel, dim3(wgs), dim3(256), 0, st, g, (const bf16_t *)x,
                        (const bf16_t *)grad_out, (float *)workspace);
-    if (out_dtype == DFM_F32)
-        hipLaunchKernelGGL(conv3d_to1_wgrad_reduce_kernel<float>, dim3(27), dim3(1024), 0, st, (const float *)workspace,
-                           wgs, (float *)grad_weight);
-    else
-        hipLaunchKernelGGL(conv3d_to1_wgrad_reduce_kernel<bf16_t>, dim3(27), dim3(1024), 0, st, (const float *)workspace,
-                           wgs, (bf16_t *)grad_weight);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(out_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(conv3d_to1_wgrad_reduce_kernel<T>, dim3(27), dim3(1024), 0, st, (const float *)workspace,
+                           wgs, (T *)grad_weight);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }

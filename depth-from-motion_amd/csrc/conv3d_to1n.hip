@@ -229,18 +229,14 @@ extern "C" DFM_API int dfm_conv3d_to1_norm_fwd(int32_t n, int32_t d, int32_t h, 
     if (nchunks > 65535) return set_error(DFM_ERR_UNSUPPORTED, "too many depth chunks");
     dim3 grid(g.tiles_w * g.tiles_h, nchunks, n);
     hipStream_t st = (hipStream_t)stream;
-    if (weight_dtype == DFM_F32) {
-        const int rc = ensure_dynamic_lds((const void *)conv3d_to1_norm_kernel<float>, T1_LDS);
-        if (rc != DFM_OK) return rc;
-        hipLaunchKernelGGL(conv3d_to1_norm_kernel<float>, grid, dim3(256), T1_LDS, st, g, (const bf16_t *)x, coef,
-                           (const float *)weight, (bf16_t *)out);
-    } else {
-        const int rc = ensure_dynamic_lds((const void *)conv3d_to1_norm_kernel<bf16_t>, T1_LDS);
-        if (rc != DFM_OK) return rc;
-        hipLaunchKernelGGL(conv3d_to1_norm_kernel<bf16_t>, grid, dim3(256), T1_LDS, st, g, (const bf16_t *)x, coef,
-                           (const bf16_t *)weight, (bf16_t *)out);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    const int rc = by_dtype(weight_dtype, [&](auto t) {
+        using T = decltype(t);
+        if (int rc = ensure_dynamic_lds((const void *)conv3d_to1_norm_kernel<T>, T1_LDS)) return rc;
+        hipLaunchKernelGGL(conv3d_to1_norm_kernel<T>, grid, dim3(256), T1_LDS, st, g, (const bf16_t *)x, coef,
+                           (const T *)weight, (bf16_t *)out);
+        return (int)DFM_OK;
+    });
+    if (rc != DFM_OK) return rc;
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }

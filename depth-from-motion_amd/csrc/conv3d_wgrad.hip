@@ -532,16 +532,13 @@ static int wgrad_impl(const dfm_conv3d_wgrad_desc *desc, const void *g, const vo
         if (pl.flat) W_LAUNCH(2, true); else W_LAUNCH(2, false);
     }
 #undef W_LAUNCH
-    if (out_dtype == DFM_BF16)
-        hipLaunchKernelGGL(conv3d_wgrad_reduce_kernel<bf16_t>, dim3(27 * 1024 / 64, pl.pairs), dim3(256), 0, st,
+    by_dtype(out_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(conv3d_wgrad_reduce_kernel<T>, dim3(27 * 1024 / 64, pl.pairs), dim3(256), 0, st,
                            (const float *)workspace, pl.g.wgs_per_pair, pl.g.b_tiles, desc->b, pl.swap, pl.flat,
-                           (bf16_t *)out);
-    else
-        hipLaunchKernelGGL(conv3d_wgrad_reduce_kernel<float>, dim3(27 * 1024 / 64, pl.pairs), dim3(256), 0, st,
-                           (const float *)workspace, pl.g.wgs_per_pair, pl.g.b_tiles, desc->b, pl.swap, pl.flat,
-                           (float *)out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+                           (T *)out);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 

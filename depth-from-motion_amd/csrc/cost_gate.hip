@@ -221,14 +221,12 @@ extern "C" DFM_API int dfm_cost_gate_mfma_pack_weights(const void *weight, int32
     if (num_depths <= 0 || num_depths > CG_MAX_D) return set_error(DFM_ERR_UNSUPPORTED, "1 .. 96 depth planes");
     if ((uintptr_t)packed & 15) return set_error(DFM_ERR_INVALID_ARG, "packed weights must be 16-byte aligned");
     const dim3 grid((unsigned)(((num_depths + 31) / 32) * ((2 * num_depths + 15) / 16)));
-    if (weight_dtype == DFM_BF16)
-        hipLaunchKernelGGL(cost_gate_mfma_pack_kernel<bf16_t>, grid, dim3(64), 0, (hipStream_t)stream, (int)num_depths,
-                           (const bf16_t *)weight, (bf16_t *)packed);
-    else
-        hipLaunchKernelGGL(cost_gate_mfma_pack_kernel<float>, grid, dim3(64), 0, (hipStream_t)stream, (int)num_depths,
-                           (const float *)weight, (bf16_t *)packed);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(weight_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(cost_gate_mfma_pack_kernel<T>, grid, dim3(64), 0, (hipStream_t)stream, (int)num_depths,
+                           (const T *)weight, (bf16_t *)packed);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -248,8 +246,7 @@ extern "C" DFM_API int dfm_cost_gate_mfma_fwd(int32_t batch, int32_t num_depths,
                        (const bf16_t *)stereo, (const bf16_t *)mono, (const uint4 *)packed_weights, (bf16_t *)out)
     if (mb == 1) CGM_LAUNCH(1); else if (mb == 2) CGM_LAUNCH(2); else CGM_LAUNCH(3);
 #undef CGM_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -271,14 +268,12 @@ extern "C" DFM_API int dfm_cost_gate_pack_weights(const void *weight, int32_t we
     if ((uintptr_t)packed & 15) return set_error(DFM_ERR_INVALID_ARG, "packed weights must be 16-byte aligned");
     const int n = 2 * num_depths * cg_pitch(num_depths);
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (weight_dtype == DFM_BF16)
-        hipLaunchKernelGGL(cost_gate_pack_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (int)num_depths,
-                           (const bf16_t *)weight, (float *)packed);
-    else
-        hipLaunchKernelGGL(cost_gate_pack_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (int)num_depths,
-                           (const float *)weight, (float *)packed);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(weight_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(cost_gate_pack_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (int)num_depths,
+                           (const T *)weight, (float *)packed);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -288,23 +283,21 @@ extern "C" DFM_API int dfm_cost_gate_fwd(int32_t batch, int32_t num_depths, int6
 {
     if (batch <= 0 || num_depths <= 0 || hw <= 0) return set_error(DFM_ERR_INVALID_ARG, "non-positive size");
     if (!stereo || !mono || !packed_weights || !out) return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
-    if (dtype != DFM_F32 && dtype != DFM_BF16) return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(dtype)) return rc;
     if (num_depths > CG_MAX_D) return set_error(DFM_ERR_UNSUPPORTED, "more than 96 depth planes");
     if ((uintptr_t)packed_weights & 15) return set_error(DFM_ERR_INVALID_ARG, "packed weights must be 16-byte aligned");
     if (batch > 65535 || (hw + 63) / 64 > 0x7fffffffll) return set_error(DFM_ERR_UNSUPPORTED, "grid too large");
     const int lds = (int)dfm_cost_gate_weight_bytes(num_depths);
     const dim3 grid((unsigned)((hw + 63) / 64), (unsigned)batch);
     hipStream_t st = (hipStream_t)stream;
-#define CG_LAUNCH(T)                                                                                         \
-    do {                                                                                                     \
-        const int rc_ = ensure_dynamic_lds((const void *)cost_gate_kernel<T>, lds);                          \
-        if (rc_ != DFM_OK) return rc_;                                                                       \
-        hipLaunchKernelGGL((cost_gate_kernel<T>), grid, dim3(256), lds, st, (int)num_depths, (long long)hw,  \
-                           (const T *)stereo, (const T *)mono, (const float4 *)packed_weights, (T *)out);    \
-    } while (0)
-    if (dtype == DFM_BF16) CG_LAUNCH(bf16_t); else CG_LAUNCH(float);
-#undef CG_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    const int rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (int rc = ensure_dynamic_lds((const void *)cost_gate_kernel<T>, lds)) return rc;
+        hipLaunchKernelGGL((cost_gate_kernel<T>), grid, dim3(256), lds, st, (int)num_depths, (long long)hw,
+                           (const T *)stereo, (const T *)mono, (const float4 *)packed_weights, (T *)out);
+        return (int)DFM_OK;
+    });
+    if (rc != DFM_OK) return rc;
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }

@@ -194,8 +194,7 @@ DFM_API int dfm_depth_head_fwd(int32_t batch, int32_t d, int32_t h, int32_t w, i
 {
     if (batch <= 0 || d <= 0 || h <= 0 || w <= 0 || scale <= 0)
         return set_error(DFM_ERR_INVALID_ARG, "non-positive size in dfm_depth_head_fwd");
-    if (dtype != DFM_F32 && dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(dtype)) return rc;
     if (!cost || !depth_samples || !depth_volumes || !softmax || !depth_preds)
         return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     if (batch > 65535 || (long long)h * scale * w * scale >= (1ll << 31) || (long long)d * scale > 4000)
@@ -209,18 +208,16 @@ DFM_API int dfm_depth_head_fwd(int32_t batch, int32_t d, int32_t h, int32_t w, i
     if ((w * scale) % 4 == 0 && bases % (4 * esz) == 0) v = 4;
     dim3 grid((npix / v + 127) / 128, batch);
     hipStream_t st = (hipStream_t)stream;
-#define DFM_DH_LAUNCH(T, V)                                                                       \
-    hipLaunchKernelGGL((depth_head_kernel<T, V, true>), grid, dim3(128), (size_t)d * scale * 16, st, (const T *)cost, d, h, \
-                       w, scale, depth_samples, (T *)depth_volumes, (T *)softmax, (T *)depth_preds,   \
-                       (float *)nullptr, (float *)nullptr)
-    if (dtype == DFM_F32) {
-        if (v == 4) DFM_DH_LAUNCH(float, 4); else DFM_DH_LAUNCH(float, 1);
-    } else {
-        if (v == 4) DFM_DH_LAUNCH(bf16_t, 4); else DFM_DH_LAUNCH(bf16_t, 1);
-    }
-#undef DFM_DH_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        by_bool(v == 4, [&](auto four) {
+            constexpr int V = decltype(four)::value ? 4 : 1;
+            hipLaunchKernelGGL((depth_head_kernel<T, V, true>), grid, dim3(128), (size_t)d * scale * 16, st,
+                               (const T *)cost, d, h, w, scale, depth_samples, (T *)depth_volumes, (T *)softmax,
+                               (T *)depth_preds, (float *)nullptr, (float *)nullptr);
+        });
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -230,8 +227,7 @@ DFM_API int dfm_depth_head_stats_fwd(int32_t batch, int32_t d, int32_t h, int32_
 {
     if (batch <= 0 || d <= 0 || h <= 0 || w <= 0 || scale <= 0)
         return set_error(DFM_ERR_INVALID_ARG, "non-positive size in dfm_depth_head_stats_fwd");
-    if (dtype != DFM_F32 && dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(dtype)) return rc;
     if (!cost || !depth_samples || !col_max || !col_sum)
         return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     if (batch > 65535 || (long long)h * scale * w * scale >= (1ll << 31) || (long long)d * scale > 4000)
@@ -239,21 +235,15 @@ DFM_API int dfm_depth_head_stats_fwd(int32_t batch, int32_t d, int32_t h, int32_
     const int npix = h * scale * w * scale;
     // one pixel per lane: there are no wide stores to feed, and 4x the waves hide the latency of the
     // cached cost loads and of expf (a B = 1 launch with 4 pixels per lane has 1.5 waves per SIMD)
-    const bool vec4 = false;
     dim3 grid((npix + 127) / 128, batch);
     hipStream_t st = (hipStream_t)stream;
-#define DFM_DH_LAUNCH(T, V)                                                                            \
-    hipLaunchKernelGGL((depth_head_kernel<T, V, false>), grid, dim3(128), (size_t)d * scale * 16, st, (const T *)cost, d, h, \
-                       w, scale, depth_samples, (T *)nullptr, (T *)nullptr, (T *)depth_preds, col_max,  \
-                       col_sum)
-    if (dtype == DFM_F32) {
-        if (vec4) DFM_DH_LAUNCH(float, 4); else DFM_DH_LAUNCH(float, 1);
-    } else {
-        if (vec4) DFM_DH_LAUNCH(bf16_t, 4); else DFM_DH_LAUNCH(bf16_t, 1);
-    }
-#undef DFM_DH_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((depth_head_kernel<T, 1, false>), grid, dim3(128), (size_t)d * scale * 16, st,
+                           (const T *)cost, d, h, w, scale, depth_samples, (T *)nullptr, (T *)nullptr,
+                           (T *)depth_preds, col_max, col_sum);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -449,8 +439,7 @@ extern "C" DFM_API int dfm_depth_head_bwd(int32_t batch, int32_t d, int32_t h, i
 {
     if (batch <= 0 || d <= 0 || h <= 0 || w <= 0 || scale <= 0)
         return set_error(DFM_ERR_INVALID_ARG, "non-positive size in dfm_depth_head_bwd");
-    if (dtype != DFM_F32 && dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(dtype)) return rc;
     if (!cost || !depth_samples || !grad_cost)
         return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     hipStream_t st = (hipStream_t)stream;
@@ -462,33 +451,24 @@ extern "C" DFM_API int dfm_depth_head_bwd(int32_t batch, int32_t d, int32_t h, i
         const size_t lds = (size_t)d * nr * ncol * sizeof(float);
         if (lds <= 64 * 1024 && batch <= 65535 && (Ho + 3) / 4 <= 65535) {
             dim3 tg((Wo + 63) / 64, (Ho + 3) / 4, batch);
-            if (dtype == DFM_F32)
-                hipLaunchKernelGGL(depth_head_bwd_tile_kernel<float>, tg, dim3(256), lds, st,
-                                   (const float *)cost, d, h, w, scale, depth_samples,
-                                   (const float *)grad_volumes, (const float *)grad_softmax,
-                                   (const float *)grad_preds, grad_cost, nr, ncol);
-            else
-                hipLaunchKernelGGL(depth_head_bwd_tile_kernel<bf16_t>, tg, dim3(256), lds, st,
-                                   (const bf16_t *)cost, d, h, w, scale, depth_samples,
-                                   (const bf16_t *)grad_volumes, (const bf16_t *)grad_softmax,
-                                   (const bf16_t *)grad_preds, grad_cost, nr, ncol);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+            by_dtype(dtype, [&](auto t) {
+                using T = decltype(t);
+                hipLaunchKernelGGL(depth_head_bwd_tile_kernel<T>, tg, dim3(256), lds, st, (const T *)cost, d, h, w,
+                                   scale, depth_samples, (const T *)grad_volumes, (const T *)grad_softmax,
+                                   (const T *)grad_preds, grad_cost, nr, ncol);
+            });
+            HIP_TRY(hipGetLastError());
             return DFM_OK;
         }
     }
     const int npix = h * scale * w * scale;
     dim3 grid((npix + 255) / 256, batch);
-    if (dtype == DFM_F32)
-        hipLaunchKernelGGL(depth_head_bwd_kernel<float>, grid, dim3(256), 0, st, (const float *)cost,
-                           d, h, w, scale, depth_samples, (const float *)grad_volumes,
-                           (const float *)grad_softmax, (const float *)grad_preds, grad_cost);
-    else
-        hipLaunchKernelGGL(depth_head_bwd_kernel<bf16_t>, grid, dim3(256), 0, st,
-                           (const bf16_t *)cost, d, h, w, scale, depth_samples,
-                           (const bf16_t *)grad_volumes, (const bf16_t *)grad_softmax,
-                           (const bf16_t *)grad_preds, grad_cost);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(depth_head_bwd_kernel<T>, grid, dim3(256), 0, st, (const T *)cost, d, h, w, scale,
+                           depth_samples, (const T *)grad_volumes, (const T *)grad_softmax, (const T *)grad_preds,
+                           grad_cost);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }

@@ -236,8 +236,7 @@ int check(const dfm_depth_loss_desc *d)
     if (!d) return set_error(DFM_ERR_INVALID_ARG, "desc is NULL");
     if (d->batch <= 0 || d->num_depths <= 0 || d->h <= 0 || d->w <= 0)
         return set_error(DFM_ERR_INVALID_ARG, "non-positive size in dfm_depth_loss_desc");
-    if (d->dtype != DFM_F32 && d->dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(d->dtype)) return rc;
     if (d->target < DFM_DL_LINEAR || d->target > DFM_DL_LAPLACIAN)
         return set_error(DFM_ERR_INVALID_ARG, "unknown target kind");
     if (d->target >= DFM_DL_GAUSSIAN && !(d->sigma > 0.0f))
@@ -272,16 +271,13 @@ extern "C" DFM_API int dfm_depth_loss_fwd(const dfm_depth_loss_desc *d, const vo
     const DlGeom g = geom(d);
     dim3 grid((d->h * d->w + 255) / 256, d->batch);
     hipStream_t st = (hipStream_t)stream;
-    if (d->dtype == DFM_F32)
-        hipLaunchKernelGGL((depth_loss_kernel<float, false, false>), grid, dim3(256), 0, st, g,
-                           (const float *)depth_volumes, depth_img, depth_samples,
-                           (const float *)nullptr, pixel_loss, valid, (float *)nullptr, (float *)nullptr);
-    else
-        hipLaunchKernelGGL((depth_loss_kernel<bf16_t, false, false>), grid, dim3(256), 0, st, g,
-                           (const bf16_t *)depth_volumes, depth_img, depth_samples,
-                           (const float *)nullptr, pixel_loss, valid, (bf16_t *)nullptr, (float *)nullptr);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(d->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((depth_loss_kernel<T, false, false>), grid, dim3(256), 0, st, g, (const T *)depth_volumes,
+                           depth_img, depth_samples, (const float *)nullptr, pixel_loss, valid, (T *)nullptr,
+                           (float *)nullptr);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -297,16 +293,13 @@ extern "C" DFM_API int dfm_depth_loss_bwd(const dfm_depth_loss_desc *d, const vo
     const DlGeom g = geom(d);
     dim3 grid((d->h * d->w + 255) / 256, d->batch);
     hipStream_t st = (hipStream_t)stream;
-    if (d->dtype == DFM_F32)
-        hipLaunchKernelGGL((depth_loss_kernel<float, true, false>), grid, dim3(256), 0, st, g,
-                           (const float *)depth_volumes, depth_img, depth_samples, grad_pixel_loss,
-                           (float *)nullptr, (unsigned char *)nullptr, (float *)grad_volumes, (float *)nullptr);
-    else
-        hipLaunchKernelGGL((depth_loss_kernel<bf16_t, true, false>), grid, dim3(256), 0, st, g,
-                           (const bf16_t *)depth_volumes, depth_img, depth_samples, grad_pixel_loss,
-                           (float *)nullptr, (unsigned char *)nullptr, (bf16_t *)grad_volumes, (float *)nullptr);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(d->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((depth_loss_kernel<T, true, false>), grid, dim3(256), 0, st, g, (const T *)depth_volumes,
+                           depth_img, depth_samples, grad_pixel_loss, (float *)nullptr, (unsigned char *)nullptr,
+                           (T *)grad_volumes, (float *)nullptr);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -334,16 +327,12 @@ extern "C" DFM_API int dfm_depth_loss_fused_fwd(const dfm_depth_loss_desc *d, co
         return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     dim3 grid((d->h * d->w + 255) / 256, d->batch);
     hipStream_t st = (hipStream_t)stream;
-    if (d->dtype == DFM_F32)
-        hipLaunchKernelGGL((depth_loss_kernel<float, false, true>), grid, dim3(256), 0, st, g, (const float *)cost,
-                           depth_img, depth_samples, (const float *)nullptr, pixel_loss, valid, (float *)nullptr,
-                           (float *)nullptr);
-    else
-        hipLaunchKernelGGL((depth_loss_kernel<bf16_t, false, true>), grid, dim3(256), 0, st, g, (const bf16_t *)cost,
-                           depth_img, depth_samples, (const float *)nullptr, pixel_loss, valid, (bf16_t *)nullptr,
-                           (float *)nullptr);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(d->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((depth_loss_kernel<T, false, true>), grid, dim3(256), 0, st, g, (const T *)cost, depth_img,
+                           depth_samples, (const float *)nullptr, pixel_loss, valid, (T *)nullptr, (float *)nullptr);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -358,15 +347,12 @@ extern "C" DFM_API int dfm_depth_loss_fused_bwd(const dfm_depth_loss_desc *d, co
         return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     dim3 grid((d->h * d->w + 255) / 256, d->batch);
     hipStream_t st = (hipStream_t)stream;
-    if (d->dtype == DFM_F32)
-        hipLaunchKernelGGL((depth_loss_kernel<float, true, true>), grid, dim3(256), 0, st, g, (const float *)cost,
-                           depth_img, depth_samples, grad_pixel_loss, (float *)nullptr, (unsigned char *)nullptr,
-                           (float *)nullptr, grad_cost);
-    else
-        hipLaunchKernelGGL((depth_loss_kernel<bf16_t, true, true>), grid, dim3(256), 0, st, g, (const bf16_t *)cost,
-                           depth_img, depth_samples, grad_pixel_loss, (float *)nullptr, (unsigned char *)nullptr,
-                           (bf16_t *)nullptr, grad_cost);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(d->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((depth_loss_kernel<T, true, true>), grid, dim3(256), 0, st, g, (const T *)cost, depth_img,
+                           depth_samples, grad_pixel_loss, (float *)nullptr, (unsigned char *)nullptr, (T *)nullptr,
+                           grad_cost);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }

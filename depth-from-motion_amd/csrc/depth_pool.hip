@@ -68,8 +68,7 @@ int pool_launch(bool bwd, const void *a, void *b, long long outer, int k, long l
         hipLaunchKernelGGL(depth_pool_bwd_kernel<T>, dim3(grid), dim3(256), 0, st, (const T *)a, (T *)b, outer, k, iv);
     else
         hipLaunchKernelGGL(depth_pool_fwd_kernel<T>, dim3(grid), dim3(256), 0, st, (const T *)a, (T *)b, outer, k, iv);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -77,7 +76,7 @@ int pool_check(const void *a, const void *b, int64_t outer, int32_t k, int64_t i
 {
     if (!a || !b) return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     if (outer <= 0 || k <= 0 || inner <= 0) return set_error(DFM_ERR_INVALID_ARG, "non-positive size");
-    if (dtype != DFM_F32 && dtype != DFM_BF16) return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(dtype)) return rc;
     const int vec = dtype == DFM_BF16 ? 8 : 4;
     if (inner % vec || ((uintptr_t)a & 15) || ((uintptr_t)b & 15))
         return set_error(DFM_ERR_UNSUPPORTED, "depth pool: inner extent in whole 16-byte vectors, 16-byte aligned buffers");
@@ -91,8 +90,9 @@ extern "C" DFM_API int dfm_depth_pool_fwd(int64_t outer, int32_t k, int64_t inne
 {
     const int rc = pool_check(x, y, outer, k, inner, dtype);
     if (rc != DFM_OK) return rc;
-    return dtype == DFM_BF16 ? pool_launch<bf16_t>(false, x, y, outer, k, inner, (hipStream_t)stream)
-                             : pool_launch<float>(false, x, y, outer, k, inner, (hipStream_t)stream);
+    return by_dtype(dtype, [&](auto t) {
+        return pool_launch<decltype(t)>(false, x, y, outer, k, inner, (hipStream_t)stream);
+    });
 }
 
 extern "C" DFM_API int dfm_depth_pool_bwd(int64_t outer, int32_t k, int64_t inner, int32_t dtype, const void *grad_y,
@@ -100,6 +100,7 @@ extern "C" DFM_API int dfm_depth_pool_bwd(int64_t outer, int32_t k, int64_t inne
 {
     const int rc = pool_check(grad_y, grad_x, outer, k, inner, dtype);
     if (rc != DFM_OK) return rc;
-    return dtype == DFM_BF16 ? pool_launch<bf16_t>(true, grad_y, grad_x, outer, k, inner, (hipStream_t)stream)
-                             : pool_launch<float>(true, grad_y, grad_x, outer, k, inner, (hipStream_t)stream);
+    return by_dtype(dtype, [&](auto t) {
+        return pool_launch<decltype(t)>(true, grad_y, grad_x, outer, k, inner, (hipStream_t)stream);
+    });
 }

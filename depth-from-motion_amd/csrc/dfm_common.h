@@ -102,17 +102,25 @@ template <> struct elem<bf16_t> {
 // Host side: a launch templated on the element type, or on a bool, written ONCE -- f is a generic lambda that
 // takes a value of the element type (float{} / bf16_t{}: T = decltype of it) or a std::bool_constant
 // (its ::value is a constant expression).  dtype has been validated (DFM_F32 or DFM_BF16) before.
+// Both return what f returns, so a launch that can fail before it starts (ensure_dynamic_lds) hands its status out:
+// `const int rc = by_dtype(dtype, [&](auto t) { ...; return (int)DFM_OK; });`  (a new entry point).
 template <typename F>
-inline void by_dtype(int32_t dtype, F &&f)
+inline decltype(auto) by_dtype(int32_t dtype, F &&f)
 {
-    if (dtype == DFM_F32) f(float{});
-    else f(bf16_t{});
+    if (dtype == DFM_F32) return f(float{});
+    else return f(bf16_t{});
 }
 template <typename F>
-inline void by_bool(bool on, F &&f)
+inline decltype(auto) by_bool(bool on, F &&f)
 {
-    if (on) f(std::true_type{});
-    else f(std::false_type{});
+    if (on) return f(std::true_type{});
+    else return f(std::false_type{});
+}
+// the element-type check of every entry point that takes a dtype
+inline int check_dtype(int32_t dtype)
+{
+    if (dtype == DFM_F32 || dtype == DFM_BF16) return DFM_OK;
+    return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
 }
 
 // unpack one 16-byte channel block into CB floats

@@ -457,8 +457,7 @@ static int f2v_fwd_impl(const dfm_f2v_desc *d, const void *stereo, const void *s
     if (d->batch <= 0 || d->channels <= 0 || d->d <= 0 || d->h <= 0 || d->w <= 0 || d->nz <= 0 ||
         d->ny <= 0 || d->nx <= 0 || d->sem_channels < 0)
         return set_error(DFM_ERR_INVALID_ARG, "non-positive size in dfm_f2v_desc");
-    if (d->dtype != DFM_F32 && d->dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(d->dtype)) return rc;
     const bool want_disp = d->stereo_atten || (d->sem_channels > 0 && !d->no_sem_atten);
     if (!stereo || !coords || !cam2img || !out || (d->sem_channels > 0 && !sem) || (want_disp && !softmax && !fh.cost))
         return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
@@ -517,8 +516,7 @@ static int f2v_fwd_impl(const dfm_f2v_desc *d, const void *stereo, const void *s
                                (const T *)sem, coords, cam2img, (T *)out, fh);
         });
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 

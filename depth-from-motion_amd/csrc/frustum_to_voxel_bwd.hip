@@ -483,8 +483,7 @@ static int f2v_bwd_impl(const dfm_f2v_desc *d, const void *grad_out, const void 
                         float *grad_sem, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!d) return set_error(DFM_ERR_INVALID_ARG, "desc is NULL");
-    if (d->dtype != DFM_F32 && d->dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(d->dtype)) return rc;
     if (!grad_out || !coords || !cam2img || !grad_stereo || (d->sem_channels > 0 && !grad_sem) ||
         ((d->stereo_atten || (d->sem_channels > 0 && !d->no_sem_atten)) && !softmax && !fh.cost))
         return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
@@ -502,8 +501,7 @@ static int f2v_bwd_impl(const dfm_f2v_desc *d, const void *grad_out, const void 
         const long long vox = (long long)d->d * d->h * d->w, pix = (long long)d->hsem * d->wsem;
         const F2vPmLayout ws = f2v_pm_layout(d, sizeof(float));
         float *gst_pm = (float *)workspace, *gsem_pm = (float *)((char *)workspace + ws.first);
-        hipError_t e = hipMemsetAsync(workspace, 0, ws.first + ws.second, st);
-        if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+        HIP_TRY(hipMemsetAsync(workspace, 0, ws.first + ws.second, st));
         const dim3 grid((unsigned)((N + F2V_VT - 1) / F2V_VT), d->batch);
         by_dtype(d->dtype, [&](auto t) {
             using T = decltype(t);
@@ -518,8 +516,7 @@ static int f2v_bwd_impl(const dfm_f2v_desc *d, const void *grad_out, const void 
             hipLaunchKernelGGL(add_from_pixel_major_kernel<float>, t2, dim3(256), 0, st, gsem_pm, grad_sem,
                                d->sem_channels, pix);
         }
-        e = hipGetLastError();
-        if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+        HIP_TRY(hipGetLastError());
         return DFM_OK;
     }
     // no workspace (or more channels than the LDS tile holds): lane-per-voxel scatter
@@ -529,8 +526,7 @@ static int f2v_bwd_impl(const dfm_f2v_desc *d, const void *grad_out, const void 
         hipLaunchKernelGGL(f2v_bwd_kernel<T>, grid, dim3(256), 0, st, g, (const T *)grad_out, (const T *)softmax, fh,
                            coords, cam2img, grad_stereo, grad_sem);
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -574,8 +570,7 @@ static int f2v_bwd_gather_impl(const dfm_f2v_desc *d, const void *grad_out, cons
                                float *grad_sem, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!d) return set_error(DFM_ERR_INVALID_ARG, "desc is NULL");
-    if (d->dtype != DFM_F32 && d->dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(d->dtype)) return rc;
     if (!grad_out || !coords || !grid6 || !cam2img || !grad_stereo || !workspace || (d->sem_channels > 0 && !grad_sem))
         return set_error(DFM_ERR_INVALID_ARG, "NULL pointer");
     const bool need_disp = d->stereo_atten || (d->sem_channels > 0 && !d->no_sem_atten);
@@ -618,8 +613,7 @@ static int f2v_bwd_gather_impl(const dfm_f2v_desc *d, const void *grad_out, cons
             });
         });
     });
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 

@@ -26,6 +26,7 @@
 #include "dfm_common.h"
 
 #include <algorithm>
+#include <initializer_list>
 
 using namespace dfm;
 
@@ -785,12 +786,109 @@ __global__ __launch_bounds__(256) void bn_bwd_coef_kernel(const float *__restric
     o[2] = rs * (rs * mu * Bm - Am);
 }
 
-// the shape checks every BatchNorm entry point shares: C whole 16-byte vectors, a power of two of them, C <= 256
-bool bn_channels_ok(int32_t c, int32_t dtype)
+// the shape every channels-last kernel needs, GroupNorm's and BatchNorm's alike: C whole 16-byte vectors, a power of
+// two of them, C <= 256, every tensor 16-byte aligned (an absent one, NULL, passes)
+bool channels_last_ok(int32_t c, int32_t dtype, std::initializer_list<const void *> tensors)
 {
     const int vec = dtype == DFM_BF16 ? 8 : 4;
     const int nvb = c / vec;
-    return c % vec == 0 && c <= 256 && (nvb & (nvb - 1)) == 0;
+    uintptr_t bits = 0;
+    for (const void *p : tensors) bits |= (uintptr_t)p;
+    return c % vec == 0 && c <= 256 && (nvb & (nvb - 1)) == 0 && (bits & 15) == 0;
+}
+const char GN_CL_NEEDS[] = "channels-last GroupNorm needs C = 16-byte vectors x a power of two, C <= 256";
+const char BN_CL_NEEDS[] = "channels-last BatchNorm needs C = 16-byte vectors x a power of two, C <= 256";
+
+// the prologue of every entry point with tensors, in the order that decides which error wins: sizes, element type,
+// pointers, workspace (`need` bytes, named `needs` in the message)
+int args_ok(const char *name, bool sizes, int32_t dtype, bool pointers, size_t workspace_bytes, size_t need,
+            const char *needs)
+{
+    if (!sizes) return set_errorf(DFM_ERR_INVALID_ARG, "bad sizes in %s", name);
+    if (int rc = check_dtype(dtype)) return rc;
+    if (!pointers) return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
+    if (workspace_bytes < need) return set_errorf(DFM_ERR_WORKSPACE, "workspace smaller than %s", needs);
+    return DFM_OK;
+}
+int gn_args_ok(const char *name, int32_t n, int32_t c, int64_t spatial, int32_t groups, int32_t dtype, bool pointers,
+               size_t workspace_bytes)
+{
+    return args_ok(name, n > 0 && c > 0 && spatial > 0 && groups > 0 && c % groups == 0, dtype, pointers,
+                   workspace_bytes, dfm_group_norm_workspace_bytes(n, c, spatial, groups),
+                   "dfm_group_norm_workspace_bytes");
+}
+int bn_args_ok(const char *name, int32_t c, int64_t rows, int32_t dtype, bool pointers, size_t workspace_bytes)
+{
+    return args_ok(name, c > 0 && rows >= 0, dtype, pointers, workspace_bytes, dfm_batch_norm_workspace_bytes(c, rows),
+                   "dfm_batch_norm_workspace_bytes");
+}
+
+// The channels-last passes, each launch stated once for GroupNorm (n samples, `groups`) and for BatchNorm, which is
+// the same with n = 1, groups = c, spatial = rows.
+
+// moment partials [n * groups][splits][3] of x
+void launch_stats_cl(int32_t n, int32_t c, int64_t spatial, int32_t groups, int splits, int32_t dtype, const void *x,
+                     float *partial, hipStream_t st)
+{
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(gn_stats_cl_kernel<T>, dim3(splits, n), dim3(256), 0, st, (const T *)x, (long long)spatial,
+                           c, groups, splits, partial);
+    });
+}
+
+// gn_apply_cl_kernel over `merged` triples, one per (sample, group): the second pass of both channels-last forwards
+// and of the gathered BatchNorm.  The kernel slices the tensor by ITS grid and merges `1` partial per group
+void launch_apply_cl(int32_t n, int32_t c, int64_t spatial, int32_t groups, float eps, int32_t dtype, int32_t relu,
+                     const void *x, const float *gamma, const float *beta, const void *residual, void *y, float *mean,
+                     float *rstd, const float *merged, hipStream_t st)
+{
+    const int asplits = pick_splits_cl((long long)spatial * c);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(gn_apply_cl_kernel<T>, dim3(asplits, n), dim3(256), 0, st, (const T *)x, (long long)spatial,
+                           c, groups, asplits, eps, merged, gamma, beta, relu, (T *)y, mean, rstd, 1,
+                           (const T *)residual);
+    });
+}
+
+// backward: the tensors both passes read.  y != NULL: the ReLU mask is y > 0; relu with y == NULL and beta: the mask
+// is recomputed from x with the forward's expression (`xmask`)
+struct BwdClArgs {
+    int32_t n, c;
+    int64_t spatial;
+    int32_t groups, dtype, relu;
+    const void *grad_y, *x, *y;
+    const float *mean, *rstd, *gamma, *beta;
+    bool xmask() const { return relu && !y && beta; }
+};
+
+// partials [n * c][splits][2]: sum(dy'), sum(dy' * xhat)
+void launch_bwd_stats_cl(const BwdClArgs &a, int splits, float *partial, hipStream_t st)
+{
+    by_dtype(a.dtype, [&](auto t) {
+        using T = decltype(t);
+        by_bool(a.xmask(), [&](auto xm) {
+            hipLaunchKernelGGL((gn_bwd_stats_cl_kernel<T, decltype(xm)::value>), dim3(splits, a.n), dim3(256), 0, st,
+                               (const T *)a.grad_y, (const T *)a.x, (const T *)a.y, (long long)a.spatial, a.c,
+                               a.groups, splits, a.relu, a.mean, a.rstd, a.gamma, a.beta, partial);
+        });
+    });
+}
+
+// dx = k1 g + k2 x + k3 from `coef`, and the residual's gradient
+void launch_bwd_apply_cl(const BwdClArgs &a, const float *coef, void *grad_x, void *grad_residual, hipStream_t st)
+{
+    const int asplits = pick_splits_cl((long long)a.spatial * a.c);
+    by_dtype(a.dtype, [&](auto t) {
+        using T = decltype(t);
+        by_bool(a.xmask(), [&](auto xm) {
+            hipLaunchKernelGGL((gn_bwd_apply_cl_kernel<T, decltype(xm)::value>), dim3(asplits, a.n), dim3(256), 0, st,
+                               (const T *)a.grad_y, (const T *)a.x, (const T *)a.y, (long long)a.spatial, a.c,
+                               a.groups, asplits, a.relu, coef, a.mean, a.rstd, a.gamma, a.beta, (T *)grad_x,
+                               (T *)grad_residual);
+        });
+    });
 }
 
 }  // namespace
@@ -806,11 +904,9 @@ DFM_API int dfm_group_norm_coefficients(int32_t n, int32_t c, int32_t groups, fl
     if (!partials || !gamma || !beta || !coef) return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     hipLaunchKernelGGL(gn_coefficients_kernel, dim3(n * groups), dim3(256), 0, (hipStream_t)stream, partials, splits,
                        c, groups, eps, gamma, beta, coef);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
-
 
 DFM_API size_t dfm_group_norm_workspace_bytes(int32_t n, int32_t c, int64_t spatial, int32_t groups)
 {
@@ -827,14 +923,9 @@ DFM_API int dfm_group_norm_fwd(int32_t n, int32_t c, int64_t spatial, int32_t gr
                                const float *beta, void *y, float *mean, float *rstd,
                                void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (n <= 0 || c <= 0 || spatial <= 0 || groups <= 0 || c % groups)
-        return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_group_norm_fwd");
-    if (dtype != DFM_F32 && dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
-    if (!x || !gamma || !beta || !y || !mean || !rstd || !workspace)
-        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
-    if (workspace_bytes < dfm_group_norm_workspace_bytes(n, c, spatial, groups))
-        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_group_norm_workspace_bytes");
+    if (int rc = gn_args_ok("dfm_group_norm_fwd", n, c, spatial, groups, dtype,
+                            x && gamma && beta && y && mean && rstd && workspace, workspace_bytes))
+        return rc;
     if ((long long)n * groups > 65535) return set_error(DFM_ERR_UNSUPPORTED, "n*groups > 65535");
     const int cpg = c / groups;
     const long long L = (long long)cpg * spatial;
@@ -842,21 +933,13 @@ DFM_API int dfm_group_norm_fwd(int32_t n, int32_t c, int64_t spatial, int32_t gr
     dim3 grid(splits, n * groups);
     hipStream_t st = (hipStream_t)stream;
     float *partial = (float *)workspace;
-    if (dtype == DFM_F32) {
-        hipLaunchKernelGGL(gn_stats_kernel<float>, grid, dim3(256), 0, st, (const float *)x, L, splits,
-                           partial);
-        hipLaunchKernelGGL(gn_apply_kernel<float>, grid, dim3(256), 0, st, (const float *)x, L,
-                           (long long)spatial, cpg, groups, splits, eps, partial, gamma, beta, relu,
-                           (float *)y, mean, rstd);
-    } else {
-        hipLaunchKernelGGL(gn_stats_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t *)x, L,
-                           splits, partial);
-        hipLaunchKernelGGL(gn_apply_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t *)x, L,
-                           (long long)spatial, cpg, groups, splits, eps, partial, gamma, beta, relu,
-                           (bf16_t *)y, mean, rstd);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(gn_stats_kernel<T>, grid, dim3(256), 0, st, (const T *)x, L, splits, partial);
+        hipLaunchKernelGGL(gn_apply_kernel<T>, grid, dim3(256), 0, st, (const T *)x, L, (long long)spatial, cpg,
+                           groups, splits, eps, partial, gamma, beta, relu, (T *)y, mean, rstd);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -876,43 +959,18 @@ DFM_API int dfm_group_norm_fwd_channels_last_res(int32_t n, int32_t c, int64_t s
                                                  const void *residual, void *y, float *mean, float *rstd,
                                                  void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (n <= 0 || c <= 0 || spatial <= 0 || groups <= 0 || c % groups)
-        return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_group_norm_fwd_channels_last");
-    if (dtype != DFM_F32 && dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
-    if (!x || !gamma || !beta || !y || !mean || !rstd || !workspace)
-        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
-    if (workspace_bytes < dfm_group_norm_workspace_bytes(n, c, spatial, groups))
-        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_group_norm_workspace_bytes");
-    const int vec = dtype == DFM_BF16 ? 8 : 4;
-    const int nvb = c / vec;
-    if (c % vec || c > 256 || (nvb & (nvb - 1)) || n > 65535 ||
-        ((uintptr_t)x & 15) || ((uintptr_t)y & 15))
-        return set_error(DFM_ERR_UNSUPPORTED,
-                         "channels-last GroupNorm needs C = 16-byte vectors x a power of two, C <= 256");
-    const int splits = pick_splits_cl((long long)spatial * c);  // workgroups of the statistics and of the apply pass
-    const int asplits = splits;
-    dim3 grid(splits, n), agrid(asplits, n);
+    if (int rc = gn_args_ok("dfm_group_norm_fwd_channels_last", n, c, spatial, groups, dtype,
+                            x && gamma && beta && y && mean && rstd && workspace, workspace_bytes))
+        return rc;
+    if (n > 65535 || !channels_last_ok(c, dtype, {x, y})) return set_error(DFM_ERR_UNSUPPORTED, GN_CL_NEEDS);
+    const int splits = pick_splits_cl((long long)spatial * c);  // workgroups of the statistics pass
     hipStream_t st = (hipStream_t)stream;
     float *partial = (float *)workspace;
     float *merged = partial + (size_t)n * groups * splits * 3;  // behind the partials
-    if (dtype == DFM_F32)
-        hipLaunchKernelGGL(gn_stats_cl_kernel<float>, grid, dim3(256), 0, st, (const float *)x,
-                           (long long)spatial, c, groups, splits, partial);
-    else
-        hipLaunchKernelGGL(gn_stats_cl_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t *)x,
-                           (long long)spatial, c, groups, splits, partial);
+    launch_stats_cl(n, c, spatial, groups, splits, dtype, x, partial, st);
     hipLaunchKernelGGL(gn_merge_partials_kernel, dim3(n * groups), dim3(256), 0, st, partial, splits, merged);
-    if (dtype == DFM_F32)
-        hipLaunchKernelGGL(gn_apply_cl_kernel<float>, agrid, dim3(256), 0, st, (const float *)x,
-                           (long long)spatial, c, groups, asplits, eps, merged, gamma, beta, relu,
-                           (float *)y, mean, rstd, 1, (const float *)residual);
-    else
-        hipLaunchKernelGGL(gn_apply_cl_kernel<bf16_t>, agrid, dim3(256), 0, st, (const bf16_t *)x,
-                           (long long)spatial, c, groups, asplits, eps, merged, gamma, beta, relu,
-                           (bf16_t *)y, mean, rstd, 1, (const bf16_t *)residual);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    launch_apply_cl(n, c, spatial, groups, eps, dtype, relu, x, gamma, beta, residual, y, mean, rstd, merged, st);
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -935,36 +993,18 @@ DFM_API int dfm_group_norm_apply_channels_last_res(int32_t n, int32_t c, int64_t
                                                    const float *partials, int32_t splits, void *workspace,
                                                    size_t workspace_bytes, void *stream)
 {
-    if (n <= 0 || c <= 0 || spatial <= 0 || groups <= 0 || c % groups || splits <= 0)
-        return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_group_norm_apply_channels_last");
-    if (dtype != DFM_F32 && dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
-    if (!x || !gamma || !beta || !y || !mean || !rstd || !partials || !workspace)
-        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
-    if (workspace_bytes < (size_t)n * groups * 3 * sizeof(float))
-        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than n*groups*3 floats");
-    const int vec = dtype == DFM_BF16 ? 8 : 4;
-    const int nvb = c / vec;
-    if (c % vec || c > 256 || (nvb & (nvb - 1)) || n > 65535 ||
-        ((uintptr_t)x & 15) || ((uintptr_t)y & 15))
-        return set_error(DFM_ERR_UNSUPPORTED,
-                         "channels-last GroupNorm needs C = 16-byte vectors x a power of two, C <= 256");
+    // a producer's partials come in: the workspace holds the merged triples only
+    if (int rc = args_ok("dfm_group_norm_apply_channels_last",
+                         n > 0 && c > 0 && spatial > 0 && groups > 0 && c % groups == 0 && splits > 0, dtype,
+                         x && gamma && beta && y && mean && rstd && partials && workspace, workspace_bytes,
+                         (size_t)n * groups * 3 * sizeof(float), "n*groups*3 floats"))
+        return rc;
+    if (n > 65535 || !channels_last_ok(c, dtype, {x, y})) return set_error(DFM_ERR_UNSUPPORTED, GN_CL_NEEDS);
     hipStream_t st = (hipStream_t)stream;
     float *merged = (float *)workspace;
     hipLaunchKernelGGL(gn_merge_partials_kernel, dim3(n * groups), dim3(256), 0, st, partials, splits, merged);
-    const int asplits = pick_splits_cl((long long)spatial * c);  // workgroups of the apply pass
-    dim3 grid(asplits, n);
-    // the apply kernel slices the tensor by ITS grid and merges `1` partial per group
-    if (dtype == DFM_F32)
-        hipLaunchKernelGGL(gn_apply_cl_kernel<float>, grid, dim3(256), 0, st, (const float *)x,
-                           (long long)spatial, c, groups, asplits, eps, merged, gamma, beta, relu,
-                           (float *)y, mean, rstd, 1, (const float *)residual);
-    else
-        hipLaunchKernelGGL(gn_apply_cl_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t *)x,
-                           (long long)spatial, c, groups, asplits, eps, merged, gamma, beta, relu,
-                           (bf16_t *)y, mean, rstd, 1, (const bf16_t *)residual);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    launch_apply_cl(n, c, spatial, groups, eps, dtype, relu, x, gamma, beta, residual, y, mean, rstd, merged, st);
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -974,39 +1014,26 @@ DFM_API int dfm_group_norm_bwd(int32_t n, int32_t c, int64_t spatial, int32_t gr
                                void *grad_x, float *grad_gamma, float *grad_beta, void *workspace,
                                size_t workspace_bytes, void *stream)
 {
-    if (n <= 0 || c <= 0 || spatial <= 0 || groups <= 0 || c % groups)
-        return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_group_norm_bwd");
-    if (dtype != DFM_F32 && dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
-    if (!grad_y || !x || (relu && !y) || !mean || !rstd || !gamma || !grad_x || !grad_gamma ||
-        !grad_beta || !workspace)
-        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
-    if (workspace_bytes < dfm_group_norm_workspace_bytes(n, c, spatial, groups))
-        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_group_norm_workspace_bytes");
+    if (int rc = gn_args_ok("dfm_group_norm_bwd", n, c, spatial, groups, dtype,
+                            grad_y && x && (!relu || y) && mean && rstd && gamma && grad_x && grad_gamma &&
+                                grad_beta && workspace,
+                            workspace_bytes))
+        return rc;
     if ((long long)n * c > 65535) return set_error(DFM_ERR_UNSUPPORTED, "n*c > 65535");
     const int cpg = c / groups;
     const int splits = pick_splits(spatial);
     dim3 grid(splits, n * c);
     hipStream_t st = (hipStream_t)stream;
     float *partial = (float *)workspace;
-    if (dtype == DFM_F32) {
-        hipLaunchKernelGGL(gn_bwd_stats_kernel<float>, grid, dim3(256), 0, st, (const float *)grad_y,
-                           (const float *)x, (const float *)y, (long long)spatial, c, cpg, splits, relu,
-                           mean, rstd, partial);
-        hipLaunchKernelGGL(gn_bwd_apply_kernel<float>, grid, dim3(256), 0, st, (const float *)grad_y,
-                           (const float *)x, (const float *)y, (long long)spatial, c, cpg, splits, relu,
-                           mean, rstd, gamma, partial, (float *)grad_x, grad_gamma, grad_beta);
-    } else {
-        hipLaunchKernelGGL(gn_bwd_stats_kernel<bf16_t>, grid, dim3(256), 0, st,
-                           (const bf16_t *)grad_y, (const bf16_t *)x, (const bf16_t *)y,
-                           (long long)spatial, c, cpg, splits, relu, mean, rstd, partial);
-        hipLaunchKernelGGL(gn_bwd_apply_kernel<bf16_t>, grid, dim3(256), 0, st,
-                           (const bf16_t *)grad_y, (const bf16_t *)x, (const bf16_t *)y,
-                           (long long)spatial, c, cpg, splits, relu, mean, rstd, gamma, partial,
-                           (bf16_t *)grad_x, grad_gamma, grad_beta);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(gn_bwd_stats_kernel<T>, grid, dim3(256), 0, st, (const T *)grad_y, (const T *)x,
+                           (const T *)y, (long long)spatial, c, cpg, splits, relu, mean, rstd, partial);
+        hipLaunchKernelGGL(gn_bwd_apply_kernel<T>, grid, dim3(256), 0, st, (const T *)grad_y, (const T *)x,
+                           (const T *)y, (long long)spatial, c, cpg, splits, relu, mean, rstd, gamma, partial,
+                           (T *)grad_x, grad_gamma, grad_beta);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -1015,46 +1042,25 @@ static int gn_bwd_cl_impl(int32_t n, int32_t c, int64_t spatial, int32_t groups,
                           const float *gamma, const float *beta, void *grad_x, void *grad_residual,
                           float *grad_gamma, float *grad_beta, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const bool xmask = relu && !y && beta;
-    if (n <= 0 || c <= 0 || spatial <= 0 || groups <= 0 || c % groups)
-        return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_group_norm_bwd_channels_last");
-    if (dtype != DFM_F32 && dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
-    if (!grad_y || !x || (relu && !y && !beta) || !mean || !rstd || !gamma || !grad_x || !grad_gamma || !grad_beta ||
-        !workspace)
-        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
-    if (workspace_bytes < dfm_group_norm_workspace_bytes(n, c, spatial, groups))
-        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_group_norm_workspace_bytes");
-    const int vec = dtype == DFM_BF16 ? 8 : 4;
-    const int nvb = c / vec;
-    if (c % vec || c > 256 || (nvb & (nvb - 1)) || n > 65535 || (long long)n * groups > 2147483647ll ||
-        ((uintptr_t)x & 15) || ((uintptr_t)grad_y & 15) || ((uintptr_t)grad_x & 15) || ((uintptr_t)y & 15) ||
-        ((uintptr_t)grad_residual & 15))
-        return set_error(DFM_ERR_UNSUPPORTED,
-                         "channels-last GroupNorm needs C = 16-byte vectors x a power of two, C <= 256");
+    if (int rc = gn_args_ok("dfm_group_norm_bwd_channels_last", n, c, spatial, groups, dtype,
+                            grad_y && x && (!relu || y || beta) && mean && rstd && gamma && grad_x && grad_gamma &&
+                                grad_beta && workspace,
+                            workspace_bytes))
+        return rc;
+    if (n > 65535 || (long long)n * groups > 2147483647ll ||
+        !channels_last_ok(c, dtype, {x, grad_y, grad_x, y, grad_residual}))
+        return set_error(DFM_ERR_UNSUPPORTED, GN_CL_NEEDS);
     // (round 6: up to GN_BW_SPLITS workgroups in the statistics pass -- 256 were one per CU, one voxel in flight a lane)
-    const int asplits = pick_splits_cl((long long)spatial * c);
-    const int splits = std::min(GN_BW_SPLITS, asplits);
+    const int splits = std::min(GN_BW_SPLITS, pick_splits_cl((long long)spatial * c));
     hipStream_t st = (hipStream_t)stream;
     float *partial = (float *)workspace;
     float *coef = partial + (size_t)n * c * GN_BW_SPLITS * 2;
-    dim3 grid(splits, n), agrid(asplits, n);
-#define GN_BW(T_, X_)                                                                                             \
-    do {                                                                                                          \
-        hipLaunchKernelGGL((gn_bwd_stats_cl_kernel<T_, X_>), grid, dim3(256), 0, st, (const T_ *)grad_y,          \
-                           (const T_ *)x, (const T_ *)y, (long long)spatial, c, groups, splits, relu, mean, rstd, \
-                           gamma, beta, partial);                                                                 \
-        hipLaunchKernelGGL(gn_bwd_coef_kernel, dim3(groups), dim3(64), 0, st, partial, n, c, c / groups, splits,  \
-                           (long long)spatial, mean, rstd, gamma, coef, grad_gamma, grad_beta);                   \
-        hipLaunchKernelGGL((gn_bwd_apply_cl_kernel<T_, X_>), agrid, dim3(256), 0, st, (const T_ *)grad_y,         \
-                           (const T_ *)x, (const T_ *)y, (long long)spatial, c, groups, asplits, relu, coef, mean, \
-                           rstd, gamma, beta, (T_ *)grad_x, (T_ *)grad_residual);                                 \
-    } while (0)
-    if (dtype == DFM_F32) { if (xmask) GN_BW(float, true); else GN_BW(float, false); }
-    else { if (xmask) GN_BW(bf16_t, true); else GN_BW(bf16_t, false); }
-#undef GN_BW
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    const BwdClArgs a = {n, c, spatial, groups, dtype, relu, grad_y, x, y, mean, rstd, gamma, beta};
+    launch_bwd_stats_cl(a, splits, partial, st);
+    hipLaunchKernelGGL(gn_bwd_coef_kernel, dim3(groups), dim3(64), 0, st, partial, n, c, c / groups, splits,
+                       (long long)spatial, mean, rstd, gamma, coef, grad_gamma, grad_beta);
+    launch_bwd_apply_cl(a, coef, grad_x, grad_residual, st);
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -1097,28 +1103,17 @@ DFM_API size_t dfm_batch_norm_workspace_bytes(int32_t c, int64_t rows)
 DFM_API int dfm_batch_norm_stats_channels_last(int32_t c, int64_t rows, int32_t dtype, const void *x, float *stats,
                                                void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (c <= 0 || rows < 0) return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_batch_norm_stats_channels_last");
-    if (dtype != DFM_F32 && dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
-    if ((rows > 0 && !x) || !stats || !workspace) return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
-    if (workspace_bytes < dfm_batch_norm_workspace_bytes(c, rows))
-        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_batch_norm_workspace_bytes");
-    if (!bn_channels_ok(c, dtype) || ((uintptr_t)x & 15))
-        return set_error(DFM_ERR_UNSUPPORTED,
-                         "channels-last BatchNorm needs C = 16-byte vectors x a power of two, C <= 256");
+    if (int rc = bn_args_ok("dfm_batch_norm_stats_channels_last", c, rows, dtype,
+                            (rows == 0 || x) && stats && workspace, workspace_bytes))
+        return rc;
+    if (!channels_last_ok(c, dtype, {x})) return set_error(DFM_ERR_UNSUPPORTED, BN_CL_NEEDS);
     // rows == 0: one workgroup that loads nothing writes a count-0 partial, merged to (0, 0, 0)
     const int splits = pick_splits_cl(rows * c);
     hipStream_t st = (hipStream_t)stream;
     float *partial = (float *)workspace;
-    if (dtype == DFM_F32)
-        hipLaunchKernelGGL(gn_stats_cl_kernel<float>, dim3(splits, 1), dim3(256), 0, st, (const float *)x,
-                           (long long)rows, c, c, splits, partial);
-    else
-        hipLaunchKernelGGL(gn_stats_cl_kernel<bf16_t>, dim3(splits, 1), dim3(256), 0, st, (const bf16_t *)x,
-                           (long long)rows, c, c, splits, partial);
+    launch_stats_cl(1, c, rows, c, splits, dtype, x, partial, st);
     hipLaunchKernelGGL(gn_merge_partials_kernel, dim3(c), dim3(256), 0, st, partial, splits, stats);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -1128,29 +1123,15 @@ DFM_API int dfm_batch_norm_apply_gathered_channels_last(int32_t c, int64_t rows,
                                                         const float *gathered, void *y, float *mean, float *rstd,
                                                         float *moments, void *stream)
 {
-    if (c <= 0 || rows < 0 || world <= 0)
-        return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_batch_norm_apply_gathered_channels_last");
-    if (dtype != DFM_F32 && dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
-    if ((rows > 0 && (!x || !y)) || !gamma || !beta || !gathered || !mean || !rstd || !moments)
-        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
-    if (!bn_channels_ok(c, dtype) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)residual & 15))
-        return set_error(DFM_ERR_UNSUPPORTED,
-                         "channels-last BatchNorm needs C = 16-byte vectors x a power of two, C <= 256");
+    if (int rc = args_ok("dfm_batch_norm_apply_gathered_channels_last", c > 0 && rows >= 0 && world > 0, dtype,
+                         (rows == 0 || (x && y)) && gamma && beta && gathered && mean && rstd && moments, 0, 0, ""))
+        return rc;
+    if (!channels_last_ok(c, dtype, {x, y, residual})) return set_error(DFM_ERR_UNSUPPORTED, BN_CL_NEEDS);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(bn_merge_gathered_kernel, dim3(1), dim3(256), 0, st, gathered, world, c, moments);
-    // gn_apply_cl_kernel with one merged partial per channel: the arithmetic of the single-process pass
-    const int asplits = pick_splits_cl(rows * c);
-    if (dtype == DFM_F32)
-        hipLaunchKernelGGL(gn_apply_cl_kernel<float>, dim3(asplits, 1), dim3(256), 0, st, (const float *)x,
-                           (long long)rows, c, c, asplits, eps, moments, gamma, beta, relu, (float *)y, mean, rstd, 1,
-                           (const float *)residual);
-    else
-        hipLaunchKernelGGL(gn_apply_cl_kernel<bf16_t>, dim3(asplits, 1), dim3(256), 0, st, (const bf16_t *)x,
-                           (long long)rows, c, c, asplits, eps, moments, gamma, beta, relu, (bf16_t *)y, mean, rstd,
-                           1, (const bf16_t *)residual);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    // one sample, one group per channel, one merged partial per channel: the arithmetic of the single-process pass
+    launch_apply_cl(1, c, rows, c, eps, dtype, relu, x, gamma, beta, residual, y, mean, rstd, moments, st);
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -1160,31 +1141,18 @@ DFM_API int dfm_batch_norm_bwd_reduce_channels_last(int32_t c, int64_t rows, int
                                                     const float *beta, float *sums, void *workspace,
                                                     size_t workspace_bytes, void *stream)
 {
-    const bool xmask = relu && !y && beta;
-    if (c <= 0 || rows < 0)
-        return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_batch_norm_bwd_reduce_channels_last");
-    if (dtype != DFM_F32 && dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
-    if ((rows > 0 && (!grad_y || !x)) || (relu && !y && !beta) || !mean || !rstd || !gamma || !sums || !workspace)
-        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
-    if (workspace_bytes < dfm_batch_norm_workspace_bytes(c, rows))
-        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_batch_norm_workspace_bytes");
-    if (!bn_channels_ok(c, dtype) || ((uintptr_t)x & 15) || ((uintptr_t)grad_y & 15) || ((uintptr_t)y & 15))
-        return set_error(DFM_ERR_UNSUPPORTED,
-                         "channels-last BatchNorm needs C = 16-byte vectors x a power of two, C <= 256");
+    if (int rc = bn_args_ok("dfm_batch_norm_bwd_reduce_channels_last", c, rows, dtype,
+                            (rows == 0 || (grad_y && x)) && (!relu || y || beta) && mean && rstd && gamma && sums &&
+                                workspace,
+                            workspace_bytes))
+        return rc;
+    if (!channels_last_ok(c, dtype, {x, grad_y, y})) return set_error(DFM_ERR_UNSUPPORTED, BN_CL_NEEDS);
     const int splits = std::min(GN_BW_SPLITS, pick_splits_cl(rows * c));
     hipStream_t st = (hipStream_t)stream;
     float *partial = (float *)workspace;
-#define BN_RED(T_, X_)                                                                                            \
-    hipLaunchKernelGGL((gn_bwd_stats_cl_kernel<T_, X_>), dim3(splits, 1), dim3(256), 0, st, (const T_ *)grad_y,   \
-                       (const T_ *)x, (const T_ *)y, (long long)rows, c, c, splits, relu, mean, rstd, gamma, beta, \
-                       partial)
-    if (dtype == DFM_F32) { if (xmask) BN_RED(float, true); else BN_RED(float, false); }
-    else { if (xmask) BN_RED(bf16_t, true); else BN_RED(bf16_t, false); }
-#undef BN_RED
+    launch_bwd_stats_cl({1, c, rows, c, dtype, relu, grad_y, x, y, mean, rstd, gamma, beta}, splits, partial, st);
     hipLaunchKernelGGL(bn_bwd_sum_kernel, dim3(c), dim3(64), 0, st, partial, c, splits, sums);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -1195,33 +1163,19 @@ DFM_API int dfm_batch_norm_bwd_apply_channels_last(int32_t c, int64_t rows, int3
                                                    void *grad_x, void *grad_residual, void *workspace,
                                                    size_t workspace_bytes, void *stream)
 {
-    const bool xmask = relu && !y && beta;
-    if (c <= 0 || rows < 0)
-        return set_error(DFM_ERR_INVALID_ARG, "bad sizes in dfm_batch_norm_bwd_apply_channels_last");
-    if (dtype != DFM_F32 && dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
-    if ((rows > 0 && (!grad_y || !x || !grad_x)) || (relu && !y && !beta) || !mean || !rstd || !gamma || !sums ||
-        !count || !workspace)
-        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
-    if (workspace_bytes < dfm_batch_norm_workspace_bytes(c, rows))
-        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_batch_norm_workspace_bytes");
-    if (!bn_channels_ok(c, dtype) || ((uintptr_t)x & 15) || ((uintptr_t)grad_y & 15) || ((uintptr_t)grad_x & 15) ||
-        ((uintptr_t)y & 15) || ((uintptr_t)grad_residual & 15))
-        return set_error(DFM_ERR_UNSUPPORTED,
-                         "channels-last BatchNorm needs C = 16-byte vectors x a power of two, C <= 256");
-    const int asplits = pick_splits_cl(rows * c);
+    if (int rc = bn_args_ok("dfm_batch_norm_bwd_apply_channels_last", c, rows, dtype,
+                            (rows == 0 || (grad_y && x && grad_x)) && (!relu || y || beta) && mean && rstd && gamma &&
+                                sums && count && workspace,
+                            workspace_bytes))
+        return rc;
+    if (!channels_last_ok(c, dtype, {x, grad_y, grad_x, y, grad_residual}))
+        return set_error(DFM_ERR_UNSUPPORTED, BN_CL_NEEDS);
     hipStream_t st = (hipStream_t)stream;
     float *coef = (float *)workspace;
     hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3(1), dim3(256), 0, st, sums, count, c, mean, rstd, gamma, coef);
-#define BN_BA(T_, X_)                                                                                             \
-    hipLaunchKernelGGL((gn_bwd_apply_cl_kernel<T_, X_>), dim3(asplits, 1), dim3(256), 0, st, (const T_ *)grad_y,  \
-                       (const T_ *)x, (const T_ *)y, (long long)rows, c, c, asplits, relu, coef, mean, rstd, gamma, \
-                       beta, (T_ *)grad_x, (T_ *)grad_residual)
-    if (dtype == DFM_F32) { if (xmask) BN_BA(float, true); else BN_BA(float, false); }
-    else { if (xmask) BN_BA(bf16_t, true); else BN_BA(bf16_t, false); }
-#undef BN_BA
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    launch_bwd_apply_cl({1, c, rows, c, dtype, relu, grad_y, x, y, mean, rstd, gamma, beta}, coef, grad_x,
+                        grad_residual, st);
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 

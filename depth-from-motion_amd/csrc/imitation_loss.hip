@@ -367,8 +367,7 @@ int check(const dfm_imitation_desc *d)
         if (len != 0 && len != 1 && len != d->channels)
             return set_error(DFM_ERR_INVALID_ARG, "center_len / scale_len must be 0, 1 or channels");
     for (int32_t dt : {d->pred_dtype, d->target_dtype})
-        if (dt != DFM_F32 && dt != DFM_BF16)
-            return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+        if (int rc = check_dtype(dt)) return rc;
     if (d->channels > IMI_MAX_C) return set_error(DFM_ERR_UNSUPPORTED, "channels > 1024");
     if ((long long)d->ny * d->nx > (1ll << 30) || (long long)d->ny * d->nx * d->nz > (1ll << 31) - 1)
         return set_error(DFM_ERR_UNSUPPORTED, "grid too large");
@@ -475,12 +474,12 @@ extern "C" DFM_API int dfm_imitation_loss_fwd(const dfm_imitation_desc *d, const
         return set_errorf(DFM_ERR_WORKSPACE, "imitation loss needs %zu workspace bytes, got %zu", ws_bytes(g),
                           workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
-    const bool pb = d->pred_dtype == DFM_BF16, tb = d->target_dtype == DFM_BF16;
-#define IMI_FWD(TP, TT) \
-    launch_fwd<TP, TT>(g, pred, target, points, boxes, center, scale, new_center, mask, stats, workspace, st)
-    if (pb) return tb ? IMI_FWD(bf16_t, bf16_t) : IMI_FWD(bf16_t, float);
-    return tb ? IMI_FWD(float, bf16_t) : IMI_FWD(float, float);
-#undef IMI_FWD
+    return by_dtype(d->pred_dtype, [&](auto tp) {
+        return by_dtype(d->target_dtype, [&](auto tt) {
+            return launch_fwd<decltype(tp), decltype(tt)>(g, pred, target, points, boxes, center, scale, new_center,
+                                                          mask, stats, workspace, st);
+        });
+    });
 }
 
 extern "C" DFM_API int dfm_imitation_loss_bwd(const dfm_imitation_desc *d, const void *pred, const void *target,
@@ -495,10 +494,10 @@ extern "C" DFM_API int dfm_imitation_loss_bwd(const dfm_imitation_desc *d, const
         return set_error(DFM_ERR_INVALID_ARG, "NULL center / scale with a non-zero length");
     const ImiGeom g = geom(d);
     hipStream_t st = (hipStream_t)stream;
-    const bool pb = d->pred_dtype == DFM_BF16, tb = d->target_dtype == DFM_BF16;
-    const int cl = d->pred_channels_last;
-#define IMI_BWD(TP, TT) launch_bwd<TP, TT>(g, cl, pred, target, mask, center, scale, coef, grad_pred, st)
-    if (pb) return tb ? IMI_BWD(bf16_t, bf16_t) : IMI_BWD(bf16_t, float);
-    return tb ? IMI_BWD(float, bf16_t) : IMI_BWD(float, float);
-#undef IMI_BWD
+    return by_dtype(d->pred_dtype, [&](auto tp) {
+        return by_dtype(d->target_dtype, [&](auto tt) {
+            return launch_bwd<decltype(tp), decltype(tt)>(g, d->pred_channels_last, pred, target, mask, center, scale,
+                                                          coef, grad_pred, st);
+        });
+    });
 }

@@ -1168,8 +1168,7 @@ int check_desc(const dfm_sweep_desc *d)
     if (d->batch <= 0 || d->channels <= 0 || d->h_in <= 0 || d->w_in <= 0 || d->num_depths <= 0 ||
         d->h_out <= 0 || d->w_out <= 0)
         return set_error(DFM_ERR_INVALID_ARG, "non-positive size in dfm_sweep_desc");
-    if (d->dtype != DFM_F32 && d->dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(d->dtype)) return rc;
     if ((long long)d->h_in * d->w_in >= (1ll << 31) / 64)
         return set_error(DFM_ERR_UNSUPPORTED, "feature map too large for 32-bit tap offsets");
     if (d->batch > 32767) return set_error(DFM_ERR_UNSUPPORTED, "batch > 32767");
@@ -1446,11 +1445,9 @@ int run_fwd(const dfm_sweep_desc *desc, const Launch &L, const void *cur, const 
             const float *depths, const float *cam2img, const float *cam2img_inv,
             const float *cur2prev, void *out, void *workspace, hipStream_t st)
 {
-    if (desc->dtype == DFM_F32)
-        return launch_fwd<float>(desc, L, cur, prev, depths, cam2img, cam2img_inv, cur2prev, out,
-                                 workspace, st);
-    return launch_fwd<bf16_t>(desc, L, cur, prev, depths, cam2img, cam2img_inv, cur2prev, out,
-                              workspace, st);
+    return by_dtype(desc->dtype, [&](auto t) {
+        return launch_fwd<decltype(t)>(desc, L, cur, prev, depths, cam2img, cam2img_inv, cur2prev, out, workspace, st);
+    });
 }
 
 // blocked maps + spill lists (tile kernels), or the pixel-major maps of the strided-sweep kernel
@@ -1510,14 +1507,11 @@ int dfm::sweep_bwd_scatter_launch(const dfm_sweep_desc *desc, const void *grad_o
     const long long nb = (g.N + 255) / 256;
     if (nb > 2147483647ll) return set_error(DFM_ERR_UNSUPPORTED, "too many lattice points");
     dim3 grid((unsigned)nb, desc->batch);
-    if (desc->dtype == DFM_F32)
-        hipLaunchKernelGGL(sweep_bwd_kernel<float>, grid, dim3(256), 0, st, g,
-                           (const float *)grad_out, depths, cam2img, cam2img_inv, cur2prev,
-                           grad_cur, grad_prev);
-    else
-        hipLaunchKernelGGL(sweep_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, g,
-                           (const bf16_t *)grad_out, depths, cam2img, cam2img_inv, cur2prev,
-                           grad_cur, grad_prev);
+    by_dtype(desc->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(sweep_bwd_kernel<T>, grid, dim3(256), 0, st, g, (const T *)grad_out, depths, cam2img,
+                           cam2img_inv, cur2prev, grad_cur, grad_prev);
+    });
     return DFM_OK;
 }
 

@@ -572,13 +572,13 @@ int sweep_bwd_impl(const dfm_sweep_desc *desc, const void *grad_out, const float
         else if ((CWV) == 4) DFM_BWD_LAUNCH(T, 4, HALF, ROWS);                                       \
         else DFM_BWD_LAUNCH(T, 2, HALF, ROWS);                                                       \
     } while (0)
-        if (desc->dtype == DFM_F32) {
-            if (!skip_cur) DFM_BWD_HALF(float, 0, cw_cur, rows_cur);
-            DFM_BWD_HALF(float, 1, cw_prev, rows_prev);
-        } else {
-            if (!mfma && !skip_cur) DFM_BWD_HALF(bf16_t, 0, cw_cur, rows_cur);
-            DFM_BWD_HALF(bf16_t, 1, cw_prev, rows_prev);
-        }
+        rc = by_dtype(desc->dtype, [&](auto t) {  // (a `return rc` of the macros leaves this lambda)
+            using T = decltype(t);
+            if (!mfma && !skip_cur) DFM_BWD_HALF(T, 0, cw_cur, rows_cur);  // (mfma: bf16 only)
+            DFM_BWD_HALF(T, 1, cw_prev, rows_prev);
+            return (int)DFM_OK;
+        });
+        if (rc != DFM_OK) return rc;
 #undef DFM_BWD_HALF
 #undef DFM_BWD_LAUNCH
         HIP_TRY(hipGetLastError());
@@ -640,12 +640,11 @@ DFM_API int dfm_plane_sweep_bwd_channels_last(const dfm_sweep_desc *desc, const 
         // coalesced load per (plane, channel); read in place, a wave's 2-byte loads land 4C bytes apart
         // and every channel pass re-fetches the lines (config K: 2.2 ms instead of 1.2 ms)
         const dim3 grid((unsigned)((P + 63) / 64), (unsigned)((C2 + 8 * vec - 1) / (8 * vec)), desc->batch);
-        if (desc->dtype == DFM_BF16)
-            hipLaunchKernelGGL(unpack_pixel_major_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream,
-                               (const bf16_t *)grad_out, (bf16_t *)workspace, C2, P);
-        else
-            hipLaunchKernelGGL(unpack_pixel_major_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream,
-                               (const float *)grad_out, (float *)workspace, C2, P);
+        by_dtype(desc->dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(unpack_pixel_major_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream,
+                               (const T *)grad_out, (T *)workspace, C2, P);
+        });
         HIP_TRY(hipGetLastError());
         return sweep_bwd_impl(desc, workspace, depths, cam2img, cam2img_inv, cur2prev, grad_cur, grad_prev, stream,
                               nullptr, false);

@@ -400,8 +400,7 @@ int gather_launch(const dfm_sweep_desc *d, const void *grad_out, const float *de
     hipLaunchKernelGGL((sweep_bwd_scatter_planes_kernel<HALF, T, CL_IN, CL_OUT>), dim3(np, ychunks), dim3(256), 0, st, g,
                        fast, d->batch, (const float *)planes, (const T *)grad_out, depths, cam2img, cam2img_inv,
                        cur2prev, grad_map);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 

@@ -745,8 +745,7 @@ int sweep_clt_launch(const dfm_sweep_desc *d, const void *cur, const void *prev,
     const size_t mb = map_bytes(d);
     hipStream_t st = (hipStream_t)stream;
     char *w8 = (char *)workspace;
-    hipError_t e = hipMemsetAsync(w8, 0, zero, st);
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipMemsetAsync(w8, 0, zero, st));
     const long long HW = (long long)d->h_in * d->w_in;
     dim3 pg((unsigned)((HW + 63) / 64), (d->channels + 31) / 32, d->batch);
     ClGrid tg;
@@ -761,18 +760,14 @@ int sweep_clt_launch(const dfm_sweep_desc *d, const void *cur, const void *prev,
     if (nb > 2147483647ll) return set_error(DFM_ERR_UNSUPPORTED, "too many lattice points");
     const uint4 *cur_maps = (const uint4 *)(nhwc ? (const char *)cur : w8 + zero);
     const uint4 *prev_maps = (const uint4 *)(nhwc ? (const char *)prev : w8 + zero + mb);
-    if (nhwc) {
-        // channels-last maps are sampled where they lie
-    } else if (d->dtype == DFM_F32) {
-        hipLaunchKernelGGL(pack_pixel_major_kernel<float>, pg, dim3(256), 0, st, (const float *)cur,
-                           (float *)(w8 + zero), d->channels, d->channels, HW);
-        hipLaunchKernelGGL(pack_pixel_major_kernel<float>, pg, dim3(256), 0, st, (const float *)prev,
-                           (float *)(w8 + zero + mb), d->channels, d->channels, HW);
-    } else {
-        hipLaunchKernelGGL(pack_pixel_major_kernel<bf16_t>, pg, dim3(256), 0, st, (const bf16_t *)cur,
-                           (bf16_t *)(w8 + zero), d->channels, d->channels, HW);
-        hipLaunchKernelGGL(pack_pixel_major_kernel<bf16_t>, pg, dim3(256), 0, st, (const bf16_t *)prev,
-                           (bf16_t *)(w8 + zero + mb), d->channels, d->channels, HW);
+    if (!nhwc) {  // channels-last maps are sampled where they lie
+        by_dtype(d->dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(pack_pixel_major_kernel<T>, pg, dim3(256), 0, st, (const T *)cur, (T *)(w8 + zero),
+                               d->channels, d->channels, HW);
+            hipLaunchKernelGGL(pack_pixel_major_kernel<T>, pg, dim3(256), 0, st, (const T *)prev,
+                               (T *)(w8 + zero + mb), d->channels, d->channels, HW);
+        });
     }
     const bool timed = profile_mark(stream, false);
     const bool walking = walk && sweep_cltw_supported(d, out);
@@ -799,8 +794,7 @@ int sweep_clt_launch(const dfm_sweep_desc *d, const void *cur, const void *prev,
                            (const uint4 *)workspace, cur_maps, prev_maps, depths, cam2img, cam2img_inv, cur2prev,
                            (bf16_t *)out);
     if (timed) profile_mark(stream, true);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     sweep_set_last_kernel(walking ? 5 : 4);  // which body ran: 5 = the depth-walking kernel, 4 = per plane
     return DFM_OK;
 }
@@ -840,8 +834,7 @@ static int sweep_cl_impl(const dfm_sweep_desc *d, const void *cur, const void *p
         return set_error(DFM_ERR_UNSUPPORTED, "feature maps too large for 32-bit tap slots");
     hipStream_t st = (hipStream_t)stream;
     char *w8 = (char *)workspace;
-    hipError_t e = hipMemsetAsync(w8, 0, zero, st);
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipMemsetAsync(w8, 0, zero, st));
     const long long HW = (long long)d->h_in * d->w_in;
     dim3 pg((unsigned)((HW + 63) / 64), (d->channels + 31) / 32, d->batch);
     ClGrid tg;
@@ -858,32 +851,23 @@ static int sweep_cl_impl(const dfm_sweep_desc *d, const void *cur, const void *p
     if (nb > 2147483647ll) return set_error(DFM_ERR_UNSUPPORTED, "too many lattice points");
     const uint4 *cur_maps = (const uint4 *)(nhwc ? (const char *)cur : w8 + zero);
     const uint4 *prev_maps = (const uint4 *)(nhwc ? (const char *)prev : w8 + zero + mb);
-    if (nhwc) {
-        // the caller's maps ARE pixel-major: nothing to re-lay
-    } else if (d->dtype == DFM_F32) {
-        hipLaunchKernelGGL(pack_pixel_major_kernel<float>, pg, dim3(256), 0, st, (const float *)cur,
-                           (float *)(w8 + zero), d->channels, d->channels, HW);
-        hipLaunchKernelGGL(pack_pixel_major_kernel<float>, pg, dim3(256), 0, st, (const float *)prev,
-                           (float *)(w8 + zero + mb), d->channels, d->channels, HW);
-    } else {
-        hipLaunchKernelGGL(pack_pixel_major_kernel<bf16_t>, pg, dim3(256), 0, st, (const bf16_t *)cur,
-                           (bf16_t *)(w8 + zero), d->channels, d->channels, HW);
-        hipLaunchKernelGGL(pack_pixel_major_kernel<bf16_t>, pg, dim3(256), 0, st,
-                           (const bf16_t *)prev, (bf16_t *)(w8 + zero + mb), d->channels,
-                           d->channels, HW);
+    if (!nhwc) {  // the caller's maps ARE pixel-major: nothing to re-lay
+        by_dtype(d->dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(pack_pixel_major_kernel<T>, pg, dim3(256), 0, st, (const T *)cur, (T *)(w8 + zero),
+                               d->channels, d->channels, HW);
+            hipLaunchKernelGGL(pack_pixel_major_kernel<T>, pg, dim3(256), 0, st, (const T *)prev,
+                               (T *)(w8 + zero + mb), d->channels, d->channels, HW);
+        });
     }
     const bool timed = profile_mark(stream, false);
-    if (d->dtype == DFM_F32)
-        hipLaunchKernelGGL(sweep_cl_kernel<float>, dim3((unsigned)nb), dim3(256), 0, st, g, tg,
-                           (const uint4 *)workspace, cur_maps, prev_maps, depths, cam2img, cam2img_inv,
-                           cur2prev, (uint4 *)out);
-    else
-        hipLaunchKernelGGL(sweep_cl_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, st, g, tg,
-                           (const uint4 *)workspace, cur_maps, prev_maps, depths, cam2img, cam2img_inv,
-                           cur2prev, (uint4 *)out);
+    by_dtype(d->dtype, [&](auto t) {
+        hipLaunchKernelGGL(sweep_cl_kernel<decltype(t)>, dim3((unsigned)nb), dim3(256), 0, st, g, tg,
+                           (const uint4 *)workspace, cur_maps, prev_maps, depths, cam2img, cam2img_inv, cur2prev,
+                           (uint4 *)out);
+    });
     if (timed) profile_mark(stream, true);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -955,8 +939,7 @@ DFM_API int dfm_plane_sweep_bwd_cur_nhwc(const dfm_sweep_desc *d, const void *gr
     hipLaunchKernelGGL(sweep_bwdc_kernel, dim3((unsigned)nw), dim3(256), 0, (hipStream_t)stream, g, sweep_make_fast(d),
                        d->batch, tiles, passes, grad_cur, (unsigned)map_bytes(d), depths, cam2img, cam2img_inv, cur2prev,
                        (const float *)grad_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 

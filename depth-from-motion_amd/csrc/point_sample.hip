@@ -50,8 +50,6 @@ using namespace dfm;
 
 namespace {
 
-int fail_ps(int code, const char *msg) { return dfm::set_error(code, msg); }
-
 struct MvGeom {
     int32_t num_views, num_frames, C, Hf, Wf, nblk;
     int32_t nx, ny, nz;  // nz == 0 : flat (N, C) output
@@ -379,19 +377,18 @@ DFM_API int dfm_point_sample_mv_fwd(const dfm_mv_desc *d, const void *feats, con
                                     unsigned char *valid_out, void *workspace,
                                     size_t workspace_bytes, void *stream)
 {
-    if (!d) return fail_ps(DFM_ERR_INVALID_ARG, "desc is NULL");
+    if (!d) return set_error(DFM_ERR_INVALID_ARG, "desc is NULL");
     if (d->num_views <= 0 || d->num_frames <= 0 || d->channels <= 0 || d->feat_h <= 0 ||
         d->feat_w <= 0 || d->num_points <= 0)
-        return fail_ps(DFM_ERR_INVALID_ARG, "non-positive size in dfm_mv_desc");
-    if (d->dtype != DFM_F32 && d->dtype != DFM_BF16)
-        return fail_ps(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
-    if (d->mode != 0 && d->mode != 1) return fail_ps(DFM_ERR_UNSUPPORTED, "mode must be 0 or 1");
+        return set_error(DFM_ERR_INVALID_ARG, "non-positive size in dfm_mv_desc");
+    if (int rc = check_dtype(d->dtype)) return rc;
+    if (d->mode != 0 && d->mode != 1) return set_error(DFM_ERR_UNSUPPORTED, "mode must be 0 or 1");
     if (d->nz > 0 && (long long)d->nx * d->ny * d->nz != d->num_points)
-        return fail_ps(DFM_ERR_INVALID_ARG, "nx*ny*nz != num_points");
+        return set_error(DFM_ERR_INVALID_ARG, "nx*ny*nz != num_points");
     if (!feats || !points || !proj || !ori_w || !out)
-        return fail_ps(DFM_ERR_INVALID_ARG, "NULL device pointer");
+        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     if (!d->feats_channels_last && (!workspace || workspace_bytes < dfm_point_sample_mv_workspace_bytes(d)))
-        return fail_ps(DFM_ERR_WORKSPACE, "workspace smaller than dfm_point_sample_mv_workspace_bytes");
+        return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_point_sample_mv_workspace_bytes");
     MvGeom g;
     g.num_views = d->num_views; g.num_frames = d->num_frames; g.C = d->channels;
     g.Hf = d->feat_h; g.Wf = d->feat_w;
@@ -404,34 +401,28 @@ DFM_API int dfm_point_sample_mv_fwd(const dfm_mv_desc *d, const void *feats, con
     g.valid_sample = d->valid_sample;
     g.out_cl = d->out_channels_last && d->nz > 0 ? 1 : 0;
     if (!d->valid_sample && (d->num_views != 1 || d->num_frames != 1))
-        return fail_ps(DFM_ERR_UNSUPPORTED, "valid_sample=0 is only supported for a single view");
+        return set_error(DFM_ERR_UNSUPPORTED, "valid_sample=0 is only supported for a single view");
     hipStream_t st = (hipStream_t)stream;
     const int HW = d->feat_h * d->feat_w;
     const int nvf = d->num_views * d->num_frames;
     const int Cp = g.nblk * CB;
     dim3 pg((HW + 63) / 64, (Cp + 31) / 32, nvf);
     const long long nb = (g.N + 255) / 256;
-    if (nb > 2147483647ll) return fail_ps(DFM_ERR_UNSUPPORTED, "too many points");
+    if (nb > 2147483647ll) return set_error(DFM_ERR_UNSUPPORTED, "too many points");
     // channels-last view features ARE the pixel-major layout: sampled where they lie
     const bool in_place = d->feats_channels_last != 0;
     if (in_place && (d->channels % CB != 0 || ((uintptr_t)feats & 15)))
-        return fail_ps(DFM_ERR_UNSUPPORTED, "channels-last view features need whole 16-byte channel blocks");
+        return set_error(DFM_ERR_UNSUPPORTED, "channels-last view features need whole 16-byte channel blocks");
     const void *maps = in_place ? feats : workspace;
-    if (d->dtype == DFM_F32) {
+    by_dtype(d->dtype, [&](auto t) {
+        using T = decltype(t);
         if (!in_place)
-            hipLaunchKernelGGL(pack_pixel_major_kernel<float>, pg, dim3(256), 0, st,
-                               (const float *)feats, (float *)workspace, g.C, Cp, (long long)HW);
-        hipLaunchKernelGGL(mv_sample_kernel<float>, dim3((unsigned)nb), dim3(256), 0, st, g,
-                           (const uint4 *)maps, points, proj, ori_w, (float *)out, valid_out);
-    } else {
-        if (!in_place)
-            hipLaunchKernelGGL(pack_pixel_major_kernel<bf16_t>, pg, dim3(256), 0, st,
-                               (const bf16_t *)feats, (bf16_t *)workspace, g.C, Cp, (long long)HW);
-        hipLaunchKernelGGL(mv_sample_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, st, g,
-                           (const uint4 *)maps, points, proj, ori_w, (bf16_t *)out, valid_out);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_ps(DFM_ERR_HIP, hipGetErrorString(e));
+            hipLaunchKernelGGL(pack_pixel_major_kernel<T>, pg, dim3(256), 0, st, (const T *)feats, (T *)workspace,
+                               g.C, Cp, (long long)HW);
+        hipLaunchKernelGGL(mv_sample_kernel<T>, dim3((unsigned)nb), dim3(256), 0, st, g, (const uint4 *)maps, points,
+                           proj, ori_w, (T *)out, valid_out);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -440,21 +431,21 @@ DFM_API int dfm_point_sample_mv_fwd_batched(const dfm_mv_desc *descs, int32_t ba
                                             const float *points, int32_t points_per_sample, const float *proj,
                                             const float *ori_w, void *out, unsigned char *valid_out, void *stream)
 {
-    if (!descs || batch <= 0) return fail_ps(DFM_ERR_INVALID_ARG, "no descriptors");
+    if (!descs || batch <= 0) return set_error(DFM_ERR_INVALID_ARG, "no descriptors");
     const dfm_mv_desc *d = &descs[0];
     if (d->num_views <= 0 || d->num_frames <= 0 || d->channels <= 0 || d->feat_h <= 0 || d->feat_w <= 0 ||
         d->num_points <= 0)
-        return fail_ps(DFM_ERR_INVALID_ARG, "non-positive size in dfm_mv_desc");
-    if (!feats || !points || !proj || !ori_w || !out) return fail_ps(DFM_ERR_INVALID_ARG, "NULL device pointer");
+        return set_error(DFM_ERR_INVALID_ARG, "non-positive size in dfm_mv_desc");
+    if (!feats || !points || !proj || !ori_w || !out) return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     if (d->nz > 0 && (long long)d->nx * d->ny * d->nz != d->num_points)
-        return fail_ps(DFM_ERR_INVALID_ARG, "nx*ny*nz != num_points");
+        return set_error(DFM_ERR_INVALID_ARG, "nx*ny*nz != num_points");
     const int CB = d->dtype == DFM_BF16 ? 8 : 4;
     const int nblk = d->channels / CB;
     // what the lanes-per-voxel kernel covers; anything else: DFM_ERR_UNSUPPORTED, use dfm_point_sample_mv_fwd
     if ((d->dtype != DFM_F32 && d->dtype != DFM_BF16) || d->mode != 0 || !d->valid_sample || !d->feats_channels_last ||
         (d->nz > 0 && !d->out_channels_last) || d->channels % CB != 0 || (nblk != 4 && nblk != 8 && nblk != 16) ||
         d->num_views * d->num_frames > 4 * nblk || ((uintptr_t)feats & 15) || ((uintptr_t)out & 15))
-        return fail_ps(DFM_ERR_UNSUPPORTED, "batched lifting: nearest mode, valid_sample, channels-last views and volume, "
+        return set_error(DFM_ERR_UNSUPPORTED, "batched lifting: nearest mode, valid_sample, channels-last views and volume, "
                                             "4 / 8 / 16 channel blocks, <= 4 x blocks (frame, view) pairs");
     for (int b = 1; b < batch; ++b) {
         const dfm_mv_desc &e = descs[b];
@@ -463,7 +454,7 @@ DFM_API int dfm_point_sample_mv_fwd_batched(const dfm_mv_desc *descs, int32_t ba
             e.num_points != d->num_points || e.mode != d->mode || e.aggregate != d->aggregate ||
             e.valid_sample != d->valid_sample || e.dtype != d->dtype || e.out_channels_last != d->out_channels_last ||
             e.feats_channels_last != d->feats_channels_last)
-            return fail_ps(DFM_ERR_INVALID_ARG, "the samples of a batch differ in more than their image transform");
+            return set_error(DFM_ERR_INVALID_ARG, "the samples of a batch differ in more than their image transform");
     }
     MvGeom g;
     g.num_views = d->num_views; g.num_frames = d->num_frames; g.C = d->channels;
@@ -474,7 +465,7 @@ DFM_API int dfm_point_sample_mv_fwd_batched(const dfm_mv_desc *descs, int32_t ba
     hipStream_t st = (hipStream_t)stream;
     const int vpw = 64 / nblk;
     const long long nb = (g.N + 4 * vpw - 1) / (4 * vpw);
-    if (nb > 2147483647ll) return fail_ps(DFM_ERR_UNSUPPORTED, "too many points");
+    if (nb > 2147483647ll) return set_error(DFM_ERR_UNSUPPORTED, "too many points");
     const size_t esz = d->dtype == DFM_BF16 ? 2 : 4;
     const size_t feat_stride = (size_t)g.num_views * g.num_frames * g.Hf * g.Wf * g.C * esz;
     const size_t out_stride = (size_t)g.N * g.C * (g.aggregate ? g.num_frames : 1) * esz;
@@ -494,17 +485,15 @@ DFM_API int dfm_point_sample_mv_fwd_batched(const dfm_mv_desc *descs, int32_t ba
         const float *owp = ori_w + (size_t)b0 * g.num_views * g.num_frames;
         void *op = (char *)out + b0 * out_stride;
         unsigned char *vp = valid_out ? valid_out + (size_t)b0 * g.N : nullptr;
-#define MV_CL_LAUNCH(T, LPV) \
+#define MV_CL_LAUNCH(LPV) \
         hipLaunchKernelGGL((mv_sample_cl_kernel<T, LPV>), grid, dim3(256), 0, st, g, mb, fp, pp, pj, owp, (T *)op, vp)
-        if (d->dtype == DFM_BF16) {
-            if (nblk == 4) MV_CL_LAUNCH(bf16_t, 4); else if (nblk == 8) MV_CL_LAUNCH(bf16_t, 8); else MV_CL_LAUNCH(bf16_t, 16);
-        } else {
-            if (nblk == 4) MV_CL_LAUNCH(float, 4); else if (nblk == 8) MV_CL_LAUNCH(float, 8); else MV_CL_LAUNCH(float, 16);
-        }
+        by_dtype(d->dtype, [&](auto t) {
+            using T = decltype(t);
+            if (nblk == 4) MV_CL_LAUNCH(4); else if (nblk == 8) MV_CL_LAUNCH(8); else MV_CL_LAUNCH(16);
+        });
 #undef MV_CL_LAUNCH
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_ps(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -712,11 +701,10 @@ extern "C" DFM_API int dfm_point_sample_mv_bwd(const dfm_mv_desc *d, const void 
                                                const float *ori_w, float *grad_feats,
                                                void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!d) return fail_ps(DFM_ERR_INVALID_ARG, "desc is NULL");
-    if (d->dtype != DFM_F32 && d->dtype != DFM_BF16)
-        return fail_ps(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (!d) return set_error(DFM_ERR_INVALID_ARG, "desc is NULL");
+    if (int rc = check_dtype(d->dtype)) return rc;
     if (!grad_out || !points || !proj || !ori_w || !grad_feats)
-        return fail_ps(DFM_ERR_INVALID_ARG, "NULL device pointer");
+        return set_error(DFM_ERR_INVALID_ARG, "NULL device pointer");
     MvGeom g;
     g.num_views = d->num_views; g.num_frames = d->num_frames; g.C = d->channels;
     g.Hf = d->feat_h; g.Wf = d->feat_w; g.nblk = 0;
@@ -733,32 +721,27 @@ extern "C" DFM_API int dfm_point_sample_mv_bwd(const dfm_mv_desc *d, const void 
         // pixel-major accumulation (see mv_sample_bwd_pm_kernel)
         const size_t need = dfm_point_sample_mv_bwd_workspace_bytes(d);
         if (workspace_bytes < need)
-            return fail_ps(DFM_ERR_WORKSPACE, "workspace smaller than dfm_point_sample_mv_bwd_workspace_bytes");
-        hipError_t e = hipMemsetAsync(workspace, 0, need, st);
-        if (e != hipSuccess) return fail_ps(DFM_ERR_HIP, hipGetErrorString(e));
+            return set_error(DFM_ERR_WORKSPACE, "workspace smaller than dfm_point_sample_mv_bwd_workspace_bytes");
+        HIP_TRY(hipMemsetAsync(workspace, 0, need, st));
         const long long nb = (g.N + MV_VT - 1) / MV_VT;
-        if (d->dtype == DFM_F32)
-            hipLaunchKernelGGL(mv_sample_bwd_pm_kernel<float>, dim3((unsigned)nb), dim3(256), lds, st, g,
-                               (const float *)grad_out, points, proj, ori_w, (float *)workspace);
-        else
-            hipLaunchKernelGGL(mv_sample_bwd_pm_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), lds, st,
-                               g, (const bf16_t *)grad_out, points, proj, ori_w, (float *)workspace);
+        by_dtype(d->dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(mv_sample_bwd_pm_kernel<T>, dim3((unsigned)nb), dim3(256), lds, st, g,
+                               (const T *)grad_out, points, proj, ori_w, (float *)workspace);
+        });
         const long long HW = (long long)d->feat_h * d->feat_w;
         dim3 tg((unsigned)((HW + 63) / 64), (d->channels + 31) / 32, nvf);
         hipLaunchKernelGGL(add_from_pixel_major_kernel<float>, tg, dim3(256), 0, st,
                            (const float *)workspace, grad_feats, d->channels, HW);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail_ps(DFM_ERR_HIP, hipGetErrorString(e));
+        HIP_TRY(hipGetLastError());
         return DFM_OK;
     }
     const long long nb = (g.N + 255) / 256;
-    if (d->dtype == DFM_F32)
-        hipLaunchKernelGGL(mv_sample_bwd_kernel<float>, dim3((unsigned)nb), dim3(256), 0, st, g,
-                           (const float *)grad_out, points, proj, ori_w, grad_feats);
-    else
-        hipLaunchKernelGGL(mv_sample_bwd_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, st, g,
-                           (const bf16_t *)grad_out, points, proj, ori_w, grad_feats);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_ps(DFM_ERR_HIP, hipGetErrorString(e));
+    by_dtype(d->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(mv_sample_bwd_kernel<T>, dim3((unsigned)nb), dim3(256), 0, st, g, (const T *)grad_out,
+                           points, proj, ori_w, grad_feats);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }

@@ -56,13 +56,11 @@ int dfm::ensure_dynamic_lds(const void *kern, int lds_bytes)
     static std::mutex mu;
     static std::map<std::pair<int, const void *>, int> seen;
     int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(mu);
     int &have = seen[std::make_pair(dev, kern)];
     if (lds_bytes > have) {
-        e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
         have = lds_bytes;
     }
     return DFM_OK;

@@ -292,8 +292,7 @@ DFM_API int dfm_spp_tail_fwd(const dfm_spp_desc *d, const void *const *pooled, c
     const long long npix = (long long)d->h * d->w;
     hipLaunchKernelGGL(spp_concat_kernel, dim3((unsigned)((npix + 3) / 4), d->batch), dim3(256), 0, st, cc,
                        (const float *)workspace, (bf16_t *)out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 

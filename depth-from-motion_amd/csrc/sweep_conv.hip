@@ -626,16 +626,13 @@ extern "C" DFM_API int dfm_sweep_conv_pack_weights(const void *w_stereo, const v
     if (weight_dtype != DFM_F32 && weight_dtype != DFM_BF16)
         return set_error(DFM_ERR_UNSUPPORTED, "weight dtype must be DFM_F32 or DFM_BF16");
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync((char *)packed + (size_t)4 * SC_FRAGS * 64 * 16, 0, 4096, st);  // the zero pixel
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
-    if (weight_dtype == DFM_F32)
-        hipLaunchKernelGGL(sweep_conv_pack_kernel<float>, dim3(SC_FRAGS, 4), dim3(64), 0, st, (const float *)w_stereo,
-                           (const float *)w_mono, (bf16_t *)packed);
-    else
-        hipLaunchKernelGGL(sweep_conv_pack_kernel<bf16_t>, dim3(SC_FRAGS, 4), dim3(64), 0, st, (const bf16_t *)w_stereo,
-                           (const bf16_t *)w_mono, (bf16_t *)packed);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipMemsetAsync((char *)packed + (size_t)4 * SC_FRAGS * 64 * 16, 0, 4096, st));  // the zero pixel
+    by_dtype(weight_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(sweep_conv_pack_kernel<T>, dim3(SC_FRAGS, 4), dim3(64), 0, st, (const T *)w_stereo,
+                           (const T *)w_mono, (bf16_t *)packed);
+    });
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -704,7 +701,6 @@ extern "C" DFM_API int dfm_sweep_conv_fwd(const dfm_sweep_desc *desc, const void
                            (const uint4 *)cur_nhwc, (const uint4 *)prev_nhwc, depths, cam2img, cam2img_inv, cur2prev, wp,
                            zero, (bf16_t *)y_stereo, (bf16_t *)y_mono, stats_stereo, stats_mono);
     if (timed) profile_mark(stream, true);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }

@@ -114,8 +114,7 @@ int vs_geom(const dfm_vs_desc *d, VsGeom &g)
     if (d->channels <= 0 || d->nx <= 0 || d->ny <= 0 || d->nz <= 0 || d->num_depths <= 0 ||
         d->h_out <= 0 || d->w_out <= 0)
         return set_error(DFM_ERR_INVALID_ARG, "non-positive size in dfm_vs_desc");
-    if (d->dtype != DFM_F32 && d->dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(d->dtype)) return rc;
     if ((long long)d->nx * d->ny * d->nz >= (1ll << 31))
         return set_error(DFM_ERR_UNSUPPORTED, "volume too large for 32-bit corner offsets");
     g.C = d->channels; g.Nx = d->nx; g.Ny = d->ny; g.Nz = d->nz;
@@ -145,8 +144,7 @@ extern "C" DFM_API int dfm_voxel_sample_fwd(const dfm_vs_desc *d, const void *vo
         hipLaunchKernelGGL(voxel_sample_kernel<T>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g,
                            (const T *)voxel_features, depths, (T *)out);
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -166,8 +164,7 @@ extern "C" DFM_API int dfm_voxel_sample_bwd(const dfm_vs_desc *d, const void *gr
         hipLaunchKernelGGL(voxel_sample_bwd_kernel<T>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g,
                            (const T *)grad_out, depths, grad_voxel_features);
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -362,8 +359,7 @@ int vsm_geom(const dfm_vs_mv_desc *d, VsmGeom &g)
     if (d->batch <= 0 || d->num_views <= 0 || d->channels <= 0 || d->nx <= 0 || d->ny <= 0 || d->nz <= 0 ||
         d->num_depths <= 0 || d->h_out <= 0 || d->w_out <= 0)
         return set_error(DFM_ERR_INVALID_ARG, "non-positive size in dfm_vs_mv_desc");
-    if (d->dtype != DFM_F32 && d->dtype != DFM_BF16)
-        return set_error(DFM_ERR_UNSUPPORTED, "dtype must be DFM_F32 or DFM_BF16");
+    if (int rc = check_dtype(d->dtype)) return rc;
     if ((long long)d->nx * d->ny * d->nz >= (1ll << 31))
         return set_error(DFM_ERR_UNSUPPORTED, "volume too large for 32-bit corner offsets");
     if ((long long)d->batch * d->num_views > 65535)
@@ -411,8 +407,7 @@ extern "C" DFM_API int dfm_voxel_sample_mv_fwd(const dfm_vs_mv_desc *d, const fl
                                    (const T *)voxel_features, vcs, vos, depths, (T *)out, ocs, ois);
         });
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
 
@@ -438,7 +433,6 @@ extern "C" DFM_API int dfm_voxel_sample_mv_bwd(const dfm_vs_mv_desc *d, const fl
                                (const T *)grad_out, gcs, gis, depths, grad_voxel_features, vcs, vos);
         });
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(DFM_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return DFM_OK;
 }
