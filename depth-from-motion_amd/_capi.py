@@ -182,6 +182,19 @@ class AnchorHeadDesc(ctypes.Structure):
         [(n, ctypes.c_int64 * 4) for n in ('cls_stride', 'reg_stride', 'dir_stride')]
 
 
+ANCHOR_LOSS_MAX_CODE = 16  # DFM_ANCHOR_LOSS_MAX_CODE
+
+
+class AnchorLossDesc(ctypes.Structure):
+    """struct dfm_anchor_loss_desc"""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        'batch', 'h', 'w', 'anchors_per_location', 'num_classes', 'box_code_size', 'dtype', 'has_dir', 'with_iou',
+        'diff_rad_by_sin', 'reserved')] + [(n, ctypes.c_float) for n in ('gamma', 'alpha', 'beta')] + \
+        [('code_weight', ctypes.c_float * ANCHOR_LOSS_MAX_CODE)] + \
+        [(n, ctypes.c_int64 * 4) for n in ('cls_stride', 'reg_stride', 'dir_stride', 'grad_cls_stride',
+                                           'grad_reg_stride', 'grad_dir_stride')]
+
+
 ATSS_MAX_LEVELS, ATSS_MAX_TOPK, ATSS_MAX_BATCH = 8, 16, 64  # DFM_ATSS_MAX_*
 ATSS_THRESH_MEANSTD, ATSS_THRESH_RATIO = 0, 1  # DFM_ATSS_THRESH_*
 ATSS_CODER_DELTA_XYWH = 0  # DFM_ATSS_CODER_DELTA_XYWH
@@ -256,6 +269,7 @@ STRUCTS = {
     'dfm_anchor_head_desc': AnchorHeadDesc, 'dfm_atss_target_desc': AtssTargetDesc, 'dfm_deform_desc': DeformDesc,
     'dfm_voxel_desc': VoxelDesc, 'dfm_sparse_conv_desc': SparseConvDesc, 'dfm_sparse_conv_plan': SparseConvPlan,
     'dfm_depth_targets_desc': DepthTargetsDesc, 'dfm_optim_tensor': OptimTensor,
+    'dfm_anchor_loss_desc': AnchorLossDesc,
 }
 
 # DFM_SPARSE_STATUS_*: bits of the device status word of the sparse-convolution index kernels
@@ -297,7 +311,7 @@ def _binding():
     vsp, vmp, cp, wp, lp = P(VsDesc), P(VsMvDesc), P(Conv3dDesc), P(Conv3dWgradDesc), P(DepthLossDesc)
     ip, atp, ahp, adp, ddp = P(ImitationDesc), P(AnchorTargetDesc), P(AnchorHeadDesc), P(AtssTargetDesc), P(DeformDesc)
     vdp, sdp, plp, i32p, i64p = P(VoxelDesc), P(SparseConvDesc), P(SparseConvPlan), P(i32), P(i64)
-    dtp = P(DepthTargetsDesc)
+    dtp, alp = P(DepthTargetsDesc), P(AnchorLossDesc)
     return {
         'dfm_hip.h': _table(
             ('dfm_version', ci, []),
@@ -491,6 +505,12 @@ def _binding():
             ('dfm_grad_sqnorm', ci, [vp, i32, vp, i64, fp, vp]),
             ('dfm_adamw_step', ci, [vp, i32, vp, i64, fp, f32, fp, i32, vp]),
             ('dfm_grad_scale', ci, [vp, i32, vp, i64, fp, f32, fp, vp]),
+        ),
+        # the 3-D anchor head's loss_single: focal, smooth-L1, direction and IoU terms over the maps in place
+        'dfm_hip_anchor_loss.h': _table(
+            ('dfm_anchor3d_loss_workspace_bytes', sz, [alp]),
+            ('dfm_anchor3d_loss_fwd', ci, [alp, vp, vp, vp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp, sz, vp]),
+            ('dfm_anchor3d_loss_bwd', ci, [alp, vp, vp, vp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp, vp, vp, vp]),
         ),
     }
 

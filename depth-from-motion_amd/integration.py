@@ -17,7 +17,8 @@ Three ways to use this package from there, all routed to the HIP kernels:
    imported), replaces ``MultiViewDfM.feature_transformation`` by
    ``MultiViewDfMMixin.feature_transformation`` and, where ``train_mixins`` is already imported,
    ``AnchorTrainMixin.anchor_target_3d`` by ``HipAnchorTrainMixin.anchor_target_3d`` and, where ``anchor3d_head`` is,
-   ``Anchor3DHead.get_bboxes`` by ``HipAnchor3DHeadMixin.get_bboxes``.  Where ``mmcv.ops`` is already imported its
+   ``Anchor3DHead.get_bboxes`` by ``HipAnchor3DHeadMixin.get_bboxes`` and ``loss_single`` of ``Anchor3DHead`` and
+   of ``LIGAAnchor3DHead`` by ``HipAnchor3DLossMixin.loss_single``.  Where ``mmcv.ops`` is already imported its
    ``modulated_deform_conv2d`` is rebound and ``ModulatedDeformConv2dPack`` registered as ``'DCNv2'`` in mmcv's
    ``CONV_LAYERS``; likewise ``Voxelization``, ``SparseConvTensor``, ``SparseSequential`` and the layer types
    ``SubMConv3d`` / ``SparseConv3d`` of the LiDAR teacher (``LidarTeacher`` below), and
@@ -45,6 +46,8 @@ from . import anchor_target as _anchor_target
 from .anchor_target import HipAnchorTrainMixin, bbox_overlaps_nearest_3d
 from . import bbox_decode as _bbox_decode
 from .bbox_decode import HipAnchor3DHeadMixin
+from . import anchor_loss as _anchor_loss
+from .anchor_loss import HipAnchor3DLossMixin
 from . import atss_target as _atss_target
 from .atss_target import HipATSSTargetMixin
 from . import deform_conv as _deform_conv
@@ -578,6 +581,32 @@ def _patch_anchor_head():
     return methods
 
 
+# the anchor head's training side: loss_single of Anchor3DHead AND of LIGAAnchor3DHead (the subclass overrides it, so
+# both are rebound), the replaced methods kept per class for the fallback policy.  Only where the head's file is
+# already imported, as above: both import mmdet.
+_ANCHOR_LOSS_CLASSES = (('mmdet3d.models.dense_heads.anchor3d_head', 'Anchor3DHead'),
+                        ('mmdet3d.models.dense_heads.liga_anchor3d_head', 'LIGAAnchor3DHead'))
+
+
+def _patch_anchor_loss():
+    """-> methods rebound"""
+    methods = []
+    ours = vars(HipAnchor3DLossMixin)
+    for mod_name, cls_name in _ANCHOR_LOSS_CLASSES:
+        mod = sys.modules.get(mod_name)
+        cls = getattr(mod, cls_name, None) if mod is not None else None
+        if cls is not None and 'loss_single' in vars(cls):
+            current = vars(cls)['loss_single']
+            if current is not ours['loss_single']:
+                _anchor_loss._REFERENCE[f'{cls_name}.loss_single'] = current
+                cls.loss_single = ours['loss_single']
+                # the helpers the rebound method calls on ``self``
+                for helper in ('_loss_single_unsupported', '_loss_single_scale', '_loss_single_fallback'):
+                    setattr(cls, helper, ours[helper])
+            methods.append(f'{cls_name}.loss_single')
+    return methods
+
+
 # the 2-D ATSS head's target assignment: LIGAATSSHead inherits get_targets from mmdet's ATSSHead; the class gets
 # this package's method, the inherited one is kept for the fallback policy.  mmdet's bbox_overlaps is rebound nowhere.
 # Only where liga_atss_head.py is already imported, as above: it imports mmdet.
@@ -787,6 +816,7 @@ def patch_reference(precision=None, strict=False):
     report['functions'] += functions
     report['methods'] += methods
     report['methods'] += _patch_anchor_head()
+    report['methods'] += _patch_anchor_loss()
     report['methods'] += _patch_atss_target()
     functions, layers = _patch_deform_conv()
     report['functions'] += functions

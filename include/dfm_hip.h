@@ -1387,6 +1387,9 @@ DFM_API int dfm_spp_tail_fwd(const dfm_spp_desc *desc, const void *const *pooled
 /* the optimizer step: the gradients' global norm, the clip and AdamW with fp32 masters over one multi-tensor table
  * (dfm_grad_sqnorm, dfm_adamw_step, dfm_grad_scale): likewise */
 #include "dfm_hip_optim.h"
+/* the 3-D anchor head's loss_single: focal, smooth-L1, direction and IoU terms over the head's maps in place
+ * (dfm_anchor3d_loss_workspace_bytes, dfm_anchor3d_loss_fwd, dfm_anchor3d_loss_bwd): likewise */
+#include "dfm_hip_anchor_loss.h"
 
 #ifdef __cplusplus
 }
