@@ -21,7 +21,8 @@ from .integration import (DfMDepthTargetMixin, DfMImitationMixin, DfMLidarTeache
                           LidarTeacher,
                           MultiViewDfMMixin, MultiViewVoxelPath, enable_fast_path, inject_detector_attributes,
                           patch_reference)
-from .conv3d import MfmaPathError, fallback_policy, set_fallback_policy, set_fp32_mode  # noqa: F401
+from .fallback import MfmaPathError, fallback_policy, set_fallback_policy  # noqa: F401
+from .conv3d import set_fp32_mode  # noqa: F401
 from .depth_head import depth_distribution_loss  # noqa: F401
 from .imitation import (ImitationLoss, NormalizeLayer, imitation_reg_layer_loss,  # noqa: F401
                         reduce_imitation_statistics)

@@ -17,12 +17,11 @@ The reference's ``assert labels.max().item() <= num_classes`` is a wait for the 
 ``[0, num_classes)`` -- ``num_classes`` itself, ``-1``, anything else -- is a row whose classes are all negative.
 CPU tensors are refused: there is no CPU path.
 """
-import warnings
 
 import torch
 
 from . import _capi
-from .conv3d import MfmaPathError, module_fallback_policy
+from .fallback import run_reference
 from ._launch import DTYPES, STREAM, WS, launch, require_gpu, upload
 
 __all__ = ['anchor3d_loss', 'HipAnchor3DLossMixin', 'counters']
@@ -187,10 +186,6 @@ def _on(host, device):
     return host if torch.device(device).type == 'cpu' else upload(host, device)
 
 
-_WARNED = set()
-_REFERENCE = {}   # 'Anchor3DHead.loss_single', 'LIGAAnchor3DHead.loss_single': what patch_reference() replaced
-
-
 class HipAnchor3DLossMixin(object):
     """``Anchor3DHead.loss_single`` and ``LIGAAnchor3DHead.loss_single`` on the HIP path, for a head class
     ``class FastHead(HipAnchor3DLossMixin, LIGAAnchor3DHead)`` (``patch_reference()`` rebinds both reference classes'
@@ -275,7 +270,7 @@ class HipAnchor3DLossMixin(object):
                 dir_weights, anchors, num_total_samples)
         why = self._loss_single_unsupported()
         if why is not None:
-            return self._loss_single_fallback(why, *args)
+            return run_reference(self, 'loss_single', why, 'anchor-loss', args, mixin=HipAnchor3DLossMixin)
         with_dir = getattr(self, 'use_direction_classifier', True)
         with_iou = getattr(self, 'loss_iou', None) is not None
         train_cfg = getattr(self, 'train_cfg', None)
@@ -292,24 +287,3 @@ class HipAnchor3DLossMixin(object):
                             diff_rad_by_sin=self.diff_rad_by_sin, with_iou=with_iou)
         losses = (out[0], out[1], out[2] if with_dir else None)
         return losses + (out[3],) if with_iou else losses
-
-    def _loss_single_fallback(self, why, *args):
-        original, mro = None, type(self).__mro__
-        for klass in mro:                                     # the nearest class whose method was replaced
-            original = _REFERENCE.get(f'{klass.__name__}.loss_single')
-            if original is not None:
-                break
-        if original is None:
-            for klass in mro[mro.index(HipAnchor3DLossMixin) + 1:] if HipAnchor3DLossMixin in mro else ():
-                if 'loss_single' in vars(klass):
-                    original = vars(klass)['loss_single']
-                    break
-        msg = (f'{type(self).__name__}.loss_single: {why} -- not covered by the anchor-loss kernels; '
-               'running the reference method.  set_fallback_policy("raise") makes this an error.')
-        if module_fallback_policy(self) == 'raise' or original is None:
-            raise MfmaPathError(msg if original is not None else msg.replace(
-                'running the reference method', 'and there is no reference method to run'))
-        if module_fallback_policy(self) != 'silent' and why not in _WARNED:
-            _WARNED.add(why)
-            warnings.warn(msg, RuntimeWarning, stacklevel=3)
-        return original(self, *args)

@@ -18,12 +18,11 @@ GT boxes and anchors of any floating dtype or stride are converted to contiguous
 there is no CPU path.
 """
 import ctypes
-import warnings
 
 import torch
 
 from . import _capi
-from .conv3d import MfmaPathError, module_fallback_policy
+from .fallback import run_reference
 from ._launch import STREAM, WS, launch, require_gpu
 from .registry import register_module
 
@@ -197,10 +196,6 @@ def anchor_target_3d(anchors, gt_bboxes_list, gt_labels_list, assigners, *, num_
     return labels, label_weights, bbox_targets, bbox_weights, dir_targets, dir_weights, counts
 
 
-_WARNED = set()
-_REFERENCE = {}   # 'anchor_target_3d': the reference method patch_reference() replaced
-
-
 class HipAnchorTrainMixin(object):
     """``AnchorTrainMixin.anchor_target_3d`` (train_mixins.py:12-100) on the HIP path, for a head class
     ``class FastHead(HipAnchorTrainMixin, LIGAAnchor3DHead)`` (``patch_reference()`` rebinds the reference
@@ -256,8 +251,9 @@ class HipAnchorTrainMixin(object):
         assert len(anchor_list) == num_imgs
         why = self._anchor_target_unsupported(anchor_list, gt_bboxes_ignore_list, gt_labels_list, sampling)
         if why is not None:
-            return self._anchor_target_fallback(why, anchor_list, gt_bboxes_list, input_metas, gt_bboxes_ignore_list,
-                                                gt_labels_list, label_channels, num_classes, sampling)
+            return run_reference(self, 'anchor_target_3d', why, 'anchor-target',
+                                 (anchor_list, gt_bboxes_list, input_metas, gt_bboxes_ignore_list, gt_labels_list,
+                                  label_channels, num_classes, sampling), mixin=HipAnchorTrainMixin)
         levels = anchor_list[0]
         code = getattr(self, 'box_code_size', levels[0].shape[-1])
         num_level_anchors = [l.view(-1, code).size(0) for l in levels]            # train_mixins.py:55-58
@@ -277,21 +273,3 @@ class HipAnchorTrainMixin(object):
                 start += n
             out.append(per_level)
         return (*out, int(pos_neg[0]), int(pos_neg[1]))
-
-    def _anchor_target_fallback(self, why, *args):
-        original = _REFERENCE.get('anchor_target_3d')
-        if original is None:
-            mro = type(self).__mro__
-            for klass in mro[mro.index(HipAnchorTrainMixin) + 1:] if HipAnchorTrainMixin in mro else ():
-                if 'anchor_target_3d' in vars(klass):
-                    original = vars(klass)['anchor_target_3d']
-                    break
-        msg = (f'{type(self).__name__}.anchor_target_3d: {why} -- not covered by the anchor-target kernels; '
-               'running the reference method.  set_fallback_policy("raise") makes this an error.')
-        if module_fallback_policy(self) == 'raise' or original is None:
-            raise MfmaPathError(msg if original is not None else msg.replace(
-                'running the reference method', 'and there is no reference method to run'))
-        if module_fallback_policy(self) != 'silent' and why not in _WARNED:
-            _WARNED.add(why)
-            warnings.warn(msg, RuntimeWarning, stacklevel=3)
-        return original(self, *args)

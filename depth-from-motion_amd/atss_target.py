@@ -17,12 +17,11 @@ Boxes and anchors of any floating dtype or stride are converted to contiguous fp
 is no CPU path.
 """
 import ctypes
-import warnings
 
 import torch
 
 from . import _capi
-from .conv3d import MfmaPathError, module_fallback_policy
+from .fallback import run_reference
 from ._launch import STREAM, WS, launch, require_gpu, upload
 from .registry import register_module
 
@@ -161,10 +160,6 @@ def atss_target_2d(anchors, num_level_anchors, gt_bboxes_list, gt_labels_list, *
     return labels, label_weights, bbox_targets, bbox_weights, assigned, counts
 
 
-_WARNED = set()
-_REFERENCE = {}   # 'get_targets': the reference method patch_reference() replaced
-
-
 def _field(obj, name, default):
     if isinstance(obj, dict):
         return obj.get(name, default)
@@ -231,8 +226,9 @@ class HipATSSTargetMixin(object):
         if why is None and not unmap_outputs:
             why = 'unmap_outputs=False'
         if why is not None:
-            return self._atss_target_fallback(why, anchor_list, valid_flag_list, gt_bboxes_list, img_metas,
-                                              gt_bboxes_ignore_list, gt_labels_list, label_channels, unmap_outputs)
+            return run_reference(self, 'get_targets', why, 'ATSS-target',
+                                 (anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list,
+                                  gt_labels_list, label_channels, unmap_outputs), mixin=HipATSSTargetMixin)
         levels = anchor_list[0]
         num_level_anchors = [l.size(0) for l in levels]
         anchors = torch.cat(list(levels)) if len(levels) > 1 else levels[0]
@@ -266,21 +262,3 @@ class HipATSSTargetMixin(object):
                 start += n
             out.append(per_level)
         return (*out, int(pos_neg[0]), int(pos_neg[1]))
-
-    def _atss_target_fallback(self, why, *args):
-        original = _REFERENCE.get('get_targets')
-        if original is None:
-            mro = type(self).__mro__
-            for klass in mro[mro.index(HipATSSTargetMixin) + 1:] if HipATSSTargetMixin in mro else ():
-                if 'get_targets' in vars(klass):
-                    original = vars(klass)['get_targets']
-                    break
-        msg = (f'{type(self).__name__}.get_targets: {why} -- not covered by the ATSS-target kernels; '
-               'running the reference method.  set_fallback_policy("raise") makes this an error.')
-        if module_fallback_policy(self) == 'raise' or original is None:
-            raise MfmaPathError(msg if original is not None else msg.replace(
-                'running the reference method', 'and there is no reference method to run'))
-        if module_fallback_policy(self) != 'silent' and why not in _WARNED:
-            _WARNED.add(why)
-            warnings.warn(msg, RuntimeWarning, stacklevel=3)
-        return original(self, *args)

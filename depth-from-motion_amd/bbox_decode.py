@@ -16,14 +16,13 @@ reference method's signature.
 Equal keys: ``torch.topk`` leaves their order undefined; here equal keys go in ascending anchor index, at the cut as
 well.  CPU tensors are refused: there is no CPU path.
 """
-import warnings
 
 import numpy as np
 import torch
 
 from . import _capi
 from .box_nms import box3d_multiclass_nms
-from .conv3d import MfmaPathError, module_fallback_policy
+from .fallback import run_reference
 from .derived import derived
 from ._launch import DTYPES, STREAM, WS, launch, require_gpu
 
@@ -141,8 +140,6 @@ def anchor3d_get_bboxes(cls_scores, bbox_preds, dir_cls_preds, anchors, cfg, *, 
     return out
 
 
-_WARNED = set()
-_REFERENCE = {}   # 'get_bboxes': the reference method patch_reference() replaced
 _STANDARD_BEV = {}
 
 
@@ -197,7 +194,9 @@ class HipAnchor3DHeadMixin(object):
         assert len(cls_scores) == len(dir_cls_preds)
         why = self._get_bboxes_unsupported(input_metas)
         if why is not None:
-            return self._get_bboxes_fallback(why, cls_scores, bbox_preds, dir_cls_preds, input_metas, cfg, rescale)
+            return run_reference(self, 'get_bboxes', why, 'box-decode',
+                                 (cls_scores, bbox_preds, dir_cls_preds, input_metas, cfg, rescale),
+                                 mixin=HipAnchor3DHeadMixin)
         featmap_sizes = [tuple(int(v) for v in c.shape[-2:]) for c in cls_scores]
         anchors = self._mlvl_anchors(featmap_sizes, cls_scores[0].device)
         cfg = self.test_cfg if cfg is None else cfg
@@ -207,21 +206,3 @@ class HipAnchor3DHeadMixin(object):
         assert len(results) == len(input_metas)
         return [(meta['box_type_3d'](boxes, box_dim=self.box_code_size), scores, labels)
                 for meta, (boxes, scores, labels) in zip(input_metas, results)]
-
-    def _get_bboxes_fallback(self, why, *args):
-        original = _REFERENCE.get('get_bboxes')
-        if original is None:
-            mro = type(self).__mro__
-            for klass in mro[mro.index(HipAnchor3DHeadMixin) + 1:] if HipAnchor3DHeadMixin in mro else ():
-                if 'get_bboxes' in vars(klass):
-                    original = vars(klass)['get_bboxes']
-                    break
-        msg = (f'{type(self).__name__}.get_bboxes: {why} -- not covered by the box-decode kernels; '
-               'running the reference method.  set_fallback_policy("raise") makes this an error.')
-        if module_fallback_policy(self) == 'raise' or original is None:
-            raise MfmaPathError(msg if original is not None else msg.replace(
-                'running the reference method', 'and there is no reference method to run'))
-        if module_fallback_policy(self) != 'silent' and why not in _WARNED:
-            _WARNED.add(why)
-            warnings.warn(msg, RuntimeWarning, stacklevel=3)
-        return original(self, *args)

@@ -21,7 +21,6 @@ describes one of its convolutions -- forward launch, both backward launches, pla
 ``_ConvGFn`` is its one autograd function, in bf16 or in split precision.
 """
 import ctypes
-import warnings
 from collections import namedtuple
 
 import torch
@@ -31,6 +30,8 @@ from torch import nn
 from . import _capi
 from ._launch import DTYPES, STREAM, WS, launch, try_launch
 from .derived import Derived, derived, note_derived_build
+from .fallback import (MfmaPathError, fallback_policy, module_fallback_policy,  # noqa: F401  (the package's public names)
+                       set_fallback_policy, warn_once)
 
 # ---------------------------------------------------------------------------------------------
 # What an ``Mfma*`` module does with a GPU input its kernel does not take (fp32, NCDHW, a shape no
@@ -41,33 +42,6 @@ from .derived import Derived, derived, note_derived_build
 # model so that every convolution of the path IS eligible.  CPU tensors never warn: there is no
 # kernel to miss, only the module-wiring tests run there.
 # ---------------------------------------------------------------------------------------------
-_POLICY = {'mode': 'warn'}
-_WARNED = set()
-
-
-class MfmaPathError(RuntimeError):
-    """strict mode: an Mfma* module was handed an input its MFMA kernel does not take"""
-
-
-def set_fallback_policy(mode):
-    """'warn' | 'raise' | 'silent'; returns the previous mode"""
-    if mode not in ('warn', 'raise', 'silent'):
-        raise ValueError(mode)
-    prev, _POLICY['mode'] = _POLICY['mode'], mode
-    return prev
-
-
-def fallback_policy():
-    return _POLICY['mode']
-
-
-def module_fallback_policy(module):
-    """the policy that governs ``module``: its own ``fallback_policy`` attribute (what
-    ``integration.enable_fast_path`` sets on the Mfma* modules of the model it converts) or, without one,
-    the process-wide mode"""
-    return getattr(module, 'fallback_policy', None) or _POLICY['mode']
-
-
 def _torch_path(module, x, why):
     """called by every Mfma* module right before it runs torch's convolution instead of its kernel"""
     mode = module_fallback_policy(module)
@@ -78,10 +52,7 @@ def _torch_path(module, x, why):
            'converts the path to bf16 / channels-last; set_fallback_policy("raise") makes this an error.')
     if mode == 'raise':
         raise MfmaPathError(msg)
-    key = (type(module).__name__, why)
-    if key not in _WARNED:
-        _WARNED.add(key)
-        warnings.warn(msg, RuntimeWarning, stacklevel=5)  # past _torch_forward, _forward and forward
+    warn_once(type(module).__name__, why, msg, stacklevel=5)  # past _torch_forward, _forward and forward
 
 
 def _why_not_bf16_cl(x, dims):
@@ -399,7 +370,7 @@ def conv3d_weight_grad(x_in, g_out, stride, padding, out_dtype=torch.float32):
                           _capi.DFM_BF16 if out.dtype == torch.bfloat16 else _capi.DFM_F32, WS, STREAM,
                           ws_bytes=nbytes):
                 return out if direct else out.to(out_dtype)
-    if x_in.is_cuda and _POLICY['mode'] == 'raise':
+    if x_in.is_cuda and fallback_policy() == 'raise':
         raise MfmaPathError(f'weight gradient of a {B}->{A} convolution outside the MFMA kernel\'s coverage '
                             '(channels not multiples of 32, layout, or a tile that does not fit the LDS)')
     return _weight_grad_gemm(x_in, g_out, stride, padding).to(out_dtype)

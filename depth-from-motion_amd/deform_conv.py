@@ -18,21 +18,18 @@ bit) and ``grad_x`` (float atomics into an fp32 buffer, converted once).
 CPU tensors are refused: there is no CPU path.
 """
 import ctypes
-import warnings
 
 import torch
 from torch import nn
 
 from . import _capi
 from ._launch import DTYPES, STREAM, launch, require_gpu
-from .conv3d import MfmaPathError, _mm_f32, long_axis_gram, module_fallback_policy
+from .conv3d import _mm_f32, long_axis_gram
+from .fallback import MfmaPathError, run_reference
 from .derived import derived
 
 __all__ = ['deform_sample', 'modulated_deform_conv2d', 'modulated_deform_conv2d_raw', 'ModulatedDeformConv2d', 'ModulatedDeformConv2dPack',
            'deform_conv_out_size']
-
-_REFERENCE = {}   # 'modulated_deform_conv2d': the mmcv function patch_reference() replaced
-_WARNED = set()
 
 
 def _pair(v):
@@ -236,22 +233,6 @@ def _unsupported(weight_shape, groups):
     return None
 
 
-def _fallback(owner, why, *args):
-    """the package's fallback policy for a setting the kernels do not cover: the captured mmcv op where
-    ``patch_reference()`` found one ('warn' says so once), else -- and under 'raise' -- an error naming the setting"""
-    original = _REFERENCE.get('modulated_deform_conv2d')
-    msg = (f'modulated_deform_conv2d: {why} -- not covered by the deformable-convolution kernels; running '
-           'mmcv\'s op.  set_fallback_policy("raise") makes this an error.')
-    policy = module_fallback_policy(owner)
-    if policy == 'raise' or original is None:
-        raise MfmaPathError(msg if original is not None else msg.replace(
-            "running mmcv's op", 'and there is no mmcv op to run'))
-    if policy != 'silent' and why not in _WARNED:
-        _WARNED.add(why)
-        warnings.warn(msg, RuntimeWarning, stacklevel=3)
-    return original(*args)
-
-
 def modulated_deform_conv2d(input, offset, mask, weight, bias=None, stride=1, padding=0, dilation=1, groups=1,
                             deform_groups=1):
     """mmcv's ``modulated_deform_conv2d`` (same signature): ``input`` ``(N, Cin, H, W)`` fp32 | bf16 in any memory
@@ -262,8 +243,9 @@ def modulated_deform_conv2d(input, offset, mask, weight, bias=None, stride=1, pa
     follows the fallback policy (mmcv's op where ``patch_reference()`` captured one, else ``MfmaPathError``)."""
     why = _unsupported(tuple(weight.shape), groups)
     if why is not None:
-        return _fallback(None, why, input, offset, mask, weight, bias, stride, padding, dilation, groups,
-                         deform_groups)
+        return run_reference(None, None, why, 'deformable-convolution',
+                             (input, offset, mask, weight, bias, stride, padding, dilation, groups, deform_groups),
+                             key='modulated_deform_conv2d')
     return _run(input, offset, mask, weight, bias, stride, padding, dilation, deform_groups, False)
 
 
@@ -321,8 +303,9 @@ class ModulatedDeformConv2d(nn.Module):
             if mask is None:   # mmcv's op takes the three chunks
                 o1, o2, m = torch.chunk(offset, 3, dim=1)
                 offset, mask = torch.cat((o1, o2), dim=1), torch.sigmoid(m)
-            return _fallback(self, why, x, offset, mask, self.weight, self.bias, self.stride, self.padding,
-                             self.dilation, self.groups, self.deform_groups)
+            return run_reference(self, None, why, 'deformable-convolution',
+                                 (x, offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation,
+                                  self.groups, self.deform_groups), key='modulated_deform_conv2d')
         return _run(x, offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation,
                     self.deform_groups, mask_is_logit, self._weight_matrix())
 

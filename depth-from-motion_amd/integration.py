@@ -34,26 +34,23 @@ Three ways to use this package from there, all routed to the HIP kernels:
 import importlib
 import inspect
 import sys
+import types
+from collections import namedtuple
 
 import numpy as np
 import torch
 from torch import nn
 
 from . import registry
+from .fallback import REPLACED
 from .box_nms import box3d_multiclass_nms, nms_bev, nms_normal_bev
 from .iou3d_loss import diff_iou_rotated_3d
-from . import anchor_target as _anchor_target
 from .anchor_target import HipAnchorTrainMixin, bbox_overlaps_nearest_3d
-from . import bbox_decode as _bbox_decode
 from .bbox_decode import HipAnchor3DHeadMixin
-from . import anchor_loss as _anchor_loss
 from .anchor_loss import HipAnchor3DLossMixin
-from . import atss_target as _atss_target
 from .atss_target import HipATSSTargetMixin
-from . import deform_conv as _deform_conv
 from .deform_conv import ModulatedDeformConv2dPack, modulated_deform_conv2d
-from . import sparse_conv as _sparse_conv
-from .sparse_conv import SparseConv3d, SparseConvTensor, SparseSequential, SubMConv3d
+from .sparse_conv import SparseConv3d, SparseConvTensor, SparseSequential, SubMConv3d, make_sparse_convmodule
 from .voxelize import Voxelization
 from . import kitti_eval as _kitti_eval
 from . import depth_targets as _depth_targets
@@ -350,7 +347,7 @@ class DfMLidarTeacherMixin:
     def extract_lidar_model_feat(self, points):
         lm = self.lidar_model
         if not hasattr(lm.voxel_layer, 'forward_batch'):   # a teacher built from mmcv's classes: the reference's method
-            return _sparse_conv._REFERENCE['DfM.extract_lidar_model_feat'](self, points)
+            return REPLACED['DfM.extract_lidar_model_feat'](self, points)
         voxels, coors, num_points, _ = lm.voxel_layer.forward_batch(list(points))
         voxel_features = lm.voxel_encoder(voxels, num_points, coors)
         spatial_feat, volume_feat = lm.middle_encoder(voxel_features, coors, len(points))
@@ -477,310 +474,204 @@ class MultiViewVoxelPath(MultiViewDfMMixin, nn.Module):
                                     depth_img.flatten(start_dim=0, end_dim=1))
 
 
-# the functions the reference's modules look up by name, and the files that define them
-_FUNCTION_PATCHES = (
-    ('mmdet3d.models.backbones.dfm_backbone', 'build_dfm_cost', build_dfm_cost),
-    ('mmdet3d.models.fusion_layers.point_fusion', 'point_sample', point_sample),
-    ('mmdet3d.models.fusion_layers.point_fusion', 'voxel_sample', voxel_sample),
-    ('mmdet3d.models.fusion_layers', 'point_sample', point_sample),
-    ('mmdet3d.models.fusion_layers', 'voxel_sample', voxel_sample),
-    ('mmdet3d.models.detectors.multiview_dfm', 'point_sample', point_sample),
-    ('mmdet3d.models.detectors.multiview_dfm', 'voxel_sample', voxel_sample),
-    ('mmdet3d.models.detectors.imvoxelnet', 'point_sample', point_sample),
-)
+# ---------------------------------------------------------------------------------------------
+# patch_reference(): one table of named groups, three kinds of row, one applier per kind
+# ---------------------------------------------------------------------------------------------
+# (a) rebind the name ``attr`` of ``module`` to ``ours``; ``key``: where REPLACED keeps what was there (None: not kept)
+Name = namedtuple('Name', 'module attr ours key load', defaults=(None, False))
+# (b) rebind ``cls.method`` to ``mixin``'s, with every other function ``mixin`` defines (the helpers the method calls
+# on ``self``); REPLACED['<cls>.<method>'] keeps what was there.  ``inherited``: ``cls`` need not define it itself
+Method = namedtuple('Method', 'module cls method mixin inherited load', defaults=(False, False))
+# (c) register ``ours`` as ``name`` (force=True) in the mmcv registry ``registry``, taken from the first of ``modules``
+# that holds it (they hold the same object); ``key``: where REPLACED keeps the previous entry (None: not looked up)
+Register = namedtuple('Register', 'modules registry name ours key load', defaults=(None, False))
+# ``load``: the module may be imported for the purpose.  Otherwise a row applies only where its module is ALREADY
+# imported: this package never drags in mmcv, mmdet or numba by itself.
 
-
-# the BEV NMS functions (mmcv CUDA ops behind them in the reference) and every module that holds them by
-# name.  Rebound only where the module is ALREADY imported: importing box3d_nms.py for this would drag in
-# numba and mmcv.ops.
-_NMS_MODULES = ('mmdet3d.core.post_processing.box3d_nms', 'mmdet3d.core.post_processing', 'mmdet3d.core',
-                'mmdet3d.models.dense_heads.anchor3d_head')
-_NMS_FUNCTIONS = (('box3d_multiclass_nms', box3d_multiclass_nms), ('nms_bev', nms_bev),
-                  ('nms_normal_bev', nms_normal_bev))
-
-
-def _patch_nms_functions():
-    done = []
-    for mod_name in _NMS_MODULES:
-        mod = sys.modules.get(mod_name)
-        for attr, fn in _NMS_FUNCTIONS:
-            if mod is not None and hasattr(mod, attr):
-                setattr(mod, attr, fn)
-                done.append(f'{mod_name}.{attr}')
-    return done
-
-
-# the reference's iou3d_loss.py holds mmcv's differentiable IoU by name (``from mmcv.ops import diff_iou_rotated_3d``);
-# its IOU3DLoss class itself is replaced through the registry.  Rebound only where already imported, as above.
-_IOU_MODULES = ('mmdet3d.models.losses.iou3d_loss',)
-
-
-def _patch_iou_functions():
-    done = []
-    for mod_name in _IOU_MODULES:
-        mod = sys.modules.get(mod_name)
-        if mod is not None and hasattr(mod, 'diff_iou_rotated_3d'):
-            mod.diff_iou_rotated_3d = diff_iou_rotated_3d
-            done.append(f'{mod_name}.diff_iou_rotated_3d')
-    return done
-
-
-# the anchor head's target assignment: the reference's train_mixins.py defines AnchorTrainMixin, whose
-# anchor_target_3d is rebound (the replaced method is kept for the fallback policy), and the modules that hold
-# bbox_overlaps_nearest_3d by name.  Only where already imported, as above: these files import mmdet.
-_TRAIN_MIXIN_MODULES = ('mmdet3d.models.dense_heads.train_mixins',)
-_OVERLAP_MODULES = ('mmdet3d.core.bbox.iou_calculators.iou3d_calculator', 'mmdet3d.core.bbox.iou_calculators',
-                    'mmdet3d.core.bbox', 'mmdet3d.core')
-
-
-def _patch_anchor_target():
-    """-> (functions, methods) rebound"""
-    functions, methods = [], []
-    for mod_name in _OVERLAP_MODULES:
-        mod = sys.modules.get(mod_name)
-        if mod is not None and hasattr(mod, 'bbox_overlaps_nearest_3d'):
-            mod.bbox_overlaps_nearest_3d = bbox_overlaps_nearest_3d
-            functions.append(f'{mod_name}.bbox_overlaps_nearest_3d')
-    for mod_name in _TRAIN_MIXIN_MODULES:
-        mod = sys.modules.get(mod_name)
-        cls = getattr(mod, 'AnchorTrainMixin', None) if mod is not None else None
-        if cls is not None and hasattr(cls, 'anchor_target_3d'):
-            current = vars(cls).get('anchor_target_3d')
-            ours = vars(HipAnchorTrainMixin)['anchor_target_3d']
-            if current is not ours:
-                _anchor_target._REFERENCE['anchor_target_3d'] = current
-                cls.anchor_target_3d = ours
-                # the two helpers the rebound method calls on ``self``
-                cls._anchor_target_unsupported = vars(HipAnchorTrainMixin)['_anchor_target_unsupported']
-                cls._anchor_target_fallback = vars(HipAnchorTrainMixin)['_anchor_target_fallback']
-            methods.append('AnchorTrainMixin.anchor_target_3d')
-    return functions, methods
-
-
-# the anchor head's inference side: Anchor3DHead.get_bboxes (inherited by LIGAAnchor3DHead) is rebound, the replaced
-# method kept for the fallback policy.  Only where anchor3d_head.py is already imported, as above: it imports mmdet.
-_ANCHOR_HEAD_MODULES = ('mmdet3d.models.dense_heads.anchor3d_head',)
-
-
-def _patch_anchor_head():
-    """-> methods rebound"""
-    methods = []
-    for mod_name in _ANCHOR_HEAD_MODULES:
-        mod = sys.modules.get(mod_name)
-        cls = getattr(mod, 'Anchor3DHead', None) if mod is not None else None
-        if cls is not None and hasattr(cls, 'get_bboxes'):
-            current = vars(cls).get('get_bboxes')
-            ours = vars(HipAnchor3DHeadMixin)['get_bboxes']
-            if current is not ours:
-                _bbox_decode._REFERENCE['get_bboxes'] = current
-                cls.get_bboxes = ours
-                # the helpers the rebound method calls on ``self``
-                for helper in ('_get_bboxes_unsupported', '_get_bboxes_fallback', '_mlvl_anchors'):
-                    setattr(cls, helper, vars(HipAnchor3DHeadMixin)[helper])
-            methods.append('Anchor3DHead.get_bboxes')
-    return methods
-
-
-# the anchor head's training side: loss_single of Anchor3DHead AND of LIGAAnchor3DHead (the subclass overrides it, so
-# both are rebound), the replaced methods kept per class for the fallback policy.  Only where the head's file is
-# already imported, as above: both import mmdet.
-_ANCHOR_LOSS_CLASSES = (('mmdet3d.models.dense_heads.anchor3d_head', 'Anchor3DHead'),
-                        ('mmdet3d.models.dense_heads.liga_anchor3d_head', 'LIGAAnchor3DHead'))
-
-
-def _patch_anchor_loss():
-    """-> methods rebound"""
-    methods = []
-    ours = vars(HipAnchor3DLossMixin)
-    for mod_name, cls_name in _ANCHOR_LOSS_CLASSES:
-        mod = sys.modules.get(mod_name)
-        cls = getattr(mod, cls_name, None) if mod is not None else None
-        if cls is not None and 'loss_single' in vars(cls):
-            current = vars(cls)['loss_single']
-            if current is not ours['loss_single']:
-                _anchor_loss._REFERENCE[f'{cls_name}.loss_single'] = current
-                cls.loss_single = ours['loss_single']
-                # the helpers the rebound method calls on ``self``
-                for helper in ('_loss_single_unsupported', '_loss_single_scale', '_loss_single_fallback'):
-                    setattr(cls, helper, ours[helper])
-            methods.append(f'{cls_name}.loss_single')
-    return methods
-
-
-# the 2-D ATSS head's target assignment: LIGAATSSHead inherits get_targets from mmdet's ATSSHead; the class gets
-# this package's method, the inherited one is kept for the fallback policy.  mmdet's bbox_overlaps is rebound nowhere.
-# Only where liga_atss_head.py is already imported, as above: it imports mmdet.
-_ATSS_HEAD_MODULES = ('mmdet3d.models.dense_heads.liga_atss_head',)
-
-
-def _patch_atss_target():
-    """-> methods rebound"""
-    methods = []
-    for mod_name in _ATSS_HEAD_MODULES:
-        mod = sys.modules.get(mod_name)
-        cls = getattr(mod, 'LIGAATSSHead', None) if mod is not None else None
-        if cls is not None and hasattr(cls, 'get_targets'):
-            ours = vars(HipATSSTargetMixin)['get_targets']
-            if vars(cls).get('get_targets') is not ours:
-                _atss_target._REFERENCE['get_targets'] = cls.get_targets        # (inherited from ATSSHead)
-                cls.get_targets = ours
-                # the helpers the rebound method calls on ``self``
-                for helper in ('_atss_target_unsupported', '_atss_target_fallback'):
-                    setattr(cls, helper, vars(HipATSSTargetMixin)[helper])
-            methods.append('LIGAATSSHead.get_targets')
-    return methods
-
-
-# the backbone's deformable convolutions (the Waymo configs' ResNet-101 with dcn=dict(type='DCNv2')): mmcv's function
-# is rebound in the modules that hold it by name, and the Pack is registered as 'DCNv2' in mmcv's CONV_LAYERS, which
-# is where mmdet's ResNet builds its dcn layers from.  The replaced function and class are kept for the fallback
-# policy.  Only where those modules are already imported, as above: this package never imports mmcv.
-_DEFORM_MODULES = ('mmcv.ops.modulated_deform_conv', 'mmcv.ops')
 _CONV_LAYER_MODULES = ('mmcv.cnn.bricks.registry', 'mmcv.cnn.bricks', 'mmcv.cnn')
+_TEACHER_NAMES = dict(Voxelization=Voxelization, SparseConvTensor=SparseConvTensor, SparseSequential=SparseSequential,
+                      SubMConv3d=SubMConv3d, SparseConv3d=SparseConv3d, make_sparse_convmodule=make_sparse_convmodule)
 
 
-def _patch_deform_conv():
-    """-> (functions rebound, conv layers registered)"""
-    functions, layers = [], []
-    for mod_name in _DEFORM_MODULES:
-        mod = sys.modules.get(mod_name)
-        current = getattr(mod, 'modulated_deform_conv2d', None) if mod is not None else None
-        if current is not None:
-            if current is not modulated_deform_conv2d:
-                _deform_conv._REFERENCE.setdefault('modulated_deform_conv2d', current)
-                mod.modulated_deform_conv2d = modulated_deform_conv2d
-            functions.append(f'{mod_name}.modulated_deform_conv2d')
-    for mod_name in _CONV_LAYER_MODULES:
-        mod = sys.modules.get(mod_name)
-        reg = getattr(mod, 'CONV_LAYERS', None) if mod is not None else None
-        if reg is not None:
-            previous = reg.get('DCNv2')
-            if previous is not ModulatedDeformConv2dPack:
-                if previous is not None:
-                    _deform_conv._REFERENCE.setdefault('DCNv2', previous)
-                reg.register_module(name='DCNv2', force=True, module=ModulatedDeformConv2dPack)
-            layers.append('DCNv2 (mmcv CONV_LAYERS)')
-            break   # the three modules hold the same registry object
-    return functions, layers
-
-
-# the LiDAR teacher's ops: mmcv's Voxelization and spconv wrapper classes are rebound in the modules that hold them
-# by name, the layer types registered in mmcv's CONV_LAYERS (where make_sparse_convmodule builds them from).  What was
-# there before is kept.  Only where those modules are already imported: this package never imports mmcv or mmdet3d.
-_TEACHER_CLASSES = dict(Voxelization=Voxelization, SparseConvTensor=SparseConvTensor,
-                        SparseSequential=SparseSequential, SubMConv3d=SubMConv3d, SparseConv3d=SparseConv3d)
-_TEACHER_MODULES = ('mmcv.ops', 'mmcv.ops.voxelize', 'mmcv.ops.sparse_conv', 'mmcv.ops.sparse_structure',
-                    'mmcv.ops.sparse_modules', 'mmdet3d.ops', 'mmdet3d.ops.sparse_block',
-                    'mmdet3d.models.middle_encoders.sparse_encoder', 'mmdet3d.models.detectors.voxelnet')
-
-
-def _patch_lidar_teacher():
-    """-> (names rebound, conv layers registered, methods replaced)"""
-    functions, layers, methods = [], [], []
-    for mod_name in _TEACHER_MODULES:
-        mod = sys.modules.get(mod_name)
-        if mod is None:
-            continue
-        for attr, cls in _TEACHER_CLASSES.items():
-            current = getattr(mod, attr, None)
-            if current is None:
-                continue
-            if current is not cls:
-                _sparse_conv._REFERENCE.setdefault(f'{mod_name}.{attr}', current)
-                setattr(mod, attr, cls)
-            functions.append(f'{mod_name}.{attr}')
-        if getattr(mod, 'make_sparse_convmodule', None) is not None:
-            if mod.make_sparse_convmodule is not _sparse_conv.make_sparse_convmodule:
-                _sparse_conv._REFERENCE.setdefault(f'{mod_name}.make_sparse_convmodule', mod.make_sparse_convmodule)
-                mod.make_sparse_convmodule = _sparse_conv.make_sparse_convmodule
-            functions.append(f'{mod_name}.make_sparse_convmodule')
-    for mod_name in _CONV_LAYER_MODULES:
-        mod = sys.modules.get(mod_name)
-        reg = getattr(mod, 'CONV_LAYERS', None) if mod is not None else None
-        if reg is not None:
-            for name, cls in (('SubMConv3d', SubMConv3d), ('SparseConv3d', SparseConv3d)):
-                previous = reg.get(name)
-                if previous is not cls:
-                    if previous is not None:
-                        _sparse_conv._REFERENCE.setdefault(f'CONV_LAYERS.{name}', previous)
-                    reg.register_module(name=name, force=True, module=cls)
-                layers.append(f'{name} (mmcv CONV_LAYERS)')
-            break   # the three modules hold the same registry object
-    det = sys.modules.get('mmdet3d.models.detectors.dfm')
-    cls = getattr(det, 'DfM', None) if det is not None else None
-    if cls is not None and hasattr(cls, 'extract_lidar_model_feat'):
-        if cls.extract_lidar_model_feat is not DfMLidarTeacherMixin.extract_lidar_model_feat:
-            _sparse_conv._REFERENCE.setdefault('DfM.extract_lidar_model_feat', cls.extract_lidar_model_feat)
-            cls.extract_lidar_model_feat = DfMLidarTeacherMixin.extract_lidar_model_feat
-        methods.append('DfM.extract_lidar_model_feat')
-    return functions, layers, methods
-
-
-# the KITTI evaluation: ``kitti_eval`` in every module that holds it by name, and ``rotate_iou_gpu_eval`` (numba.cuda in
-# the reference) where it is defined.  The datasets import ``kitti_eval`` from ``mmdet3d.core.evaluation`` at call time,
-# so rebinding the names is enough.  Only where those modules are already imported, as above: eval.py imports numba.
-_KITTI_EVAL_MODULES = ('mmdet3d.core.evaluation.kitti_utils.eval', 'mmdet3d.core.evaluation.kitti_utils',
-                       'mmdet3d.core.evaluation', 'mmdet3d.core')
-_ROTATE_IOU_MODULES = ('mmdet3d.core.evaluation.kitti_utils.rotate_iou',)
-
-
-def _patch_kitti_eval():
-    """-> functions rebound"""
-    done = []
-    for modules, attr, fn in ((_KITTI_EVAL_MODULES, 'kitti_eval', _kitti_eval.kitti_eval),
-                              (_ROTATE_IOU_MODULES, 'rotate_iou_gpu_eval', _kitti_eval.rotate_iou_eval)):
-        for mod_name in modules:
-            mod = sys.modules.get(mod_name)
-            if mod is not None and hasattr(mod, attr):
-                setattr(mod, attr, fn)
-                done.append(f'{mod_name}.{attr}')
-    return done
-
-
-# the depth loss's targets: ``depth_map_in_boxes_cpu`` where the pipeline holds it by name (its body calls mmcv's
-# compiled ``points_in_boxes_cpu``), and mmcv's ``points_in_boxes_part`` / ``_all`` where the box structures and the
-# detector imported them.  Only where those modules are already imported, as above.
-_DEPTH_MAP_MODULES = ('mmdet3d.datasets.utils', 'mmdet3d.datasets.pipelines.transforms_3d')
-_POINTS_IN_BOXES_MODULES = ('mmdet3d.core.bbox.structures.base_box3d', 'mmdet3d.models.detectors.dfm')
-
-
-def _patch_depth_targets():
-    """-> functions rebound; [] when none of the modules is imported"""
-    done = []
-    for modules, names in ((_DEPTH_MAP_MODULES, {'depth_map_in_boxes_cpu': _depth_targets.depth_map_in_boxes}),
-                           (_POINTS_IN_BOXES_MODULES, {'points_in_boxes_part': _depth_targets.points_in_boxes_part,
-                                                       'points_in_boxes_all': _depth_targets.points_in_boxes_all})):
-        for mod_name in modules:
-            mod = sys.modules.get(mod_name)
-            for attr, fn in names.items():
-                if mod is not None and hasattr(mod, attr):
-                    setattr(mod, attr, fn)
-                    done.append(f'{mod_name}.{attr}')
-    return done
-
-
-# the optimizer step: ``FusedAdamW`` into mmcv's OPTIMIZERS registry (a config names it ``type='FusedAdamW'``), and the
-# clip of ``OptimizerHook.clip_grads``.  The hook module holds torch's ``clip_grad`` MODULE and calls
-# ``clip_grad.clip_grad_norm_``: it gets a namespace of its own in that place, torch's module is left as it is.
+# the optimizer hook module holds torch's ``clip_grad`` MODULE and calls ``clip_grad.clip_grad_norm_``: it gets a
+# namespace of its own in that place, torch's module is left as it is.
 class _ClipGrad:
     clip_grad_norm_ = staticmethod(_optim.clip_grad_norm_)
 
 
-def _patch_optimizer():
-    """-> (modules registered, functions rebound); ([], []) without mmcv"""
+def _rebind_clip_grad():
+    hooks = _module('mmcv.runner.hooks.optimizer', True)
+    if not hasattr(hooks, 'clip_grad'):
+        return None
+    hooks.clip_grad = _ClipGrad
+    return 'functions', 'mmcv.runner.hooks.optimizer.clip_grad.clip_grad_norm_'
+
+
+def _accept_staged_metas():
+    # dfm.py:288-291 builds ``torch.tensor([img_meta['cur2prevs'] ...])``, which cannot take the device
+    # tensors of a batch staged by data_geometry.stage_geometry: hand it host arrays (one 64-byte-per-
+    # frame copy back; DfMStereoPath and the registered DfMBackbone read staged matrices in place)
+    cls = getattr(_module('mmdet3d.models.detectors.dfm', True), 'DfM', None)
+    extract_feat = getattr(cls, 'extract_feat', None)
+    if extract_feat is None or getattr(extract_feat, '_dfm_staged_metas', False):
+        return None
+    cls.extract_feat = _extract_feat_with_staged_metas(extract_feat)
+    return 'methods', 'DfM.extract_feat (accepts device-staged cur2prevs)'
+
+
+def _rows(modules, names, **kwargs):
+    """a Name row for every name in every module, module by module"""
+    return [Name(m, attr, ours, **kwargs) for m in modules for attr, ours in names.items()]
+
+
+PATCHES = {
+    # the functions the reference's modules look up by name, and the files that define them
+    'core': [Name(m, attr, ours, load=True) for m, attr, ours in (
+        ('mmdet3d.models.backbones.dfm_backbone', 'build_dfm_cost', build_dfm_cost),
+        ('mmdet3d.models.fusion_layers.point_fusion', 'point_sample', point_sample),
+        ('mmdet3d.models.fusion_layers.point_fusion', 'voxel_sample', voxel_sample),
+        ('mmdet3d.models.fusion_layers', 'point_sample', point_sample),
+        ('mmdet3d.models.fusion_layers', 'voxel_sample', voxel_sample),
+        ('mmdet3d.models.detectors.multiview_dfm', 'point_sample', point_sample),
+        ('mmdet3d.models.detectors.multiview_dfm', 'voxel_sample', voxel_sample),
+        ('mmdet3d.models.detectors.imvoxelnet', 'point_sample', point_sample))],
+    # the BEV NMS functions (mmcv CUDA ops behind them in the reference) and every module that holds them by
+    # name.  Not loaded: importing box3d_nms.py for this would drag in numba and mmcv.ops.
+    'nms': _rows(('mmdet3d.core.post_processing.box3d_nms', 'mmdet3d.core.post_processing', 'mmdet3d.core',
+                  'mmdet3d.models.dense_heads.anchor3d_head'),
+                 dict(box3d_multiclass_nms=box3d_multiclass_nms, nms_bev=nms_bev, nms_normal_bev=nms_normal_bev)),
+    # the reference's iou3d_loss.py holds mmcv's differentiable IoU by name (``from mmcv.ops import
+    # diff_iou_rotated_3d``); its IOU3DLoss class itself is replaced through the registry.
+    'iou': [Name('mmdet3d.models.losses.iou3d_loss', 'diff_iou_rotated_3d', diff_iou_rotated_3d)],
+    # the KITTI evaluation: ``kitti_eval`` in every module that holds it by name, and ``rotate_iou_gpu_eval``
+    # (numba.cuda in the reference) where it is defined.  The datasets import ``kitti_eval`` from
+    # ``mmdet3d.core.evaluation`` at call time, so rebinding the names is enough.  Not loaded: eval.py imports numba.
+    'kitti_eval': [
+        *_rows(('mmdet3d.core.evaluation.kitti_utils.eval', 'mmdet3d.core.evaluation.kitti_utils',
+                'mmdet3d.core.evaluation', 'mmdet3d.core'), dict(kitti_eval=_kitti_eval.kitti_eval)),
+        Name('mmdet3d.core.evaluation.kitti_utils.rotate_iou', 'rotate_iou_gpu_eval', _kitti_eval.rotate_iou_eval)],
+    # the depth loss's targets: ``depth_map_in_boxes_cpu`` where the pipeline holds it by name (its body calls mmcv's
+    # compiled ``points_in_boxes_cpu``), and mmcv's ``points_in_boxes_part`` / ``_all`` where the box structures and
+    # the detector imported them.
+    'depth_targets': [
+        *_rows(('mmdet3d.datasets.utils', 'mmdet3d.datasets.pipelines.transforms_3d'),
+               dict(depth_map_in_boxes_cpu=_depth_targets.depth_map_in_boxes)),
+        *_rows(('mmdet3d.core.bbox.structures.base_box3d', 'mmdet3d.models.detectors.dfm'),
+               dict(points_in_boxes_part=_depth_targets.points_in_boxes_part,
+                    points_in_boxes_all=_depth_targets.points_in_boxes_all))],
+    # the optimizer step: ``FusedAdamW`` into mmcv's OPTIMIZERS registry (a config names it ``type='FusedAdamW'``),
+    # and the clip of ``OptimizerHook.clip_grads``.  Loaded: the runner imports both modules anyway.
+    'optimizer': [Register(('mmcv.runner.optimizer',), 'OPTIMIZERS', 'FusedAdamW', _optim.FusedAdamW, load=True),
+                  _rebind_clip_grad],
+    # the anchor head's target assignment: the modules that hold bbox_overlaps_nearest_3d by name, and
+    # AnchorTrainMixin.anchor_target_3d of the reference's train_mixins.py.  Not loaded: these files import mmdet.
+    'anchor_target': [
+        *_rows(('mmdet3d.core.bbox.iou_calculators.iou3d_calculator', 'mmdet3d.core.bbox.iou_calculators',
+                'mmdet3d.core.bbox', 'mmdet3d.core'), dict(bbox_overlaps_nearest_3d=bbox_overlaps_nearest_3d)),
+        Method('mmdet3d.models.dense_heads.train_mixins', 'AnchorTrainMixin', 'anchor_target_3d', HipAnchorTrainMixin)],
+    # the anchor head's inference side: Anchor3DHead.get_bboxes (inherited by LIGAAnchor3DHead).  Not loaded:
+    # anchor3d_head.py imports mmdet.
+    'anchor_head': [Method('mmdet3d.models.dense_heads.anchor3d_head', 'Anchor3DHead', 'get_bboxes',
+                           HipAnchor3DHeadMixin)],
+    # the anchor head's training side: loss_single of Anchor3DHead AND of LIGAAnchor3DHead (the subclass overrides
+    # it, so both are rebound and each keeps its own).  Not loaded: both files import mmdet.
+    'anchor_loss': [Method('mmdet3d.models.dense_heads.anchor3d_head', 'Anchor3DHead', 'loss_single',
+                           HipAnchor3DLossMixin),
+                    Method('mmdet3d.models.dense_heads.liga_anchor3d_head', 'LIGAAnchor3DHead', 'loss_single',
+                           HipAnchor3DLossMixin)],
+    # the 2-D ATSS head's target assignment: LIGAATSSHead inherits get_targets from mmdet's ATSSHead; the class gets
+    # this package's method, the inherited one is kept.  mmdet's bbox_overlaps is rebound nowhere.  Not loaded:
+    # liga_atss_head.py imports mmdet.
+    'atss_target': [Method('mmdet3d.models.dense_heads.liga_atss_head', 'LIGAATSSHead', 'get_targets',
+                           HipATSSTargetMixin, inherited=True)],
+    # the backbone's deformable convolutions (the Waymo configs' ResNet-101 with dcn=dict(type='DCNv2')): mmcv's
+    # function is rebound in the modules that hold it by name, and the Pack is registered as 'DCNv2' in mmcv's
+    # CONV_LAYERS, which is where mmdet's ResNet builds its dcn layers from.  Not loaded: this package never imports
+    # mmcv.
+    'deform_conv': [
+        *_rows(('mmcv.ops.modulated_deform_conv', 'mmcv.ops'), dict(modulated_deform_conv2d=modulated_deform_conv2d),
+               key='modulated_deform_conv2d'),
+        Register(_CONV_LAYER_MODULES, 'CONV_LAYERS', 'DCNv2', ModulatedDeformConv2dPack, key='DCNv2')],
+    # the LiDAR teacher's ops: mmcv's Voxelization and spconv wrapper classes are rebound in the modules that hold
+    # them by name, the layer types registered in mmcv's CONV_LAYERS (where make_sparse_convmodule builds them from),
+    # and ``DfM.extract_lidar_model_feat``.  Not loaded: this package never imports mmcv or mmdet3d.
+    'lidar_teacher': [
+        *(Name(m, attr, ours, key=f'{m}.{attr}') for m in (
+            'mmcv.ops', 'mmcv.ops.voxelize', 'mmcv.ops.sparse_conv', 'mmcv.ops.sparse_structure',
+            'mmcv.ops.sparse_modules', 'mmdet3d.ops', 'mmdet3d.ops.sparse_block',
+            'mmdet3d.models.middle_encoders.sparse_encoder', 'mmdet3d.models.detectors.voxelnet')
+          for attr, ours in _TEACHER_NAMES.items()),
+        Register(_CONV_LAYER_MODULES, 'CONV_LAYERS', 'SubMConv3d', SubMConv3d, key='CONV_LAYERS.SubMConv3d'),
+        Register(_CONV_LAYER_MODULES, 'CONV_LAYERS', 'SparseConv3d', SparseConv3d, key='CONV_LAYERS.SparseConv3d'),
+        Method('mmdet3d.models.detectors.dfm', 'DfM', 'extract_lidar_model_feat', DfMLidarTeacherMixin)],
+    # the detectors themselves.  Loaded: patch_reference() is called to build them.
+    'detectors': [Method('mmdet3d.models.detectors.multiview_dfm', 'MultiViewDfM', 'feature_transformation',
+                         MultiViewDfMMixin, load=True),
+                  _accept_staged_metas],
+}
+
+
+def _module(name, load):
+    if not load:
+        return sys.modules.get(name)
     try:
-        registry_mod = importlib.import_module('mmcv.runner.optimizer')
-        hooks = importlib.import_module('mmcv.runner.hooks.optimizer')
+        return importlib.import_module(name)
     except ImportError:
-        return [], []
-    modules, functions = [], []
-    if hasattr(registry_mod, 'OPTIMIZERS'):
-        registry_mod.OPTIMIZERS.register_module(name='FusedAdamW', force=True, module=_optim.FusedAdamW)
-        modules.append('FusedAdamW (mmcv OPTIMIZERS)')
-    if hasattr(hooks, 'clip_grad'):
-        hooks.clip_grad = _ClipGrad
-        functions.append('mmcv.runner.hooks.optimizer.clip_grad.clip_grad_norm_')
-    return modules, functions
+        return None
+
+
+def _apply_name(row):
+    mod = _module(row.module, row.load)
+    current = getattr(mod, row.attr, None)
+    if current is None:
+        return None
+    if current is not row.ours:
+        if row.key is not None:
+            REPLACED[row.key] = current
+        setattr(mod, row.attr, row.ours)
+    return 'functions', f'{row.module}.{row.attr}'
+
+
+def _apply_method(row):
+    cls = getattr(_module(row.module, row.load), row.cls, None)
+    if cls is None or not (hasattr(cls, row.method) if row.inherited else row.method in vars(cls)):
+        return None
+    ours = vars(row.mixin)
+    if vars(cls).get(row.method) is not ours[row.method]:
+        REPLACED[f'{cls.__name__}.{row.method}'] = getattr(cls, row.method)
+        for name, fn in ours.items():
+            if isinstance(fn, types.FunctionType):
+                setattr(cls, name, fn)
+    return 'methods', f'{row.cls}.{row.method}'
+
+
+def _apply_register(row):
+    for mod_name in row.modules:
+        reg = getattr(_module(mod_name, row.load), row.registry, None)
+        if reg is None:
+            continue
+        previous = reg.get(row.name) if row.key is not None else None
+        if previous is not row.ours:
+            if previous is not None:
+                REPLACED[row.key] = previous
+            reg.register_module(name=row.name, force=True, module=row.ours)
+        return 'modules', f'{row.name} (mmcv {row.registry})'
+    return None
+
+
+_APPLIERS = {Name: _apply_name, Method: _apply_method, Register: _apply_register}
+
+
+def apply_patches(group):
+    """apply the rows of ``PATCHES[group]`` -> ``{'modules': [...], 'functions': [...], 'methods': [...]}``, what
+    ``patch_reference()`` adds to its report for the group.  Applying a group again changes nothing and reports the
+    same."""
+    report = {'modules': [], 'functions': [], 'methods': []}
+    for row in PATCHES[group]:
+        done = row() if callable(row) else _APPLIERS[type(row)](row)
+        if done is not None:
+            report[done[0]].append(done[1])
+    return report
 
 
 def patch_reference(precision=None, strict=False):
@@ -797,64 +688,25 @@ def patch_reference(precision=None, strict=False):
     if precision not in (None, 'fp32', 'bf16'):
         raise ValueError(f'precision must be None, "fp32" or "bf16", got {precision!r}')
     report = {'modules': registry.register_into_mmdet3d(), 'functions': [], 'methods': []}
-    for mod_name, attr, fn in _FUNCTION_PATCHES:
-        try:
-            mod = importlib.import_module(mod_name)
-        except ImportError:
-            continue
-        if hasattr(mod, attr):
-            setattr(mod, attr, fn)
-            report['functions'].append(f'{mod_name}.{attr}')
-    report['functions'] += _patch_nms_functions()
-    report['functions'] += _patch_iou_functions()
-    report['functions'] += _patch_kitti_eval()
-    report['functions'] += _patch_depth_targets()
-    layers, functions = _patch_optimizer()
-    report['modules'] += layers
-    report['functions'] += functions
-    functions, methods = _patch_anchor_target()
-    report['functions'] += functions
-    report['methods'] += methods
-    report['methods'] += _patch_anchor_head()
-    report['methods'] += _patch_anchor_loss()
-    report['methods'] += _patch_atss_target()
-    functions, layers = _patch_deform_conv()
-    report['functions'] += functions
-    report['modules'] += layers
-    functions, layers, methods = _patch_lidar_teacher()
-    report['functions'] += functions
-    report['modules'] += layers
-    report['methods'] += methods
-    try:
-        det = importlib.import_module('mmdet3d.models.detectors.multiview_dfm')
-        det.MultiViewDfM.feature_transformation = MultiViewDfMMixin.feature_transformation
-        report['methods'].append('MultiViewDfM.feature_transformation')
-    except (ImportError, AttributeError):
-        pass
-    try:
-        # dfm.py:288-291 builds ``torch.tensor([img_meta['cur2prevs'] ...])``, which cannot take the device
-        # tensors of a batch staged by data_geometry.stage_geometry: hand it host arrays (one 64-byte-per-
-        # frame copy back; DfMStereoPath and the registered DfMBackbone read staged matrices in place)
-        cls = importlib.import_module('mmdet3d.models.detectors.dfm').DfM
-        if not getattr(cls.extract_feat, '_dfm_staged_metas', False):
-            cls.extract_feat = _extract_feat_with_staged_metas(cls.extract_feat)
-            report['methods'].append('DfM.extract_feat (accepts device-staged cur2prevs)')
-    except (ImportError, AttributeError):
-        pass
+    for group in PATCHES:
+        for kind, done in apply_patches(group).items():
+            report[kind] += done
     if precision == 'bf16':
-        # every module of a detector is built inside DfM.__init__ (MultiViewDfM.__init__ calls it and
-        # adds plain attributes only, multiview_dfm.py:36-65): converting at its end covers both
-        try:
-            cls = importlib.import_module('mmdet3d.models.detectors.dfm').DfM
-        except (ImportError, AttributeError):
-            cls = None
-        if cls is not None and not getattr(cls.__init__, '_dfm_fast', False):
-            cls.__init__ = _init_then_fast_path(cls.__init__, strict)
-            report['methods'].append('DfM.__init__ -> enable_fast_path(bf16)')
-        elif cls is not None:  # patched before: the wrapper reads the strictness of the latest call
-            _patch_state['strict'] = bool(strict)
-            report['methods'].append(f'DfM.__init__ already patched (strict={bool(strict)} from now on)')
+        report['methods'] += _fast_path_after_init(strict)
     return report
+
+
+def _fast_path_after_init(strict):
+    # every module of a detector is built inside DfM.__init__ (MultiViewDfM.__init__ calls it and
+    # adds plain attributes only, multiview_dfm.py:36-65): converting at its end covers both
+    cls = getattr(_module('mmdet3d.models.detectors.dfm', True), 'DfM', None)
+    if cls is None:
+        return []
+    if not getattr(cls.__init__, '_dfm_fast', False):
+        cls.__init__ = _init_then_fast_path(cls.__init__, strict)
+        return ['DfM.__init__ -> enable_fast_path(bf16)']
+    _patch_state['strict'] = bool(strict)   # patched before: the wrapper reads the strictness of the latest call
+    return [f'DfM.__init__ already patched (strict={bool(strict)} from now on)']
 
 
 def _extract_feat_with_staged_metas(extract_feat):
@@ -934,7 +786,7 @@ def enable_fast_path(model, dtype=torch.bfloat16, strict=True, boundary_casts=Tr
     * ``strict`` (default True): every Mfma* module INSIDE ``model`` gets ``fallback_policy = 'raise'`` -- an
       input its kernel does not take (wrong dtype / layout, a shape no tiling fits) is an error there instead
       of a one-time warning and torch's convolution.  Per model: other models in the process keep the
-      process-wide mode (conv3d.set_fallback_policy; 'warn' by default).  ``strict=False`` leaves the
+      process-wide mode (fallback.set_fallback_policy; 'warn' by default).  ``strict=False`` leaves the
       modules' policy as it is.
 
     Returns a report dict(roots=[names], converted_parameters=n, cast_back=[names], dtype=...).

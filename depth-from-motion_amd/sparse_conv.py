@@ -30,14 +30,13 @@ from torch import nn
 
 from . import _capi
 from ._launch import STREAM, launch, require_gpu
-from .conv3d import MfmaPathError
+from .fallback import MfmaPathError
 from .derived import derived
 from .registry import register_module
 
 __all__ = ['SparseConvTensor', 'SubMConv3d', 'SparseConv3d', 'SparseSequential', 'make_sparse_convmodule',
            'CustomSparseEncoder', 'sparse_conv_plan']
 
-_REFERENCE = {}   # what patch_reference() replaced: 'mmcv.ops.SubMConv3d' -> mmcv's class, ...
 
 
 def _triple(v):

@@ -22,7 +22,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _capi
 from ._launch import STREAM, WS, launch
-from .conv3d import MfmaPathError
+from .fallback import MfmaPathError
 from .sparse_conv import SparseSequential, _SparseConvBase, _size3
 
 __all__ = ['enable_sparse_training']

@@ -15,7 +15,6 @@ import torch
 from tests import anchor_loss_ref as ref
 from tests import util
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ('plain', 'plain_cw', 'plain_nodir', 'liga', 'liga_reduce', 'liga_iou', 'liga_reduce_iou', 'nopos')
 
 
@@ -197,7 +196,7 @@ def test_mixin_falls_back_or_raises_for_what_the_kernels_do_not_do(pkg, al, z):
         with pytest.raises(RuntimeError, match='no CPU path'):
             head.loss_single(*args)
     finally:
-        al._WARNED.clear()
+        importlib.import_module('depth-from-motion_amd.fallback').WARNED.clear()
 
 
 def test_patch_reference_rebinds_both_head_classes(pkg, al, z):
@@ -207,11 +206,13 @@ def test_patch_reference_rebinds_both_head_classes(pkg, al, z):
     chain = ('mmdet3d', 'mmdet3d.models', 'mmdet3d.models.dense_heads') + names
     before = {k: sys.modules.get(k) for k in chain}
     integ = importlib.import_module('depth-from-motion_amd.integration')
-    kept = dict(al._REFERENCE)
+    fb = importlib.import_module('depth-from-motion_amd.fallback')
+    nothing = {'modules': [], 'functions': [], 'methods': []}
+    kept = dict(fb.REPLACED)
     try:
         for k in chain:
             sys.modules.pop(k, None)
-        assert integ._patch_anchor_loss() == [] and not any(n in sys.modules for n in names)
+        assert integ.apply_patches('anchor_loss') == nothing and not any(n in sys.modules for n in names)
         for k in chain:
             m = types.ModuleType(k)
             m.__path__ = []
@@ -225,17 +226,16 @@ def test_patch_reference_rebinds_both_head_classes(pkg, al, z):
             def loss_single(self, *args):
                 return 'liga', args
         originals = (Anchor3DHead.__dict__['loss_single'], LIGAAnchor3DHead.__dict__['loss_single'])
-        sys.modules[names[0]].Anchor3DHead = Anchor3DHead
-        assert integ._patch_anchor_loss() == ['Anchor3DHead.loss_single']           # the other file is not imported
-        sys.modules[names[1]].LIGAAnchor3DHead = LIGAAnchor3DHead
         both = ['Anchor3DHead.loss_single', 'LIGAAnchor3DHead.loss_single']
+        sys.modules[names[0]].Anchor3DHead = Anchor3DHead
+        assert integ.apply_patches('anchor_loss') == dict(nothing, methods=both[:1])   # the other file is not imported
+        sys.modules[names[1]].LIGAAnchor3DHead = LIGAAnchor3DHead
         for _ in range(2):
-            assert integ._patch_anchor_loss() == both
+            assert integ.apply_patches('anchor_loss') == dict(nothing, methods=both)
             for klass, original in zip((Anchor3DHead, LIGAAnchor3DHead), originals):
                 assert klass.__dict__['loss_single'] is pkg.HipAnchor3DLossMixin.__dict__['loss_single']
-                assert al._REFERENCE[f'{klass.__name__}.loss_single'] is original
-        src = open(os.path.join(ROOT, 'depth-from-motion_amd', 'integration.py')).read()
-        assert "report['methods'] += _patch_anchor_loss()" in src and "report['methods'] += _patch_anchor_head()" in src
+                assert fb.REPLACED[f'{klass.__name__}.loss_single'] is original
+        assert 'anchor_loss' in integ.PATCHES and 'anchor_head' in integ.PATCHES     # what patch_reference() iterates
         # each class falls back to its own replaced method
         args = tuple(inputs(z)) + (41,)
         for klass, tag in ((Anchor3DHead, 'plain'), (LIGAAnchor3DHead, 'liga')):
@@ -243,11 +243,11 @@ def test_patch_reference_rebinds_both_head_classes(pkg, al, z):
             head.use_sigmoid_cls = False
             with pytest.warns(RuntimeWarning, match='softmax'):
                 assert head.loss_single(*args) == (tag, args)
-            al._WARNED.clear()
+            fb.WARNED.clear()
     finally:
-        al._REFERENCE.clear()
-        al._REFERENCE.update(kept)
-        al._WARNED.clear()
+        fb.REPLACED.clear()
+        fb.REPLACED.update(kept)
+        fb.WARNED.clear()
         for k, v in before.items():
             if v is None:
                 sys.modules.pop(k, None)

@@ -217,12 +217,13 @@ def test_patch_reference_rebinds_a_stub_train_mixins_module(pkg):
              'mmdet3d.core.bbox.iou_calculators', calc)
     before = {k: sys.modules.get(k) for k in chain}
     integ = importlib.import_module('depth-from-motion_amd.integration')
-    at = importlib.import_module('depth-from-motion_amd.anchor_target')
-    kept = dict(at._REFERENCE)
+    fb = importlib.import_module('depth-from-motion_amd.fallback')
+    nothing = {'modules': [], 'functions': [], 'methods': []}
+    kept = dict(fb.REPLACED)
     try:
         for k in chain:
             sys.modules.pop(k, None)
-        assert integ._patch_anchor_target() == ([], []) and mixins not in sys.modules
+        assert integ.apply_patches('anchor_target') == nothing and mixins not in sys.modules
         for k in chain:
             m = types.ModuleType(k)
             m.__path__ = []
@@ -234,13 +235,15 @@ def test_patch_reference_rebinds_a_stub_train_mixins_module(pkg):
         original = AnchorTrainMixin.__dict__['anchor_target_3d']
         sys.modules[mixins].AnchorTrainMixin = AnchorTrainMixin
         sys.modules[calc].bbox_overlaps_nearest_3d = lambda *a, **k: None
-        functions, methods = integ._patch_anchor_target()         # what patch_reference adds to its report
-        assert functions == [calc + '.bbox_overlaps_nearest_3d'] and methods == ['AnchorTrainMixin.anchor_target_3d']
+        done = integ.apply_patches('anchor_target')               # what patch_reference adds to its report
+        assert done == dict(nothing, functions=[calc + '.bbox_overlaps_nearest_3d'],
+                            methods=['AnchorTrainMixin.anchor_target_3d'])
         assert sys.modules[calc].bbox_overlaps_nearest_3d is pkg.bbox_overlaps_nearest_3d
         assert not hasattr(sys.modules['mmdet3d.core.bbox'], 'bbox_overlaps_nearest_3d')
         assert AnchorTrainMixin.__dict__['anchor_target_3d'] is pkg.HipAnchorTrainMixin.__dict__['anchor_target_3d']
-        assert at._REFERENCE['anchor_target_3d'] is original
-        assert integ._patch_anchor_target()[1] == methods and at._REFERENCE['anchor_target_3d'] is original   # twice
+        key = 'AnchorTrainMixin.anchor_target_3d'
+        assert fb.REPLACED[key] is original
+        assert integ.apply_patches('anchor_target') == done and fb.REPLACED[key] is original      # twice
         # a configuration the kernels do not cover goes to the kept method under 'warn' and is an error under 'raise'
         head = AnchorTrainMixin()
         head.bbox_assigner, head.bbox_sampler = [dict(type='MaxIoUAssigner')], object()
@@ -251,9 +254,9 @@ def test_patch_reference_rebinds_a_stub_train_mixins_module(pkg):
         with pytest.raises(pkg.MfmaPathError, match='sampler'):
             head.anchor_target_3d(*args)
     finally:
-        at._REFERENCE.clear()
-        at._REFERENCE.update(kept)
-        at._WARNED.clear()
+        fb.REPLACED.clear()
+        fb.REPLACED.update(kept)
+        fb.WARNED.clear()
         for k, v in before.items():
             if v is None:
                 sys.modules.pop(k, None)

@@ -287,12 +287,13 @@ def test_patch_reference_rebinds_a_stub_liga_atss_head_module(pkg):
     chain = ('mmdet3d', 'mmdet3d.models', 'mmdet3d.models.dense_heads', name)
     before = {k: sys.modules.get(k) for k in chain}
     integ = importlib.import_module('depth-from-motion_amd.integration')
-    at = importlib.import_module('depth-from-motion_amd.atss_target')
-    kept = dict(at._REFERENCE)
+    fb = importlib.import_module('depth-from-motion_amd.fallback')
+    nothing = {'modules': [], 'functions': [], 'methods': []}
+    kept = dict(fb.REPLACED)
     try:
         for k in chain:
             sys.modules.pop(k, None)
-        assert integ._patch_atss_target() == [] and name not in sys.modules
+        assert integ.apply_patches('atss_target') == nothing and name not in sys.modules
         for k in chain:
             m = types.ModuleType(k)
             m.__path__ = []
@@ -307,12 +308,14 @@ def test_patch_reference_rebinds_a_stub_liga_atss_head_module(pkg):
         original = ATSSHead.__dict__['get_targets']
         sys.modules[name].LIGAATSSHead = LIGAATSSHead
         sys.modules[name].bbox_overlaps = mmdet_overlaps = lambda *a, **k: None
-        assert integ._patch_atss_target() == ['LIGAATSSHead.get_targets']  # what patch_reference adds to its report
+        done = dict(nothing, methods=['LIGAATSSHead.get_targets'])
+        assert integ.apply_patches('atss_target') == done           # what patch_reference adds to its report
         assert LIGAATSSHead.__dict__['get_targets'] is pkg.HipATSSTargetMixin.__dict__['get_targets']
-        assert ATSSHead.__dict__['get_targets'] is original and at._REFERENCE['get_targets'] is original
+        assert ATSSHead.__dict__['get_targets'] is original and \
+            fb.REPLACED['LIGAATSSHead.get_targets'] is original
         assert sys.modules[name].bbox_overlaps is mmdet_overlaps
-        assert integ._patch_atss_target() == ['LIGAATSSHead.get_targets'] and \
-            at._REFERENCE['get_targets'] is original                                                      # twice
+        assert integ.apply_patches('atss_target') == done and \
+            fb.REPLACED['LIGAATSSHead.get_targets'] is original                                           # twice
         # a configuration the kernels do not cover goes to the kept method under 'warn' and is an error under 'raise'
         head = LIGAATSSHead()
         head.assigner = type('ATSS3DCenterAssigner', (), dict(thresh_mode='ratio'))()
@@ -324,9 +327,9 @@ def test_patch_reference_rebinds_a_stub_liga_atss_head_module(pkg):
         with pytest.raises(pkg.MfmaPathError, match='ratio'):
             head.get_targets(*args)
     finally:
-        at._REFERENCE.clear()
-        at._REFERENCE.update(kept)
-        at._WARNED.clear()
+        fb.REPLACED.clear()
+        fb.REPLACED.update(kept)
+        fb.WARNED.clear()
         for k, v in before.items():
             if v is None:
                 sys.modules.pop(k, None)

@@ -131,7 +131,9 @@ def test_patch_reference_rebinds_only_loaded_modules(pkg):
                 setattr(sys.modules[k], f, old)
         sys.modules['mmdet3d.models.dense_heads.anchor3d_head'].box3d_multiclass_nms = old
         integ = importlib.import_module('depth-from-motion_amd.integration')
-        done = integ._patch_nms_functions()                       # what patch_reference adds to its report
+        done = integ.apply_patches('nms')                         # what patch_reference adds to its report
+        assert done['modules'] == [] and done['methods'] == []
+        done = done['functions']
         assert sys.modules['mmdet3d.core.post_processing.box3d_nms'].nms_bev is pkg.nms_bev
         assert sys.modules['mmdet3d.core.post_processing'].nms_normal_bev is pkg.nms_normal_bev
         head = sys.modules['mmdet3d.models.dense_heads.anchor3d_head']

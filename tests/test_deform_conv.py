@@ -317,10 +317,10 @@ def test_cpu_tensors_are_refused(pkg):
 
 
 def test_unsupported_settings_follow_the_fallback_policy(pkg):
-    dc = importlib.import_module('depth-from-motion_amd.deform_conv')
+    fb = importlib.import_module('depth-from-motion_amd.fallback')
     x, off, msk = torch.zeros(1, 8, 5, 5), torch.zeros(1, 18, 5, 5), torch.zeros(1, 9, 5, 5)
-    kept = dict(dc._REFERENCE)
-    dc._REFERENCE.clear()
+    kept = dict(fb.REPLACED)
+    fb.REPLACED.clear()
     try:
         with pytest.raises(pkg.MfmaPathError, match='groups=2.*no mmcv op'):
             pkg.modulated_deform_conv2d(x, off, msk, torch.zeros(8, 4, 3, 3), padding=1, groups=2)
@@ -328,7 +328,7 @@ def test_unsupported_settings_follow_the_fallback_policy(pkg):
         with pytest.raises(pkg.MfmaPathError, match='kernel_size'):
             m(x)
         calls = []
-        dc._REFERENCE['modulated_deform_conv2d'] = lambda *a: calls.append(a) or 'mmcv'
+        fb.REPLACED['modulated_deform_conv2d'] = lambda *a: calls.append(a) or 'mmcv'
         with pytest.warns(RuntimeWarning, match='groups=2'):
             assert pkg.modulated_deform_conv2d(x, off, msk, torch.zeros(8, 4, 3, 3), None, 1, 1, 1, 2, 1) == 'mmcv'
         assert calls[0][8] == 2 and calls[0][0] is x
@@ -340,24 +340,25 @@ def test_unsupported_settings_follow_the_fallback_policy(pkg):
         offset, mask = calls[-1][1], calls[-1][2]                             # the Pack hands mmcv's op the chunks
         assert tuple(offset.shape) == (1, 2, 5, 5) and tuple(mask.shape) == (1, 1, 5, 5) and (mask == 0.5).all()
     finally:
-        dc._REFERENCE.clear()
-        dc._REFERENCE.update(kept)
-        dc._WARNED.clear()
+        fb.REPLACED.clear()
+        fb.REPLACED.update(kept)
+        fb.WARNED.clear()
 
 
 def test_patch_rebinds_stub_mmcv_modules_and_touches_nothing_when_absent(pkg):
     integ = importlib.import_module('depth-from-motion_amd.integration')
-    dc = importlib.import_module('depth-from-motion_amd.deform_conv')
+    fb = importlib.import_module('depth-from-motion_amd.fallback')
+    nothing = {'modules': [], 'functions': [], 'methods': []}
     chain = ('mmcv', 'mmcv.ops', 'mmcv.ops.modulated_deform_conv', 'mmcv.cnn', 'mmcv.cnn.bricks',
              'mmcv.cnn.bricks.registry')
     before = {k: sys.modules.get(k) for k in chain}
-    kept = dict(dc._REFERENCE)
+    kept = dict(fb.REPLACED)
     try:
         for k in chain:
             sys.modules.pop(k, None)
-        dc._REFERENCE.clear()
-        assert integ._patch_deform_conv() == ([], []) and not any(k in sys.modules for k in chain)
-        assert dc._REFERENCE == {}
+        fb.REPLACED.clear()
+        assert integ.apply_patches('deform_conv') == nothing and not any(k in sys.modules for k in chain)
+        assert fb.REPLACED == {}
 
         class Registry:
             def __init__(self):
@@ -386,18 +387,18 @@ def test_patch_rebinds_stub_mmcv_modules_and_touches_nothing_when_absent(pkg):
         sys.modules['mmcv.ops'].nms = other = object()
         sys.modules['mmcv.cnn'].CONV_LAYERS = reg
         sys.modules['mmcv.cnn.bricks.registry'].CONV_LAYERS = reg
-        functions, layers = integ._patch_deform_conv()
-        assert functions == ['mmcv.ops.modulated_deform_conv.modulated_deform_conv2d',
-                             'mmcv.ops.modulated_deform_conv2d']
-        assert layers == ['DCNv2 (mmcv CONV_LAYERS)']
+        done = integ.apply_patches('deform_conv')
+        assert done == dict(nothing, functions=['mmcv.ops.modulated_deform_conv.modulated_deform_conv2d',
+                                                'mmcv.ops.modulated_deform_conv2d'],
+                            modules=['DCNv2 (mmcv CONV_LAYERS)'])
         assert sys.modules['mmcv.ops'].modulated_deform_conv2d is pkg.modulated_deform_conv2d
         assert sys.modules['mmcv.ops.modulated_deform_conv'].modulated_deform_conv2d is pkg.modulated_deform_conv2d
         assert sys.modules['mmcv.ops'].nms is other
         assert reg.table['DCNv2'] is pkg.ModulatedDeformConv2dPack and reg.table['Conv2d'] is torch.nn.Conv2d
-        assert dc._REFERENCE == {'modulated_deform_conv2d': mmcv_op, 'DCNv2': MmcvPack}   # kept for the fallback
+        assert fb.REPLACED == {'modulated_deform_conv2d': mmcv_op, 'DCNv2': MmcvPack}     # kept for the fallback
         # a second call changes nothing and loses nothing
-        assert integ._patch_deform_conv() == (functions, layers)
-        assert dc._REFERENCE == {'modulated_deform_conv2d': mmcv_op, 'DCNv2': MmcvPack}
+        assert integ.apply_patches('deform_conv') == done
+        assert fb.REPLACED == {'modulated_deform_conv2d': mmcv_op, 'DCNv2': MmcvPack}
         # the captured op is what an unsupported setting falls back to
         x = torch.zeros(1, 8, 5, 5)
         with pytest.warns(RuntimeWarning, match='kernel_size'):
@@ -408,6 +409,6 @@ def test_patch_rebinds_stub_mmcv_modules_and_touches_nothing_when_absent(pkg):
                 sys.modules.pop(k, None)
             else:
                 sys.modules[k] = v
-        dc._REFERENCE.clear()
-        dc._REFERENCE.update(kept)
-        dc._WARNED.clear()
+        fb.REPLACED.clear()
+        fb.REPLACED.update(kept)
+        fb.WARNED.clear()

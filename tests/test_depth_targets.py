@@ -149,7 +149,8 @@ def test_patch_rebinds_only_loaded_modules(pkg, dt):
     try:
         for k in names:
             sys.modules.pop(k, None)
-        assert integ._patch_depth_targets() == [] and not any(k in sys.modules for k in names)
+        nothing = {'modules': [], 'functions': [], 'methods': []}
+        assert integ.apply_patches('depth_targets') == nothing and not any(k in sys.modules for k in names)
         for k in names:
             m = types.ModuleType(k)
             m.__path__ = []
@@ -159,16 +160,16 @@ def test_patch_rebinds_only_loaded_modules(pkg, dt):
         sys.modules[names[8]].points_in_boxes_part = sys.modules[names[8]].points_in_boxes_all = old
         sys.modules[names[8]].box_iou_rotated = old
         sys.modules[names[11]].points_in_boxes_part = old
-        done = integ._patch_depth_targets()
-        assert done == [f'{names[4]}.depth_map_in_boxes_cpu', f'{names[8]}.points_in_boxes_part',
-                        f'{names[8]}.points_in_boxes_all', f'{names[11]}.points_in_boxes_part']
+        done = integ.apply_patches('depth_targets')
+        assert done == dict(nothing, functions=[f'{names[4]}.depth_map_in_boxes_cpu', f'{names[8]}.points_in_boxes_part',
+                                                f'{names[8]}.points_in_boxes_all', f'{names[11]}.points_in_boxes_part'])
         assert sys.modules[names[4]].depth_map_in_boxes_cpu is dt.depth_map_in_boxes
         assert sys.modules[names[8]].points_in_boxes_part is dt.points_in_boxes_part
         assert sys.modules[names[8]].points_in_boxes_all is dt.points_in_boxes_all
         assert sys.modules[names[11]].points_in_boxes_part is dt.points_in_boxes_part
         assert sys.modules[names[8]].box_iou_rotated is old
         assert not hasattr(sys.modules[names[11]], 'points_in_boxes_all')
-        assert 'mmdet3d.datasets.utils' not in sys.modules and integ._patch_depth_targets() == done
+        assert 'mmdet3d.datasets.utils' not in sys.modules and integ.apply_patches('depth_targets') == done
     finally:
         for k, v in before.items():
             if v is None:

@@ -35,11 +35,12 @@ def cv():
 
 @pytest.fixture()
 def policy(cv):
+    warned = importlib.import_module('depth-from-motion_amd.fallback').WARNED
     prev = cv.fallback_policy()
-    cv._WARNED.clear()
+    warned.clear()
     yield cv
     cv.set_fallback_policy(prev)
-    cv._WARNED.clear()
+    warned.clear()
 
 
 def _kitti_model():

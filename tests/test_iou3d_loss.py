@@ -193,14 +193,15 @@ def test_patch_reference_rebinds_the_loaded_loss_module(pkg):
     try:
         for k in chain:
             sys.modules.pop(k, None)
-        assert integ._patch_iou_functions() == [] and name not in sys.modules
+        nothing = {'modules': [], 'functions': [], 'methods': []}
+        assert integ.apply_patches('iou') == nothing and name not in sys.modules
         for k in chain:
             m = types.ModuleType(k)
             m.__path__ = []
             sys.modules[k] = m
         sys.modules[name].diff_iou_rotated_3d = old
-        done = integ._patch_iou_functions()                       # what patch_reference adds to its report
-        assert done == [name + '.diff_iou_rotated_3d']
+        done = integ.apply_patches('iou')                         # what patch_reference adds to its report
+        assert done == dict(nothing, functions=[name + '.diff_iou_rotated_3d'])
         assert sys.modules[name].diff_iou_rotated_3d is pkg.diff_iou_rotated_3d
         assert not hasattr(sys.modules['mmdet3d.models.losses'], 'diff_iou_rotated_3d')
     finally:

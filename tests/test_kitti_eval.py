@@ -375,10 +375,11 @@ def test_patch_reference_rebinds_only_loaded_modules(pkg, ke):
              'mmdet3d.core.evaluation.kitti_utils.eval', 'mmdet3d.core.evaluation.kitti_utils.rotate_iou')
     before = {k: sys.modules.get(k) for k in names}
     old = lambda *a, **k: 'reference'                                         # noqa: E731
+    nothing = {'modules': [], 'functions': [], 'methods': []}
     try:
         for k in names:
             sys.modules.pop(k, None)
-        assert integ._patch_kitti_eval() == [] and not any(k in sys.modules for k in names)
+        assert integ.apply_patches('kitti_eval') == nothing and not any(k in sys.modules for k in names)
         for k in names:
             m = types.ModuleType(k)
             m.__path__ = []
@@ -388,14 +389,15 @@ def test_patch_reference_rebinds_only_loaded_modules(pkg, ke):
             sys.modules[k].kitti_eval = old
         sys.modules[names[4]].kitti_eval_coco_style = old
         sys.modules[names[5]].rotate_iou_gpu_eval = old
-        done = integ._patch_kitti_eval()
-        assert done == [f'{k}.kitti_eval' for k in (names[4], names[3], names[2])] + [f'{names[5]}.rotate_iou_gpu_eval']
+        done = integ.apply_patches('kitti_eval')
+        assert done == dict(nothing, functions=[f'{k}.kitti_eval' for k in (names[4], names[3], names[2])] +
+                            [f'{names[5]}.rotate_iou_gpu_eval'])
         for k in names[2:5]:
             assert sys.modules[k].kitti_eval is pkg.kitti_eval
         assert sys.modules[names[5]].rotate_iou_gpu_eval is pkg.rotate_iou_eval
         assert sys.modules[names[4]].kitti_eval_coco_style is old and 'mmdet3d.core' not in sys.modules
         assert not hasattr(sys.modules[names[5]], 'kitti_eval')
-        assert integ._patch_kitti_eval() == done                              # twice: the same report
+        assert integ.apply_patches('kitti_eval') == done                           # twice: the same report
     finally:
         for k, v in before.items():
             if v is None:

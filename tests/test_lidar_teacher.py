@@ -348,18 +348,19 @@ def test_cpu_tensors_training_mode_and_grad_inputs_are_refused(pkg):
 
 def test_patch_rebinds_stub_modules_and_touches_nothing_when_absent(pkg):
     integ = importlib.import_module('depth-from-motion_amd.integration')
-    sc = importlib.import_module('depth-from-motion_amd.sparse_conv')
+    fb = importlib.import_module('depth-from-motion_amd.fallback')
+    nothing = {'modules': [], 'functions': [], 'methods': []}
     chain = ('mmcv', 'mmcv.ops', 'mmcv.cnn', 'mmdet3d', 'mmdet3d.ops', 'mmdet3d.models',
              'mmdet3d.models.middle_encoders', 'mmdet3d.models.middle_encoders.sparse_encoder',
              'mmdet3d.models.detectors', 'mmdet3d.models.detectors.dfm')
     before = {k: sys.modules.get(k) for k in chain}
-    kept = dict(sc._REFERENCE)
+    kept = dict(fb.REPLACED)
     try:
         for k in chain:
             sys.modules.pop(k, None)
-        sc._REFERENCE.clear()
-        assert integ._patch_lidar_teacher() == ([], [], []) and not any(k in sys.modules for k in chain)
-        assert sc._REFERENCE == {}
+        fb.REPLACED.clear()
+        assert integ.apply_patches('lidar_teacher') == nothing and not any(k in sys.modules for k in chain)
+        assert fb.REPLACED == {}
 
         class Registry:
             def __init__(self):
@@ -398,11 +399,12 @@ def test_patch_rebinds_stub_modules_and_touches_nothing_when_absent(pkg):
         sys.modules['mmdet3d.ops'].make_sparse_convmodule = ref_make
         sys.modules['mmdet3d.models.middle_encoders.sparse_encoder'].make_sparse_convmodule = ref_make
         sys.modules['mmdet3d.models.detectors.dfm'].DfM = DfM
-        functions, layers, methods = integ._patch_lidar_teacher()
-        assert functions == ['mmcv.ops.Voxelization', 'mmcv.ops.SubMConv3d', 'mmdet3d.ops.make_sparse_convmodule',
-                             'mmdet3d.models.middle_encoders.sparse_encoder.make_sparse_convmodule']
-        assert layers == ['SubMConv3d (mmcv CONV_LAYERS)', 'SparseConv3d (mmcv CONV_LAYERS)']
-        assert methods == ['DfM.extract_lidar_model_feat']
+        done = integ.apply_patches('lidar_teacher')
+        assert set(done) == set(nothing)
+        assert done['functions'] == ['mmcv.ops.Voxelization', 'mmcv.ops.SubMConv3d', 'mmdet3d.ops.make_sparse_convmodule',
+                                     'mmdet3d.models.middle_encoders.sparse_encoder.make_sparse_convmodule']
+        assert done['modules'] == ['SubMConv3d (mmcv CONV_LAYERS)', 'SparseConv3d (mmcv CONV_LAYERS)']
+        assert done['methods'] == ['DfM.extract_lidar_model_feat']
         assert sys.modules['mmcv.ops'].Voxelization is pkg.Voxelization
         assert sys.modules['mmcv.ops'].SubMConv3d is pkg.SubMConv3d and sys.modules['mmcv.ops'].nms is other
         assert reg.table['SubMConv3d'] is pkg.SubMConv3d and reg.table['SparseConv3d'] is pkg.SparseConv3d
@@ -413,9 +415,9 @@ def test_patch_rebinds_stub_modules_and_touches_nothing_when_absent(pkg):
                 'CONV_LAYERS.SubMConv3d': MmcvSubM, 'mmdet3d.ops.make_sparse_convmodule': ref_make,
                 'mmdet3d.models.middle_encoders.sparse_encoder.make_sparse_convmodule': ref_make,
                 'DfM.extract_lidar_model_feat': ref_method}
-        assert sc._REFERENCE == want                                # what was replaced is kept
+        assert fb.REPLACED == want                                  # what was replaced is kept
         # a second call changes nothing and loses nothing
-        assert integ._patch_lidar_teacher() == (functions, layers, methods) and sc._REFERENCE == want
+        assert integ.apply_patches('lidar_teacher') == done and fb.REPLACED == want
         # a teacher built from classes that are not this package's keeps the reference's method
         det = DfM()
         det.lidar_model = types.SimpleNamespace(voxel_layer=MmcvVoxelization())
@@ -426,8 +428,8 @@ def test_patch_rebinds_stub_modules_and_touches_nothing_when_absent(pkg):
                 sys.modules.pop(k, None)
             else:
                 sys.modules[k] = v
-        sc._REFERENCE.clear()
-        sc._REFERENCE.update(kept)
+        fb.REPLACED.clear()
+        fb.REPLACED.update(kept)
 
 
 def test_the_fixture_is_small_and_whole(pkg):
