@@ -35,6 +35,7 @@ from .bbox_decode import (HipAnchor3DHeadMixin, anchor3d_get_bboxes, anchor_head
                           delta_xyzwlhr_decode)
 from .anchor_loss import HipAnchor3DLossMixin, anchor3d_loss  # noqa: F401
 from .atss_target import BboxOverlaps2D, HipATSSTargetMixin, atss_target_2d, bbox_overlaps  # noqa: F401
+from .atss_loss import HipATSSLossMixin, atss_loss_2d  # noqa: F401
 from .deform_conv import (ModulatedDeformConv2d, ModulatedDeformConv2dPack, deform_sample,  # noqa: F401
                           modulated_deform_conv2d)
 from .voxelize import HardSimpleVFE, Voxelization, hard_voxelize, hard_voxelize_batch  # noqa: F401
@@ -70,4 +71,5 @@ __all__ = ['build_dfm_cost', 'plane_sweep_grid', 'point_sample', 'mv_feature_tra
            'bev_box_overlap', 'd3_box_overlap', 'image_box_overlap', 'calculate_iou_partly', 'eval_class', 'get_mAP11',
            'get_mAP40', 'do_eval', 'kitti_eval', 'generate_depth_map', 'depth_map_in_boxes', 'generate_depth_targets',
            'points_in_boxes_part', 'points_in_boxes_all', 'points_in_boxes_idmap', 'GenerateDepthMap', 'DfMDepthTargetMixin',
-           'FusedAdamW', 'clip_grad_norm_', 'anchor3d_loss', 'HipAnchor3DLossMixin']
+           'FusedAdamW', 'clip_grad_norm_', 'anchor3d_loss', 'HipAnchor3DLossMixin', 'atss_loss_2d',
+           'HipATSSLossMixin']

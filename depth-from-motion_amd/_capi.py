@@ -208,6 +208,17 @@ class AtssTargetDesc(ctypes.Structure):
                                            ('target_means', ctypes.c_float * 4), ('target_stds', ctypes.c_float * 4)]
 
 
+class AtssLossDesc(ctypes.Structure):
+    """struct dfm_atss_loss_desc"""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        'batch', 'num_levels', 'num_anchors', 'num_classes', 'reg_class_agnostic', 'dtype', 'reg_dtype', 'reserved')] + \
+        [('gamma', ctypes.c_float), ('alpha', ctypes.c_float), ('target_means', ctypes.c_float * 4),
+         ('target_stds', ctypes.c_float * 4)] + \
+        [(n, ctypes.c_int32 * ATSS_MAX_LEVELS) for n in ('h', 'w', 'row_offset', 'reserved_levels')] + \
+        [(n, ctypes.c_int64 * (ATSS_MAX_LEVELS * 4)) for n in ('cls_stride', 'reg_stride', 'ctr_stride',
+                                                               'grad_cls_stride', 'grad_reg_stride', 'grad_ctr_stride')]
+
+
 class DeformDesc(ctypes.Structure):
     """struct dfm_deform_desc"""
     _fields_ = [(n, ctypes.c_int32) for n in (
@@ -269,7 +280,7 @@ STRUCTS = {
     'dfm_anchor_head_desc': AnchorHeadDesc, 'dfm_atss_target_desc': AtssTargetDesc, 'dfm_deform_desc': DeformDesc,
     'dfm_voxel_desc': VoxelDesc, 'dfm_sparse_conv_desc': SparseConvDesc, 'dfm_sparse_conv_plan': SparseConvPlan,
     'dfm_depth_targets_desc': DepthTargetsDesc, 'dfm_optim_tensor': OptimTensor,
-    'dfm_anchor_loss_desc': AnchorLossDesc,
+    'dfm_anchor_loss_desc': AnchorLossDesc, 'dfm_atss_loss_desc': AtssLossDesc,
 }
 
 # DFM_SPARSE_STATUS_*: bits of the device status word of the sparse-convolution index kernels
@@ -311,7 +322,7 @@ def _binding():
     vsp, vmp, cp, wp, lp = P(VsDesc), P(VsMvDesc), P(Conv3dDesc), P(Conv3dWgradDesc), P(DepthLossDesc)
     ip, atp, ahp, adp, ddp = P(ImitationDesc), P(AnchorTargetDesc), P(AnchorHeadDesc), P(AtssTargetDesc), P(DeformDesc)
     vdp, sdp, plp, i32p, i64p = P(VoxelDesc), P(SparseConvDesc), P(SparseConvPlan), P(i32), P(i64)
-    dtp, alp = P(DepthTargetsDesc), P(AnchorLossDesc)
+    dtp, alp, slp = P(DepthTargetsDesc), P(AnchorLossDesc), P(AtssLossDesc)
     return {
         'dfm_hip.h': _table(
             ('dfm_version', ci, []),
@@ -511,6 +522,13 @@ def _binding():
             ('dfm_anchor3d_loss_workspace_bytes', sz, [alp]),
             ('dfm_anchor3d_loss_fwd', ci, [alp, vp, vp, vp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp, sz, vp]),
             ('dfm_anchor3d_loss_bwd', ci, [alp, vp, vp, vp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp, vp, vp, vp]),
+        ),
+        # the 2-D ATSS head's loss over all levels: focal, centerness-weighted GIoU and centerness terms; the maps and
+        # their gradients come as HOST arrays of 3 L device pointers
+        'dfm_hip_atss_loss.h': _table(
+            ('dfm_atss_loss_workspace_bytes', sz, [slp]),
+            ('dfm_atss_loss_fwd', ci, [slp, pp, fp, fp, fp, fp, fp, vp, sz, vp]),
+            ('dfm_atss_loss_bwd', ci, [slp, pp, fp, fp, fp, fp, fp, pp, vp]),
         ),
     }
 

@@ -170,6 +170,38 @@ def _kind(obj):
     return obj.get('type') if isinstance(obj, dict) else type(obj).__name__
 
 
+def head_dense_targets(head, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_labels_list):
+    """``atss_target_2d`` for a head's lists, as ``HipATSSTargetMixin.get_targets`` and ``HipATSSLossMixin.loss`` (the
+    next step of the same path) call it: the level-concatenated anchors of the first image, ``anchor_inside_flags`` of
+    every image at once on the device, the head's assigner, coder and ``train_cfg`` read by attribute.  Returns
+    ``(anchors (A, 4+), num_level_anchors, inside (B, A) bool, [labels, label_weights, bbox_targets, bbox_weights],
+    counts (B, 2) int32)``, everything on the device; nothing is copied to the host."""
+    levels = anchor_list[0]
+    num_level_anchors = [l.size(0) for l in levels]
+    anchors = torch.cat(list(levels)) if len(levels) > 1 else levels[0]
+    require_gpu(anchors, 'anchors')
+    train_cfg = head.train_cfg
+    border = _field(train_cfg, 'allowed_border', -1)
+    # anchor_inside_flags for every image at once, on the device
+    inside = torch.stack([torch.cat(list(flags)) if len(flags) > 1 else flags[0] for flags in valid_flag_list])
+    inside = inside.to(anchors.device).ne(0)
+    if border >= 0:
+        hw = upload(torch.tensor([[float(m['img_shape'][0]), float(m['img_shape'][1])] for m in img_metas],
+                                 dtype=torch.float32), anchors.device)
+        a = anchors.to(torch.float32)
+        inside = inside & ((a[:, 0] >= -border) & (a[:, 1] >= -border))[None] & \
+            (a[None, :, 2] < hw[:, 1:2] + border) & (a[None, :, 3] < hw[:, 0:1] + border)
+    assigner = head.assigner
+    width = 6 if _field(assigner, 'append_3d_centers', True) else 4
+    coder = head.bbox_coder
+    *dense, _, counts = atss_target_2d(
+        anchors[:, :4], num_level_anchors, [g[:, :width] for g in gt_bboxes_list], gt_labels_list,
+        topk=_field(assigner, 'topk', 9), num_classes=head.num_classes,
+        pos_weight=_field(train_cfg, 'pos_weight', -1), inside_flags=inside,
+        target_means=getattr(coder, 'means', (0., 0., 0., 0.)), target_stds=getattr(coder, 'stds', (1., 1., 1., 1.)))
+    return anchors, num_level_anchors, inside, dense, counts
+
+
 class HipATSSTargetMixin(object):
     """``ATSSHead.get_targets`` as ``LIGAATSSHead`` runs it (mmdet's method over ``LIGAATSSHead._get_target_single``,
     liga_atss_head.py:399-483) on the HIP path, for a head class ``class FastHead(HipATSSTargetMixin, LIGAATSSHead)``
@@ -229,29 +261,8 @@ class HipATSSTargetMixin(object):
             return run_reference(self, 'get_targets', why, 'ATSS-target',
                                  (anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list,
                                   gt_labels_list, label_channels, unmap_outputs), mixin=HipATSSTargetMixin)
-        levels = anchor_list[0]
-        num_level_anchors = [l.size(0) for l in levels]
-        anchors = torch.cat(list(levels)) if len(levels) > 1 else levels[0]
-        require_gpu(anchors, 'anchors')
-        train_cfg = self.train_cfg
-        border = _field(train_cfg, 'allowed_border', -1)
-        # anchor_inside_flags for every image at once, on the device
-        inside = torch.stack([torch.cat(list(flags)) if len(flags) > 1 else flags[0] for flags in valid_flag_list])
-        inside = inside.to(anchors.device).ne(0)
-        if border >= 0:
-            hw = upload(torch.tensor([[float(m['img_shape'][0]), float(m['img_shape'][1])] for m in img_metas],
-                                     dtype=torch.float32), anchors.device)
-            a = anchors.to(torch.float32)
-            inside = inside & ((a[:, 0] >= -border) & (a[:, 1] >= -border))[None] & \
-                (a[None, :, 2] < hw[:, 1:2] + border) & (a[None, :, 3] < hw[:, 0:1] + border)
-        assigner = self.assigner
-        width = 6 if _field(assigner, 'append_3d_centers', True) else 4
-        coder = self.bbox_coder
-        *dense, _, counts = atss_target_2d(
-            anchors[:, :4], num_level_anchors, [g[:, :width] for g in gt_bboxes_list], gt_labels_list,
-            topk=_field(assigner, 'topk', 9), num_classes=self.num_classes,
-            pos_weight=_field(train_cfg, 'pos_weight', -1), inside_flags=inside,
-            target_means=getattr(coder, 'means', (0., 0., 0., 0.)), target_stds=getattr(coder, 'stds', (1., 1., 1., 1.)))
+        anchors, num_level_anchors, inside, dense, counts = head_dense_targets(
+            self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_labels_list)
         pos_neg = counts.clamp(min=1).sum(0).tolist()        # the one host read (mmdet: max(inds.numel(), 1))
         kept = anchors[None] * inside[..., None].to(anchors.dtype)                # unmap: zero rows outside
         out = []

@@ -17,6 +17,7 @@
 // positives are a few hundred among half a million rows, so most waves never take that branch.
 // No atomics, no memset: the same bits run after run.
 #include "bbox_coder.h"
+#include "focal_loss.h"
 #include "iou3d_geom.h"
 
 using namespace dfm;
@@ -89,28 +90,7 @@ __device__ __forceinline__ void store(const Map &m, const Row &o, int ch, float 
     ((T *)m.p)[at(m, o, ch)] = elem<T>::store(v);
 }
 
-// sigmoid(|z|) and sigmoid(-|z|) from e = exp(-|z|): no subtraction, finite for every finite z
-__device__ __forceinline__ void sigmoid_pair(float e, float &big, float &small)
-{
-    big = __fdiv_rn(1.0f, 1.0f + e);
-    small = e * big;
-}
-
-// the focal term of one logit; grad = d value / d x
-template <bool GRAD>
-__device__ __forceinline__ float focal(float x, bool t, float gamma, float alpha, float &grad)
-{
-    const float e = expf(-fabsf(x));
-    float big, small;
-    sigmoid_pair(e, big, small);
-    const float p = x >= 0.0f ? big : small, q = x >= 0.0f ? small : big;     // sigmoid(x), 1 - sigmoid(x)
-    const float pt = t ? q : p, one_minus_pt = t ? p : q;
-    const float bce = (t ? fmaxf(-x, 0.0f) : fmaxf(x, 0.0f)) + log1pf(e);     // = max(x, 0) - x t + log1p(e)
-    const float aw = t ? alpha : 1.0f - alpha;
-    const float mod = gamma == 2.0f ? pt * pt : powf(pt, gamma);
-    if constexpr (GRAD) grad = (t ? -aw : aw) * mod * (gamma * one_minus_pt * bce + pt);
-    return aw * mod * bce;
-}
+// (sigmoid_pair and the focal term of one logit: csrc/focal_loss.h, shared with csrc/atss_loss.hip)
 
 // the cross entropy of two logits against class `one`; po = softmax probability of the OTHER class
 __device__ __forceinline__ float cross_entropy2(float d0, float d1, bool one, float &po)

@@ -18,7 +18,9 @@ Three ways to use this package from there, all routed to the HIP kernels:
    ``MultiViewDfMMixin.feature_transformation`` and, where ``train_mixins`` is already imported,
    ``AnchorTrainMixin.anchor_target_3d`` by ``HipAnchorTrainMixin.anchor_target_3d`` and, where ``anchor3d_head`` is,
    ``Anchor3DHead.get_bboxes`` by ``HipAnchor3DHeadMixin.get_bboxes`` and ``loss_single`` of ``Anchor3DHead`` and
-   of ``LIGAAnchor3DHead`` by ``HipAnchor3DLossMixin.loss_single``.  Where ``mmcv.ops`` is already imported its
+   of ``LIGAAnchor3DHead`` by ``HipAnchor3DLossMixin.loss_single``, and, where ``liga_atss_head`` is,
+   ``LIGAATSSHead.get_targets`` by ``HipATSSTargetMixin.get_targets`` and ``LIGAATSSHead.loss`` by
+   ``HipATSSLossMixin.loss``.  Where ``mmcv.ops`` is already imported its
    ``modulated_deform_conv2d`` is rebound and ``ModulatedDeformConv2dPack`` registered as ``'DCNv2'`` in mmcv's
    ``CONV_LAYERS``; likewise ``Voxelization``, ``SparseConvTensor``, ``SparseSequential`` and the layer types
    ``SubMConv3d`` / ``SparseConv3d`` of the LiDAR teacher (``LidarTeacher`` below), and
@@ -49,6 +51,7 @@ from .anchor_target import HipAnchorTrainMixin, bbox_overlaps_nearest_3d
 from .bbox_decode import HipAnchor3DHeadMixin
 from .anchor_loss import HipAnchor3DLossMixin
 from .atss_target import HipATSSTargetMixin
+from .atss_loss import HipATSSLossMixin
 from .deform_conv import ModulatedDeformConv2dPack, modulated_deform_conv2d
 from .sparse_conv import SparseConv3d, SparseConvTensor, SparseSequential, SubMConv3d, make_sparse_convmodule
 from .voxelize import Voxelization
@@ -584,6 +587,12 @@ PATCHES = {
     # liga_atss_head.py imports mmdet.
     'atss_target': [Method('mmdet3d.models.dense_heads.liga_atss_head', 'LIGAATSSHead', 'get_targets',
                            HipATSSTargetMixin, inherited=True)],
+    # the 2-D ATSS head's loss: LIGAATSSHead inherits loss from mmdet's ATSSHead and overrides loss_single; the class
+    # gets this package's loss (targets and all levels' terms without leaving the device), the inherited one is kept
+    # and still finds the reference's loss_single.  A group of its own: 'atss_target' reports get_targets alone.  Not
+    # loaded: liga_atss_head.py imports mmdet.
+    'atss_loss': [Method('mmdet3d.models.dense_heads.liga_atss_head', 'LIGAATSSHead', 'loss', HipATSSLossMixin,
+                         inherited=True)],
     # the backbone's deformable convolutions (the Waymo configs' ResNet-101 with dcn=dict(type='DCNv2')): mmcv's
     # function is rebound in the modules that hold it by name, and the Pack is registered as 'DCNv2' in mmcv's
     # CONV_LAYERS, which is where mmdet's ResNet builds its dcn layers from.  Not loaded: this package never imports

@@ -1390,6 +1390,9 @@ DFM_API int dfm_spp_tail_fwd(const dfm_spp_desc *desc, const void *const *pooled
 /* the 3-D anchor head's loss_single: focal, smooth-L1, direction and IoU terms over the head's maps in place
  * (dfm_anchor3d_loss_workspace_bytes, dfm_anchor3d_loss_fwd, dfm_anchor3d_loss_bwd): likewise */
 #include "dfm_hip_anchor_loss.h"
+/* the 2-D ATSS head's loss over all pyramid levels: focal, centerness-weighted GIoU and centerness terms over the
+ * head's maps in place (dfm_atss_loss_workspace_bytes, dfm_atss_loss_fwd, dfm_atss_loss_bwd): likewise */
+#include "dfm_hip_atss_loss.h"
 
 #ifdef __cplusplus
 }
