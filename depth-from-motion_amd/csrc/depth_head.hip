@@ -283,7 +283,9 @@ __global__ __launch_bounds__(256) void depth_head_bwd_kernel(
         const float b0 = lerp_fma(uw.w0, elem<T>::load(p0[o10]), uw.w1, elem<T>::load(p0[o11]));
         const float a1 = lerp_fma(uw.w0, elem<T>::load(p1[o00]), uw.w1, elem<T>::load(p1[o01]));
         const float b1 = lerp_fma(uw.w0, elem<T>::load(p1[o10]), uw.w1, elem<T>::load(p1[o11]));
-        return lerp_fma(ud.w0, lerp_fma(uh.w0, a0, uh.w1, b0), ud.w1, lerp_fma(uh.w0, a1, uh.w1, b1));
+        // rounded through the storage type, as the forward's softmax read it: p here is the forward's p
+        return elem<T>::load(elem<T>::store(
+            lerp_fma(ud.w0, lerp_fma(uh.w0, a0, uh.w1, b0), ud.w1, lerp_fma(uh.w0, a1, uh.w1, b1))));
     };
     const bool soft_path = gsoft || gpred;
     float mx = -INFINITY, sum = 0.0f, dotps = 0.0f;
@@ -361,7 +363,8 @@ __global__ __launch_bounds__(256) void depth_head_bwd_tile_kernel(
                 c1 = column(ud.i1);
                 have = ud.i0;
             }
-            return lerp_fma(ud.w0, c0, ud.w1, c1);
+            // rounded through the storage type, as the forward's softmax read it: p here is the forward's p
+            return elem<T>::load(elem<T>::store(lerp_fma(ud.w0, c0, ud.w1, c1)));
         };
         const size_t plane_o = (size_t)Ho * Wo;
         const size_t pix = (size_t)h * Wo + w;
