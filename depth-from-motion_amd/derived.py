@@ -7,11 +7,11 @@ tables.  All of it lives in a ``Derived`` cache, which makes three rules hold by
    matches a dead one) with the same version, address and device, and the non-tensor part of the key is equal.
 2. It is no part of a module's identity: a cache pickles and deep-copies as a new empty cache (``torch.save(model)``,
    EMA hooks, ``mp.spawn`` arguments), and the copy rebuilds on its first forward.
-3. A value is built lazily by the FIRST call that needs it, with kernels on that call's HIP stream.  A module that runs
+3. A value is built lazily by the FIRST call that needs it, with kernels on that call's HIP stream.  Work that runs
    on two streams (DfMStereoPath: one 2-D neck for the previous frame on a side stream and for the current frame on the
-   main stream) would let the second stream read what the first has not finished writing.  Every miss of a cache
-   bumps a counter; a caller that forks streams compares it around the first call and makes the other stream wait
-   when anything was built (integration.DfMStereoPath.forward).
+   main stream; the two stacks of DfMBackbone and DfMNeck, which share process-wide caches) would let the second
+   stream read what the first has not finished writing.  Every miss of a cache bumps a counter; streams.fork_join,
+   the only place that forks, reads it around every step and makes the other stream wait when anything was built.
 """
 import weakref
 

@@ -63,6 +63,7 @@ from .geometry import prepare_coordinates_3d, prepare_depth
 from .conv3d import MfmaConv3dTo1
 from .graphs import GraphedCallable
 from .plane_sweep import build_dfm_cost
+from .streams import fork_join
 from .point_sample import (mv_feature_transformation, point_sample, voxel_centers, voxel_sample,
                            voxel_sample_mv)
 
@@ -157,30 +158,10 @@ class DfMStereoPath(nn.Module):
     def forward(self, cur_feats, prev_feats, img_metas):
         # the two frames' 2-D necks are independent calls of the same module: at inference (eval mode: no running
         # statistics to update, nothing recorded) the previous frame's runs on a side HIP stream
-        if (self.two_streams and cur_feats[0].is_cuda and not torch.is_grad_enabled() and not self.training and
-                not torch.cuda.is_current_stream_capturing()):
-            from .modules import DfMBackbone
-            from .derived import derived_builds
-            d0 = cur_feats[0].device
-            main = torch.cuda.current_stream(d0)
-            side = DfMBackbone._side_streams.get(d0)
-            if side is None:
-                side = DfMBackbone._side_streams[d0] = torch.cuda.Stream(device=d0)
-            side.wait_stream(main)
-            built = derived_builds()
-            with torch.cuda.stream(side):
-                prev_stereo, _ = self._run_2d('neck_prev', self.neck, list(prev_feats))
-            if derived_builds() != built:
-                # the first call after a weight load / change built the neck's derived state (packed weights,
-                # folded norms) with kernels on the SIDE stream: the main-stream call finds the caches filled
-                # and would read them unordered.  That one forward runs the two frames back to back.
-                main.wait_stream(side)
-            cur_stereo, cur_sem = self._run_2d('neck_cur', self.neck, list(cur_feats))
-            main.wait_stream(side)
-            prev_stereo.record_stream(main)
-        else:
-            cur_stereo, cur_sem = self._run_2d('neck_cur', self.neck, list(cur_feats))
-            prev_stereo, _ = self._run_2d('neck_prev', self.neck, list(prev_feats))
+        (cur_stereo, cur_sem), (prev_stereo, _) = fork_join(
+            lambda: self._run_2d('neck_cur', self.neck, list(cur_feats)),
+            lambda: self._run_2d('neck_prev', self.neck, list(prev_feats)), cur_feats[0].device,
+            fork=self.two_streams and not torch.is_grad_enabled() and not self.training)
         dev = cur_stereo.device
         for meta in img_metas:  # dfm.py:288-293: (N-1,4,4) tensors on the device
             meta['cur2prevs'] = torch.as_tensor(np.asarray(meta['cur2prevs'], dtype=np.float32)

@@ -30,7 +30,7 @@ from torch import nn
 
 from .conv3d import (conv3d_to1_norm, long_axis_gram, MfmaConv2d, MfmaConv3d, MfmaConv3dG, MfmaConv3dTo1, MfmaConvTranspose2d,
                      MfmaConvTranspose3d, channel_slice, channel_split)
-from .derived import Derived, derived
+from .derived import Derived, derived, note_derived_build
 from .depth_head import depth_distribution_loss, depth_head_forward, depth_head_statistics
 from .frustum_to_voxel import frustum_to_voxel_sample
 from .geometry import stack_meta
@@ -40,6 +40,7 @@ from ._launch import DTYPES, STREAM, WS, launch, pointers
 from .plane_sweep import build_dfm_cost
 from .sweep_conv import pack_sweep_conv_weights, sweep_conv_supported, sweep_dres0
 from .registry import register_module
+from .streams import drain, fork_join, may_fork
 
 
 def _on_device(owner, name, device):
@@ -267,12 +268,7 @@ class hourglass(nn.Module):  # noqa: N801  (reference class name)
         """forward with ``out_residual`` added to the first output (DfMBackbone's
         ``cost = cost + hourglass(cost)[0]``, dfm_backbone.py:180-183).  GroupNorm, the residual adds
         and the ReLUs that follow them are one pass of the fused kernel each."""
-        steps = self.forward_add_steps(x, presqu, postsqu, out_residual)
-        while True:
-            try:
-                next(steps)
-            except StopIteration as done:
-                return done.value
+        return drain(self.forward_add_steps(x, presqu, postsqu, out_residual))
 
     def forward_add_steps(self, x, presqu, postsqu, out_residual):
         """``forward_add`` as a generator that yields after every layer (conv + norm: four launches) and returns the
@@ -342,37 +338,12 @@ class DfMBackbone(nn.Module):
     def init_weights(self):
         pass
 
-    @staticmethod
-    def _aggregate(first, second, hgs, x):
-        return DfMBackbone._aggregate_rest(second, hgs, first(x))
-
-    @staticmethod
-    def _aggregate_rest(second, hgs, cost):
-        cost = second(cost, residual=cost)
-        outs = []
-        for hg in hgs:
-            cost, _, _ = hg.forward_add(cost, None, None, cost)  # cost + hourglass(cost)[0]
-            outs.append(cost)
-        return outs if outs else [cost]
-
-    # The stereo and the mono aggregation stacks (dfm_backbone.py:175-183 / 189-198) share nothing until
-    # `_predict`: at inference they run on TWO HIP streams (round 5).  Each stack is a chain of ~30 launches --
-    # full-resolution convolutions that leave a quarter of the CUs idle in their second round of workgroups,
-    # hourglass levels of 250 workgroups (half a chip), GroupNorm passes -- and the other stack's kernels fill
-    # what one leaves free.  The side stream waits for what the main stream has produced so far, the main stream
-    # joins it before the prediction heads; scratch is per (device, stream) (_launch.Workspace) and the
-    # side stream's results are handed to the main stream with record_stream.  two_streams = False pins one stream.
+    # The stereo and the mono aggregation stacks (dfm_backbone.py:175-183 / 189-198) share nothing until `_predict`:
+    # they run on TWO HIP streams (streams.fork_join; `forward` says in which order).  Each stack is a chain of ~30
+    # launches -- full-resolution convolutions that leave a quarter of the CUs idle in their second round of
+    # workgroups, hourglass levels of 250 workgroups (half a chip), GroupNorm passes -- and the other stack's kernels
+    # fill what one leaves free.  two_streams = False pins one stream.
     two_streams = True
-    # With autograd recording: every backward node runs on the stream its forward ran on (the engine inserts the
-    # cross-stream waits), so the two stacks overlap in the backward pass as well (backbone_train 12.5 -> 10.7 ms,
-    # profiles/archive/r05_c16_*).  The mono stack's PARAMETER gradients, however, must not be produced on the side stream:
-    # gradient hooks (DistributedDataParallel's reducer, GradientBucketReducer) run under the stream of the
-    # AccumulateGrad node and order their bucket copies / collectives against that stream only.  An AccumulateGrad
-    # node takes the stream that is current when it is CREATED, so `_two_branches` creates the mono parameters'
-    # nodes on the main stream before it forks (`_pin_accumulators`): the weight-gradient kernels still run on the
-    # side stream, the accumulation -- and every hook -- on the main stream behind the engine's event wait
-    # (tests/test_backward_gpu.py checks the stream the hooks see).  two_streams = False pins one stream here too.
-    _side_streams = {}
 
     def _stack_steps(self, first, second, hgs, pred):
         """one aggregation stack + its prediction head as a generator: ``first()`` produces the stack's input (the
@@ -390,66 +361,6 @@ class DfMBackbone(nn.Module):
         outs = outs if outs else [cost]
         assert len(outs) == 1, 'Only support num_hg=1 for now.'
         return outs, self._pred_head(pred, outs[0])
-
-    def _two_stacks_interleaved(self, stereo_first, mono_first, device):
-        """Inference: the two stacks on two HIP streams with their layers ISSUED ALTERNATELY (round 6).  A layer costs
-        the host 20-27 us to enqueue (tools/host_overhead_probe.py) against 15-60 us on the device, and round 5
-        enqueued the whole mono stack (~0.5 ms of host time) before the first stereo launch: the main stream sat idle
-        behind the fused sweep for as long, and the forward took sweep + host(mono) + stereo.  Alternating the two
-        generators keeps both streams fed from the start."""
-        main = torch.cuda.current_stream(device)
-        side = DfMBackbone._side_streams.get(device)
-        if side is None:
-            side = DfMBackbone._side_streams[device] = torch.cuda.Stream(device=device)
-        side.wait_stream(main)
-        gens = [(side, self._stack_steps(mono_first, self.dres1_mono, self.hg_mono, self.pred_mono[0])),
-                (main, self._stack_steps(stereo_first, self.dres1, self.hg_stereo, self.pred_stereo[0]))]
-        results = {}
-        try:
-            while gens:
-                for item in list(gens):
-                    st, gen = item
-                    torch.cuda.set_stream(st)
-                    try:
-                        next(gen)
-                    except StopIteration as done:
-                        results[st is side] = done.value
-                        gens.remove(item)
-        finally:
-            torch.cuda.set_stream(main)
-        (mono, m_cost), (stereo, s_cost) = results[True], results[False]
-        main.wait_stream(side)
-        for t in list(mono) + [m_cost]:
-            t.record_stream(main)
-        return (stereo, s_cost), (mono, m_cost)
-
-    def _two_branches(self, stereo_fn, mono_fn, device):
-        # each branch ends with its own prediction head (dfm_backbone.py:120-127): -> (features, cost)
-        def stereo_all():
-            st = stereo_fn()
-            assert len(st) == 1, 'Only support num_hg=1 for now.'
-            return st, self._pred_head(self.pred_stereo[0], st[0])
-
-        def mono_all():
-            mo = mono_fn()
-            assert len(mo) == 1, 'Only support num_hg=1 for now.'
-            return mo, self._pred_head(self.pred_mono[0], mo[0])
-        if not (self.two_streams and device.type == 'cuda' and not torch.cuda.is_current_stream_capturing()):
-            return stereo_all(), mono_all()
-        main = torch.cuda.current_stream(device)
-        side = DfMBackbone._side_streams.get(device)
-        if side is None:
-            side = DfMBackbone._side_streams[device] = torch.cuda.Stream(device=device)
-        pins = self._pin_accumulators() if torch.is_grad_enabled() else None
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            mono, m_cost = mono_all()
-        del pins  # (the recorded graph holds the nodes from here on)
-        stereo, s_cost = stereo_all()
-        main.wait_stream(side)
-        for t in list(mono) + [m_cost]:
-            t.record_stream(main)
-        return (stereo, s_cost), (mono, m_cost)
 
     # False keeps the three-launch prediction head at inference too (the reference of the fused head's tests)
     fused_pred = True
@@ -470,19 +381,21 @@ class DfMBackbone(nn.Module):
             return conv3d_to1_norm(y, partials, gamma, beta, norm.eps, last.weight, relu=True)
         return seq(x)
 
-    def _interleave_ok(self, device):
-        return (self.two_streams and device.type == 'cuda' and
-                not torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing())
-
     def _pin_accumulators(self):
-        """views of the mono stack's trainable parameters taken on the CURRENT (main) stream: each creates the
-        parameter's AccumulateGrad node, which keeps the stream it was created under; holding the views keeps the
-        nodes alive until the side-stream forward has linked them into the graph"""
+        """views of the mono stack's trainable parameters taken on the CURRENT (main) stream, before the fork.  Every
+        backward node runs on the stream its forward ran on (the engine inserts the cross-stream waits), so the two
+        stacks overlap in the backward pass as well (backbone_train 12.5 -> 10.7 ms, profiles/archive/r05_c16_*).  The
+        mono stack's PARAMETER gradients, however, must not be produced on the side stream: gradient hooks
+        (DistributedDataParallel's reducer, GradientBucketReducer) run under the stream of the AccumulateGrad node and
+        order their bucket copies / collectives against that stream only.  An AccumulateGrad node takes the stream that
+        is current when it is CREATED, and each view creates its parameter's node: the weight-gradient kernels still
+        run on the side stream, the accumulation -- and every hook -- on the main stream behind the engine's event wait
+        (tests/test_backward_gpu.py checks the stream the hooks see).  Holding the views keeps the nodes alive until the
+        side-stream forward has linked them into the graph."""
         # (torch >= 2.10 notes once per process that these nodes' stream differs from their producers': intended --
         #  the engine's event wait orders them; the process-wide switch for that note is left to the application)
         return [p.view_as(p) for m in (self.dres0_mono, self.dres1_mono, self.hg_mono, self.pred_mono)
                 for p in m.parameters() if p.requires_grad]
-
 
     def _sweep_dres0_fusable(self, cur, prev=None):
         """the fused plane sweep + dres0 / dres0_mono kernel takes this call: inference, bf16 32-channel
@@ -514,34 +427,32 @@ class DfMBackbone(nn.Module):
                 self.feat_sample_factor, self.cost_sample_factor, ori_cam2imgs, cur2prevs[:, 0],
                 meta0['ori_shape'][:2], self._sweep_conv_packed(), meta0.get('flip', False), meta0['crop_offset'],
                 img_scale_factor=meta0.get('scale_factor', [1.0])[0])
-            if self._interleave_ok(ys.device):
-                stereo, mono = self._two_stacks_interleaved(
-                    lambda: self.dres0.gn(ys, relu=True, partials=ps),
-                    lambda: self.dres0_mono.gn(ym, relu=True, partials=pm), ys.device)
-                return self._predict(*stereo, *mono)
-            stereo, mono = self._two_branches(
-                lambda: self._aggregate_rest(self.dres1, self.hg_stereo, self.dres0.gn(ys, relu=True, partials=ps)),
-                lambda: self._aggregate_rest(self.dres1_mono, self.hg_mono,
-                                             self.dres0_mono.gn(ym, relu=True, partials=pm)), ys.device)
-            return self._predict(*stereo, *mono)
-        # plane sweep: HIP kernel (reference: build_dfm_cost, batch semantics per sample)
-        cost_raw = build_dfm_cost(
-            cur_stereo_feats, prev_stereo_feats,
-            _on_device(self, 'downsampled_depth', cur_stereo_feats.device), self.feat_sample_factor,
-            self.cost_sample_factor, ori_cam2imgs, cur2prevs[:, 0], meta0['ori_shape'][:2],
-            meta0.get('flip', False), meta0['crop_offset'],
-            img_scale_factor=meta0.get('scale_factor', [1.0])[0],
-            memory_format=self.volume_memory_format)
-        # the volume's two consumers: dres0 (whole) and dres0_mono (the cur half) -- one autograd node whose backward adds
-        # the half's gradient into a copy of the whole volume's (conv3d.channel_split)
-        cost_all, cost_cur = channel_split(cost_raw, 0, self.in_channels)
-        if self._interleave_ok(cost_raw.device):
-            stereo, mono = self._two_stacks_interleaved(
-                lambda: self.dres0(cost_all), lambda: self.dres0_mono(cost_cur), cost_raw.device)
-            return self._predict(*stereo, *mono)
-        stereo, mono = self._two_branches(
-            lambda: self._aggregate(self.dres0, self.dres1, self.hg_stereo, cost_all),
-            lambda: self._aggregate(self.dres0_mono, self.dres1_mono, self.hg_mono, cost_cur), cost_raw.device)
+            stereo_first, mono_first = (lambda: self.dres0.gn(ys, relu=True, partials=ps),
+                                        lambda: self.dres0_mono.gn(ym, relu=True, partials=pm))
+        else:
+            # plane sweep: HIP kernel (reference: build_dfm_cost, batch semantics per sample)
+            cost_raw = build_dfm_cost(
+                cur_stereo_feats, prev_stereo_feats,
+                _on_device(self, 'downsampled_depth', cur_stereo_feats.device), self.feat_sample_factor,
+                self.cost_sample_factor, ori_cam2imgs, cur2prevs[:, 0], meta0['ori_shape'][:2],
+                meta0.get('flip', False), meta0['crop_offset'],
+                img_scale_factor=meta0.get('scale_factor', [1.0])[0],
+                memory_format=self.volume_memory_format)
+            # the volume's two consumers: dres0 (whole) and dres0_mono (the cur half) -- one autograd node whose backward adds
+            # the half's gradient into a copy of the whole volume's (conv3d.channel_split)
+            cost_all, cost_cur = channel_split(cost_raw, 0, self.in_channels)
+            stereo_first, mono_first = (lambda: self.dres0(cost_all)), (lambda: self.dres0_mono(cost_cur))
+        # Inference: the layers of the two stacks are issued ALTERNATELY (round 6).  A layer costs the host 20-27 us to
+        # enqueue (tools/host_overhead_probe.py) against 15-60 us on the device; enqueueing the whole mono stack first
+        # (~0.5 ms of host time) left the main stream idle behind the sweep for as long.  With autograd recording the
+        # mono stack is issued to its end first, its AccumulateGrad nodes pinned to the main stream.
+        grad, device = torch.is_grad_enabled(), cur_stereo_feats.device
+        pins = self._pin_accumulators() if grad and self.two_streams and may_fork(device) else None
+        stereo, mono = fork_join(
+            self._stack_steps(stereo_first, self.dres1, self.hg_stereo, self.pred_stereo[0]),
+            self._stack_steps(mono_first, self.dres1_mono, self.hg_mono, self.pred_mono[0]),
+            device, fork=self.two_streams, alternate=not grad)
+        del pins  # (the recorded graph holds the nodes from here on)
         return self._predict(*stereo, *mono)
 
     # fused_gate = False keeps the torch sequence of the gate at inference too, mfma_gate = False the VALU kernel for
@@ -845,18 +756,10 @@ class DfMNeck(nn.Module):
         # the mono and the stereo stacks (dfm_neck.py:108-111) are independent: two HIP streams at inference, like
         # DfMBackbone's branches (the stacks' launches are 4.2 rounds of workgroups each: one fills the other's
         # last round); two_streams = False pins one stream
-        if (self.two_streams and x.is_cuda and not torch.is_grad_enabled() and
-                not torch.cuda.is_current_stream_capturing()):
-            main = torch.cuda.current_stream(x.device)
-            side = DfMBackbone._side_streams.get(x.device)
-            if side is None:
-                side = DfMBackbone._side_streams[x.device] = torch.cuda.Stream(device=x.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                mono = _to_bev(self.mono_layers(channel_slice(x, 0, self.in_channels[0])))
-            stereo = _to_bev(self.stereo_layers(x))
-            main.wait_stream(side)
-            mono.record_stream(main)
+        if self.two_streams and not torch.is_grad_enabled() and may_fork(x.device):
+            stereo, mono = fork_join(lambda: _to_bev(self.stereo_layers(x)),
+                                     lambda: _to_bev(self.mono_layers(channel_slice(x, 0, self.in_channels[0]))),
+                                     x.device)
         else:
             x_all, x_mono = channel_split(x, 0, self.in_channels[0])   # (one backward node for the two uses of x)
             mono = _to_bev(self.mono_layers(x_mono))
@@ -1060,6 +963,7 @@ def _channels_last_2d(module, feats):
                                           m.weight.shape[0] if isinstance(m, MfmaConv2d) else m.weight.shape[1],
                                           tuple(m.weight.shape[2:]), m.stride, m.padding):
                     m.weight.data = m.weight.data.contiguous()
+        note_derived_build()  # (the copies ran on the caller's stream: streams.fork_join orders the other stream)
         module.__dict__['_weights_format'] = want
         module.__dict__['_weights_channels_last'] = nhwc
     if not nhwc:

@@ -401,7 +401,7 @@ def test_backbone_two_streams_in_training_hooks_see_the_main_stream(pkg):
 
     assert m.two_streams
     g2 = run(True)
-    assert mods.DfMBackbone._side_streams.get(dev) is not None, 'the side stream was never used'
+    assert pkg.streams._side_streams.get(dev) is not None, 'the side stream was never used'
     off = [n for n, ok in seen.items() if not ok]
     assert seen and not off, f'hooks ran off the main stream for {off[:4]}'
     assert any(n.startswith('dres1_mono') for n in seen) and any(n.startswith('hg_mono') for n in seen)

@@ -1,6 +1,6 @@
 """Every value kept in a ``derived.Derived`` cache follows its source on the GPU: forward, change the source in place,
 forward again -- the result equals BIT FOR BIT that of a fresh module (or functional call) that never saw the old value,
-``derived_builds()`` advanced during that forward (what makes DfMStereoPath order its two streams) and does not
+``derived_builds()`` advanced during that forward (what makes streams.fork_join order its two streams) and does not
 advance during a third, unchanged one.  One case per cache site, at the smallest input its kernel takes."""
 import gc
 import importlib
