@@ -317,8 +317,12 @@ def _check_backward(pkg, B, C, H, W, D, fsf, csf, crop, seed, img_shape, dtype=t
 
 
 def test_backward_matches_torch_cpu_autograd(pkg):
-    """strided sweep (cost_sample_factor 2): lane-per-point scatter kernel"""
+    """strided sweep (cost_sample_factor 2), six channels: the default backward dispatch, i.e. the LDS-atomic tile
+    kernel on a strided lattice (id 5).  The ``kernel_mode`` fixture's ``launch_options`` are thread-local and never
+    reach the autograd thread that runs the backward (tests/test_host_logic_round3.py), so every mode of this file
+    takes that same kernel; the scatter kernel (id 1) is pinned in tests/test_sweep_bwd_exact_gpu.py."""
     _check_backward(pkg, 2, 6, 20, 64, 3, 8, 2, (3, 5), 5, (375, 1242))
+    assert pkg._capi.lib().dfm_plane_sweep_bwd_last_kernel() == 5
 
 
 @pytest.mark.parametrize('case', [
